@@ -1,11 +1,14 @@
 """bench.py -- headline benchmark of the MI355X hot path (contract: see the task statement / DESIGN.md 'Measurement').
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                             (everything below the timed steps as well: see `--full`)
+    python bench.py ... --dump-outputs DIR                 (after the timed steps: what the last step computed, DIR/<name>.npy)
 
-BASELINE.json's metric has two halves -- "voxels/sec: unet_deconv 108^3 train step + 900^3 diced inference" -- and the
-default run (`--workload headline`) measures both in one process: the train step is the top-level `value` (it is the
-half BASELINE.json quotes on configs[1]), the 900^3 diced inference (configs[2]) is the nested `inference` object with
-its own `roofline` and `cpu_baseline`.
+BASELINE.json's metric has two halves -- "voxels/sec: unet_deconv 108^3 train step + 900^3 diced inference".  A plain run
+sets up, warms up, times K steps of the selected workload and prints one JSON line: for the default `--workload headline`
+that is the train step, the top-level `value` (the half BASELINE.json quotes on configs[1]).  `--full` adds to the same
+line what takes runs of its own: the 900^3 diced inference (configs[2]) as the nested `inference` object with its own
+`roofline` and `cpu_baseline`, the A/B steps on other kernel sets, the CPU baselines and `parity_vs_cpu_oracle`.
 
 Train leg at every N (BASELINE.json configs[1]): one *step* = one `optimize_parameters()` of the Apollo model
 (axial_to_lateral_gan_apollo: unet_deconv G_A + deep_linear_gen G_B + four 2-D PatchGANs, LSGAN + InstanceNorm,
@@ -13,7 +16,8 @@ fp32) on one 108^3 crop, batch 1, per GPU.  Inputs are synthetic random uint16 c
 are random-init (kaiming), as the reference would start.  Scaling is WEAK: every rank trains on its own crop and the
 gradients are all-reduced (RCCL) once per optimizer phase.  value = voxels fed to G_A per second over all ranks.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (`--full` only: fp32_mfma_kernels, three_term_split, deep_linear_tail.layer_by_layer, cpu_baseline,
+inference, parity_vs_cpu_oracle):
   roofline     -- for the kernel class that took most of the timed region: algorithmic FLOP / launch, measured with HIP
                   events on the launch stream inside the timed steps (neuroclear_amd.ops.prof), against the dense MFMA
                   peak of /opt/skills/guides/MI355X_MICROARCH.md for the instruction the class runs on: 157.3 TFLOP/s
@@ -32,6 +36,11 @@ FLOP over the wall time of the timed region (`event_ms_per_cube` = the mean HIP-
 overlaps its neighbours').
 `--workload train` / `--workload infer` run one leg only (infer = BASELINE.json configs[2], cubes sharded over ranks);
 `--crop 148 --batch 4` is the shape of configs[3] (in fp32), `--model athena` the step of configs[4].
+
+`--dump-outputs DIR` (rank 0): the train step's losses (loss_<name>.npy, float64), `fake` and `rec` (float32) and every network's
+parameters after the step (param_<net>.npy, float32, flattened in parameters() order); the inference volume (volume.npy, float32).
+Arrays larger than DUMP_MAX_ELEMS are a fixed seeded sample of their flat indices (DUMP_SAMPLE_SEED, sorted), so two builds given the
+same arguments -- which make the same inputs and weights -- can be compared file by file.
 """
 import argparse
 import json
@@ -304,6 +313,37 @@ def parity_infer(gpu, ref):
                 ok=bool(len(d) == 2 and max(d) <= B['cube_max_abs'] and lsb <= B['slab_max_lsb']))
 
 
+DUMP_MAX_ELEMS = dict(volume=1 << 21, param=1 << 20, inference=1 << 23)  # at most 8 / 4 / 32 MB per file: <= 64 MB for every workload
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(path, arrays, kind):
+    """Write {name: array} as path/<name>.npy (float64 stays float64, everything else float32); arrays larger than
+    DUMP_MAX_ELEMS[kind[name]] are reduced to a fixed seeded sample of their flat indices."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        cap = DUMP_MAX_ELEMS[kind[name]]
+        if a.size > cap:  # (sampled before the cast: a 900^3 uint16 volume is 2.9 GB as float32)
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
+def train_outputs(model):
+    """What optimize_parameters() leaves a caller: the losses, `fake` and `rec`, and every network's parameters."""
+    import torch
+    arrays = {'loss_' + k: np.float64(float(v)) for k, v in model.get_current_losses().items()}
+    kind = dict.fromkeys(arrays, 'volume')
+    for k in ('fake', 'rec'):
+        arrays[k] = getattr(model, k).detach().float().cpu().numpy()
+        kind[k] = 'volume'
+    for n in model.model_names:
+        with torch.no_grad():
+            arrays['param_' + n] = torch.cat([p.detach().float().reshape(-1) for p in getattr(model, 'net' + n).parameters()]).cpu().numpy()
+        kind['param_' + n] = 'param'
+    return arrays, kind
+
+
 def run_train(args, rank, world, dev):
     import torch
     import torch.distributed as dist
@@ -359,6 +399,8 @@ def run_train(args, rank, world, dev):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     stats, whole = ({}, []) if args.no_prof else ops.prof_stop()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *train_outputs(model))
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -489,6 +531,8 @@ def run_infer(args, rank, world, dev, steps=None, warmup=None):
         t = torch.tensor([dt] + per_volume, dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, per_volume = float(t[0].item()), [float(v) for v in t[1:].tolist()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(volume=out), dict(volume='inference'))
     del out
     from neuroclear_amd.util import util as U
     padded = U.padded_shape((L, L, L), 120, 15)
@@ -596,7 +640,7 @@ def main():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='headline', choices=['headline', 'train', 'infer'],
-                    help='headline = the 108^3 train step (top-level value) + one 900^3 diced inference (nested)')
+                    help='headline = the 108^3 train step (top-level value) + with --full one 900^3 diced inference (nested)')
     ap.add_argument('--crop', type=int, default=108)
     ap.add_argument('--batch', type=int, default=1, help='crops per step and GPU (headline: 1; configs[3] shape: --crop 148 --batch 4)')
     ap.add_argument('--model', default='apollo', choices=['apollo', 'athena'], help='athena = configs[4]')
@@ -606,12 +650,19 @@ def main():
     ap.add_argument('--data', default='random', choices=['random', 'structured'],
                     help='training crops: uniform uint16 noise (the north star\'s "synthetic random volumes") or crops of the structured '
                          'volume of SURVEY.md 8d (seed.structured_volume; configs[4])')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what takes runs of its own: the nested 900^3 inference leg (headline), the A/B steps on other kernel '
+                         'sets, the CPU baselines and parity_vs_cpu_oracle (a plain run times the selected workload only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (see the module docstring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines and the parity check')
     ap.add_argument('--no-prof', action='store_true', help='skip the per-launch HIP events (A/B runs)')
     ap.add_argument('--prof-all', action='store_true',
                     help='bracket every convolution launch with HIP events (default: launches of >= 1 GFLOP only -- the '
                          'events around the ~700 small PatchGAN launches of a step cost more than those kernels)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # `python bench.py --gpus N` with no launcher around it (the reference's own multi-GPU run needs none either:
@@ -676,11 +727,11 @@ def main():
     if world > 1:
         out['dist'] = dict(backend=dist.get_backend(), devices=torch.cuda.device_count(),
                            ranks_share_devices=torch.cuda.device_count() < world)
-    if headline and split_on and world == 1:
+    if args.full and headline and split_on and world == 1:
         # the same step with those layers on the fp32 MFMA kernels (v_mfma_f32_32x32x2_f32), for comparison
         import copy
         a2 = copy.copy(args)
-        a2.steps, a2.warmup, a2.no_prof = 3, 1, True
+        a2.steps, a2.warmup, a2.no_prof, a2.dump_outputs = 3, 1, True, None
         _ops.set_conv_split(False)
         try:
             dt2, units2, _, cfg2 = run_train(a2, rank, world, dev)
@@ -714,10 +765,10 @@ def main():
         if args.crop == 108 and args.batch == 1 and args.model == 'apollo':  # (figures of the headline shape, where every plan of DESIGN.md 4.6 applies)
             out['deep_linear_tail'].update(macs_per_voxel_executed_fwd_bwd=833900,
                                            note='the reference-count 9.904 TFLOP per step include 2.79 TFLOP this evaluation does not execute')
-        if headline and world == 1:
+        if args.full and headline and world == 1:
             import copy
             a4 = copy.copy(args)
-            a4.steps, a4.warmup, a4.no_prof = 3, 1, True
+            a4.steps, a4.warmup, a4.no_prof, a4.dump_outputs = 3, 1, True, None
             prev_mode = int(_lib().nc_get_dl_collapse())  # (2: the position-typed 7^3 form of round 6; 1: the collapsed tail + rank forms of round 5)
             _lib().nc_set_dl_collapse(0)
             try:
@@ -730,9 +781,9 @@ def main():
                 _lib().nc_set_dl_collapse(prev_mode)
     # CPU legs: rank 0 only, at every N (the other ranks have nothing to add to a host-core figure), and AFTER the last GPU leg and the
     # process group are done with -- no rank sits in an RCCL call while rank 0 spends a minute on its host cores
-    cpu = rank == 0 and not args.no_cpu_baseline
+    cpu = rank == 0 and args.full and not args.no_cpu_baseline
     inf = None
-    if headline:
+    if args.full and headline:
         # second half of BASELINE.json's metric: one 900^3 diced inference (configs[2]), strong scaling over ranks
         import gc
         gc.collect()
@@ -746,7 +797,10 @@ def main():
         try:
             if os.environ.get('NC_BENCH_FAIL_INFER') == '1':  # test hook: the injected failure of tests/test_bench_guard.py
                 raise RuntimeError('injected inference failure (NC_BENCH_FAIL_INFER=1)')
-            idt, iunits, iroof, icfg = run_infer(args, rank, world, dev, steps=isteps, warmup=1)
+            import copy
+            ai = copy.copy(args)
+            ai.dump_outputs = None  # (the outputs of the timed path -- the train step above -- are the ones written)
+            idt, iunits, iroof, icfg = run_infer(ai, rank, world, dev, steps=isteps, warmup=1)
         except Exception as e:
             guard.fail('inference leg raised on rank %d: %r' % (rank, e))  # does not return
         guard.disarm()

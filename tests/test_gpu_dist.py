@@ -117,12 +117,12 @@ def test_two_ranks_p2p_failure_falls_back_to_reduce(tmp_path):
 
 
 def test_bench_line_survives_an_inference_failure():
-    """`python bench.py` whose inference leg raises still prints the measured train line, with inference.error, and
+    """`python bench.py --full` whose inference leg raises still prints the measured train line, with inference.error, and
     leaves non-zero."""
     env = dict(os.environ, NC_BENCH_FAIL_INFER='1')
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no-cpu-baseline'], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline'], env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 3, (p.returncode, p.stderr[-2000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]

@@ -1,6 +1,6 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06; mkdir -p $O
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout 600 python3 bench.py --workload train --crop 148 --batch 4 --precision bf16 --no-cpu-baseline > $O/bench_config3.json 2>/dev/null
 timeout 600 python3 bench.py --workload train --model athena --data structured --steps 8 --warmup 3 --no-cpu-baseline > $O/bench_athena.json 2>/dev/null
 python3 - <<'PY'

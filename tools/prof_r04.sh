@@ -42,8 +42,8 @@ find $O -name "*kernel_trace.csv" -delete; find $O -name "t_agent_info.csv" -del
 for m in 1 0 1 0; do
   echo "configs[3] 4x148^3 bf16 NC_C8X=$m $(NC_C8X=$m timeout 600 python3 bench.py --crop 148 --batch 4 --precision bf16 --workload train --no-cpu-baseline --steps 8 --warmup 3 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.readline()); print('ms_per_step %.2f' % j['ms_per_step'], {k: v['tflops'] for k, v in j['roofline']['classes'].items() if '_lp_k' in k})")" >> $O/ab_r04.txt
 done
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-NC_DIST_BACKEND=gloo timeout 900 python3 bench.py --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_2rank_dry.json 2> $O/bench_2rank_dry.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+NC_DIST_BACKEND=gloo timeout 900 python3 bench.py --gpus 2 --steps 5 --warmup 2 --full --no-cpu-baseline > $O/bench_2rank_dry.json 2> $O/bench_2rank_dry.err
 for f in train108 infer athena c3; do tail -1 $O/$f.log | cut -c1-300; done
 cat $O/ab_r04.txt; cut -c1-600 $O/bench_default.json; cut -c1-400 $O/bench_2rank_dry.json
 grep -E "conv_c8x|conv_h<2, 3|conv_h<2, 5|wgrad_s3x" $O/c8_sq_counters_mode1.csv | tail -8; grep -E "conv_h<2, 3|conv_h<2, 5" $O/c8_sq_counters_mode0.csv | tail -4

@@ -35,5 +35,5 @@ find $O -name "*kernel_trace.csv" -delete; find $O -name "t_agent_info.csv" -del
 for m in 1 0 1 0 2; do
   echo "configs[3] 4x148^3 bf16 NC_C8X=$m $(NC_C8X=$m timeout 600 python3 bench.py --crop 148 --batch 4 --precision bf16 --workload train --no-cpu-baseline --steps 8 --warmup 3 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.readline()); print('ms_per_step %.2f' % j['ms_per_step'], {k: v['tflops'] for k, v in j['roofline']['classes'].items() if '_lp_k' in k})")" >> $O/ab_r04.txt
 done
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cat $O/ab_r04.txt; cut -c1-300 $O/bench_default.json

@@ -12,5 +12,5 @@ for m in 3 0 3 0 1; do
   echo "athena 108^3 structured NC_P2D=$m $(NC_P2D=$m timeout 600 python3 bench.py --workload train --model athena --data structured --no-cpu-baseline --steps 8 --warmup 3 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.readline()); print('ms_per_step %.2f' % j['ms_per_step'], 'first-step G_A %.5f D_B_xz %.5f' % (j['config']['first_step_losses']['G_A'], j['config']['first_step_losses']['D_B_xz']))")" >> $O/ab_athena.txt
 done
 timeout 400 python3 tools/p2d_check.py 2>&1 | grep -v amdgpu.ids > $O/p2d_layers.txt
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cat $O/ab_athena.txt; cat $O/p2d_layers.txt | grep -A1 "^B 216\|^B 108"; cut -c1-200 $O/bench_default.json; tail -12 $O/p2d_sq_counters.csv

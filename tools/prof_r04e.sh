@@ -9,5 +9,5 @@ $T rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WA
 python3 tools/pmc_summary.py $O/sq $O/h2_sq_counters.csv k_conv_s3x > /dev/null
 find $O -name "*counter_collection.csv" -delete; find $O -name "*kernel_trace.csv" -delete; find $O -name "t_agent_info.csv" -delete
 timeout 300 python3 tools/h2_check.py > $O/h2_layers.txt 2>&1
-timeout 900 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 grep "^{" $O/train.log | cut -c1-200; grep "^{" $O/infer.log | cut -c1-200; cut -c1-300 $O/bench_default.json; tail -4 $O/h2_sq_counters.csv
