@@ -507,6 +507,17 @@ size_t nc_convT_k2s2_split_ws_bytes(int N, int C, int D, int H, int W, int K);
 int nc_convT_k2s2_fwd_split(const float* x, const void* xs, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0,
                             int N, int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Learned-PSF generators (--netG_B linearkernel / linearkernel_double / linearkernel_LK31): LinearKernel and LinearKernel_double at
+ *      models/networks.py:840-871, one bias-free Conv3d(1, 1, k, stride 1, padding (k - 1) / 2) -- applied twice with one weight in the
+ *      _double form -- and its autograd backward (loss.backward(), apollo:283).  x, y, dy, dx: [N][1][D][H][W]; w, dw: [1][1][k][k][k].
+ *      Odd k from 3 to 31, any N, D, H, W >= 1 (extents below k included); anything else is NC_ERR_SHAPE.  Exact fp32 products with fp32
+ *      accumulation on v_mfma_f32_16x16x4_f32 (csrc/conv_lk.hip); bit-identical from run to run.  Only nc_lk_wgrad uses the workspace
+ *      (fixed-order partial sums, nc_lk_ws_bytes); nc_lk_fwd / nc_lk_dgrad accept ws = NULL. */
+size_t nc_lk_ws_bytes(int N, int D, int H, int W, int k);
+int nc_lk_fwd(const float* x, const float* w, float* y, int N, int D, int H, int W, int k, void* ws, size_t ws_bytes, void* stream);
+int nc_lk_dgrad(const float* dy, const float* w, float* dx, int N, int D, int H, int W, int k, void* ws, size_t ws_bytes, void* stream);
+int nc_lk_wgrad(const float* x, const float* dy, float* dw, int N, int D, int H, int W, int k, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

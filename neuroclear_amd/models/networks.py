@@ -4,10 +4,11 @@ Same factory names, argument meaning, state-dict keys and error behaviour as the
 BASELINE.json's north_star names -- `unet_deconv` (:478-538), `deep_linear_gen` (:893-917), `basic` / `n_layers`
 PatchGAN (:1009-1067) -- plus, as the first widening row, `unet_vanilla` (:540-608) and the `pixel`
 discriminator (:1147-1179), which are built from the same kernels; `get_norm_layer` (:20-44: instance -- the hot path -- and batch),
-`GANLoss` (:252-319: lsgan -- the hot path -- vanilla, wgangp), `init_net` (:122-137), `get_scheduler` (:50-86).  Every forward/backward runs HIP kernels from libnc_hip.so through neuroclear_amd.ops;
-there is no torch.nn.functional compute and no CPU fallback.  Networks outside the scope table (SURVEY.md 8a:
-resnet, VGG, linear kernels, spectral-norm D, ...) raise NotImplementedError exactly like an unknown name does in
-the reference (:196, :246).
+`GANLoss` (:252-319: lsgan -- the hot path -- vanilla, wgangp), `init_net` (:122-137), `get_scheduler` (:50-86), and the learned-PSF
+generators `linearkernel`, `linearkernel_double`, `linearkernel_LK31` (:840-871, :183-188).  Every forward/backward runs HIP kernels from
+libnc_hip.so through neuroclear_amd.ops; there is no torch.nn.functional compute and no CPU fallback.  Networks outside the scope table
+(resnet, VGG, linearkernel_NC, fixed_kernel, ...) raise NotImplementedError exactly like an unknown name does in the
+reference (:196, :246).
 """
 import functools
 import os
@@ -453,6 +454,27 @@ class DeepLinearGenerator(nn.Module):
         return self.final_layer(self.feature_block(self.first_layer(input)))
 
 
+class LinearKernel(nn.Module):
+    """networks.py:840-854: one bias-free Conv3d(input_nc, output_nc, k, padding (k - 1) / 2) -- the learned PSF of the B -> A path.  The
+    weight lives in `convlayer` (state-dict key convlayer.weight, initialised by init_net as a Conv); this wrapper has no `weight` of its own,
+    so init_weights' 'Linear' rule does not touch it.  The 1 -> 1 channel 3-D form runs on nc_lk_* in fp32 under every conv precision."""
+
+    def __init__(self, input_nc, output_nc, kernel_size, dimension=3):
+        super().__init__()
+        self.convlayer = Conv(input_nc, output_nc, kernel_size, 1, (kernel_size - 1) // 2, bias=False, dimension=dimension)
+
+    def forward(self, inputs):
+        return ops.linear_kernel(inputs, self.convlayer.weight)
+
+
+class LinearKernel_double(LinearKernel):
+    """networks.py:856-871: the same kernel applied twice (one shared weight; autograd adds both gradient contributions)."""
+
+    def forward(self, inputs):
+        w = self.convlayer.weight
+        return ops.linear_kernel(ops.linear_kernel(inputs, w), w)
+
+
 class NLayerDiscriminator(nn.Module):
     """networks.py:1009-1067 (PatchGAN).  With instance norm every conv carries a bias (:1025-1028)."""
 
@@ -530,8 +552,18 @@ def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, in
         net = DeepLinearGenerator(input_nc, output_nc)
     elif netG == 'unet_vanilla':
         net = Unet_vanilla(1, output_nc, norm_layer=norm_layer, dimension=dimension)  # input_nc forced to 1 (:176)
-    elif netG in ('unet_twoouts', 'resnet_9blocks', 'resnet_6blocks', 'VGG', 'linearkernel',
-                  'linearkernel_double', 'linearkernel_LK31', 'linearkernel_NC', 'fixed_kernel'):
+    elif netG == 'linearkernel':
+        net = LinearKernel(input_nc, output_nc, kernel_size, dimension=dimension)
+    elif netG == 'linearkernel_double':
+        net = LinearKernel_double(input_nc, output_nc, kernel_size, dimension=dimension)
+    elif netG == 'linearkernel_LK31':
+        net = LinearKernel(input_nc, output_nc, 31, dimension=dimension)
+    elif netG == 'linearkernel_NC':
+        raise NotImplementedError('Generator [linearkernel_NC] cannot be built: the reference\'s LinearKernel_NC fails in its own constructor '
+                                  '(super(LinearKernel, self), networks.py:876)')
+    elif netG == 'fixed_kernel':
+        raise NotImplementedError('Generator [fixed_kernel] needs given_psf, which no model of the reference passes (networks.py:189-190)')
+    elif netG in ('unet_twoouts', 'resnet_9blocks', 'resnet_6blocks', 'VGG'):
         raise NotImplementedError('Generator [%s] is outside the MI355X hot path (SURVEY.md 8a)' % netG)
     else:
         raise NotImplementedError('Generator model name [%s] is not recognized' % netG)

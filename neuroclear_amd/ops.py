@@ -25,7 +25,8 @@ def prof_start(min_flop=0.0):
     lib().nc_prof_begin(ctypes.c_double(min_flop))
 
 
-_PATH = {0: 'direct', 1: 'mfma', 2: 'gemm', 3: 'flat', 4: 'taps', 5: 'k1', 6: 'to1', 7: 'img', 8: 'pg1', 9: 'split', 10: 'split2d', 11: 'split'}
+_PATH = {0: 'direct', 1: 'mfma', 2: 'gemm', 3: 'flat', 4: 'taps', 5: 'k1', 6: 'to1', 7: 'img', 8: 'pg1', 9: 'split', 10: 'split2d', 11: 'split',
+         12: 'lk'}
 
 
 def prof_stop():
@@ -428,6 +429,55 @@ def conv(x, w, b=None, stride=1, padding=0, link=None, prev=None):
     """nn.Conv3d / nn.Conv2d (models/networks.py:361-369).  link / prev: BiasLink shared with the InstanceNorm behind /
     in front of this layer."""
     return _Conv.apply(x, w, b, int(stride), int(padding), link, prev)
+
+
+def _lk_ok(x, w):
+    """nc_lk_* cover this call: a dense fp32 CUDA x [N, 1, D, H, W] and w [1, 1, k, k, k] with odd k in 3 .. 31."""
+    return (x.is_cuda and w.is_cuda and x.dim() == 5 and x.shape[1] == 1 and x.dtype == torch.float32 and w.dtype == torch.float32
+            and tuple(w.shape[:2]) == (1, 1) and w.dim() == 5 and w.shape[2] == w.shape[3] == w.shape[4]
+            and w.shape[2] % 2 == 1 and 3 <= w.shape[2] <= 31)
+
+
+def _lk_call(fn, a, b, out, k, ws, what):
+    N, _, D, H, W = out.shape
+    check(fn(_ptr(a), _ptr(b), _ptr(out), I(N), I(D), I(H), I(W), I(k), _ptr(ws), Z(0 if ws is None else ws.numel()), _stream()), what)
+    return out
+
+
+class _LinearKernel(torch.autograd.Function):
+    """Conv3d(1, 1, k, padding (k - 1) / 2, bias=False) of LinearKernel / LinearKernel_double (models/networks.py:840-871) on
+    nc_lk_fwd / nc_lk_dgrad / nc_lk_wgrad.  The weight gradient goes back through autograd (never into FlatAdam's flat buffer:
+    the _double form uses its weight twice and autograd adds the two contributions)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        x, w = x.contiguous(), w.contiguous()
+        ctx.save_for_backward(x, w)
+        return _lk_call(lib().nc_lk_fwd, x, w, torch.empty_like(x), w.shape[2], None, 'nc_lk_fwd')
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        k = w.shape[2]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _lk_call(lib().nc_lk_dgrad, dy, w, torch.empty_like(dy), k, None, 'nc_lk_dgrad')
+        if ctx.needs_input_grad[1]:
+            N, _, D, H, W = x.shape
+            ws = workspace(lib().nc_lk_ws_bytes(I(N), I(D), I(H), I(W), I(k)), x.device, 'ws_lk')
+            dw = torch.empty_like(w)
+            check(lib().nc_lk_wgrad(_ptr(x), _ptr(dy), _ptr(dw), I(N), I(D), I(H), I(W), I(k), _ptr(ws), Z(ws.numel()), _stream()),
+                  'nc_lk_wgrad')
+        return dx, dw
+
+
+def linear_kernel(x, w):
+    """The learned PSF: one bias-free Conv3d(1, 1, k, stride 1, padding (k - 1) // 2) (networks.py:840-854).  Always fp32, whatever
+    set_conv_precision says.  Another kernel size, or a CPU tensor, goes to ops.conv (which has no CPU path either: it raises)."""
+    if _lk_ok(x, w):
+        return _LinearKernel.apply(x, w)
+    return conv(x, w, None, 1, (w.shape[-1] - 1) // 2)
 
 
 class _ConvT(torch.autograd.Function):

@@ -57,6 +57,11 @@ def deep_linear_spec():
     ]
 
 
+def linear_kernel_spec(k=9):
+    """(key, shape) list of ``LinearKernel`` / ``LinearKernel_double`` (``models/networks.py:840-871``): one bias-free 1 -> 1 conv."""
+    return [('convlayer.weight', (1, 1, k, k, k))]
+
+
 def patchgan_spec(dimension=2, input_nc=1, ndf=64, n_layers=3):
     """(key, shape) list of ``NLayerDiscriminator`` (``models/networks.py:1009-1061``) with instance norm
     (=> every conv carries a bias, ``:1025-1028``).  Sequential indices: conv at 0, then 2+3*(n-1) for the middle
