@@ -518,6 +518,23 @@ int nc_lk_fwd(const float* x, const float* w, float* y, int N, int D, int H, int
 int nc_lk_dgrad(const float* dy, const float* w, float* dx, int N, int D, int H, int W, int k, void* ws, size_t ws_bytes, void* stream);
 int nc_lk_wgrad(const float* x, const float* dy, float* dw, int N, int D, int H, int W, int k, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- KernelGAN patch discriminator (--netD kernelGAN): KernelPatchDiscriminator at models/networks.py:1113-1145, built by define_D at
+ *      :243-244 with n_layers = 5, here with InstanceNorm, input_nc = 1 and ndf = 64 (any other ndf is NC_ERR_SHAPE): a valid 7^nd conv
+ *      (1 -> 64), three [1x1 conv 64 -> 64, InstanceNorm, ReLU], a 1x1 conv 64 -> 1, every conv with a bias.  Forward and backward as
+ *      one call each, like nc_patchgan_*: params = the 10 tensors in state-dict order, packed (nc_kgan_param_floats); saved is opaque
+ *      (nc_kgan_saved_floats); nd = 2 (x is [B,1,H,W], pass D = 1) or 3; y is [B,1,(D-6),H-6,W-6].  bwd: dx and dparams may be NULL;
+ *      dparams is overwritten (not accumulated).  A spatial edge below 7, or an output plane of one element (InstanceNorm in training
+ *      mode refuses it), is NC_ERR_SHAPE.  The first two convs run collapsed into one; exact fp32 products with fp32
+ *      accumulation (csrc/kgan.hip); bit-identical from run to run.  Both directions need the workspace (nc_kgan_ws_bytes). */
+size_t nc_kgan_param_floats(int ndf, int nd);
+size_t nc_kgan_saved_floats(int B, int D, int H, int W, int ndf, int nd);
+size_t nc_kgan_ws_bytes(int B, int D, int H, int W, int ndf, int nd);
+int nc_kgan_out_shape(int B, int D, int H, int W, int ndf, int nd, int* oD, int* oH, int* oW);
+int nc_kgan_fwd(const float* params, const float* x, float* y, float* saved, int B, int D, int H, int W, int ndf, int nd, void* ws,
+                size_t ws_bytes, void* stream);
+int nc_kgan_bwd(const float* params, const float* x, const float* saved, const float* dy, float* dx, float* dparams, int B, int D, int H,
+                int W, int ndf, int nd, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

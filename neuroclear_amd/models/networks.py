@@ -5,10 +5,10 @@ BASELINE.json's north_star names -- `unet_deconv` (:478-538), `deep_linear_gen` 
 PatchGAN (:1009-1067) -- plus, as the first widening row, `unet_vanilla` (:540-608) and the `pixel`
 discriminator (:1147-1179), which are built from the same kernels; `get_norm_layer` (:20-44: instance -- the hot path -- and batch),
 `GANLoss` (:252-319: lsgan -- the hot path -- vanilla, wgangp), `init_net` (:122-137), `get_scheduler` (:50-86), and the learned-PSF
-generators `linearkernel`, `linearkernel_double`, `linearkernel_LK31` (:840-871, :183-188).  Every forward/backward runs HIP kernels from
-libnc_hip.so through neuroclear_amd.ops; there is no torch.nn.functional compute and no CPU fallback.  Networks outside the scope table
-(resnet, VGG, linearkernel_NC, fixed_kernel, ...) raise NotImplementedError exactly like an unknown name does in the
-reference (:196, :246).
+generators `linearkernel`, `linearkernel_double`, `linearkernel_LK31` (:840-871, :183-188), and the KernelGAN patch discriminator
+`kernelGAN` (:1113-1145, :243-244).  Every forward/backward runs HIP kernels from libnc_hip.so through neuroclear_amd.ops; there is no
+torch.nn.functional compute and no CPU fallback.  Networks outside the scope table (resnet, VGG, linearkernel_NC,
+fixed_kernel, ...) raise NotImplementedError exactly like an unknown name does in the reference (:196, :246).
 """
 import functools
 import os
@@ -525,6 +525,56 @@ class NLayerDiscriminator(nn.Module):
         return ops.patchgan_join_real(input, list(self.parameters()), *self._cfg, share)
 
 
+class KernelPatchDiscriminator(nn.Module):
+    """networks.py:1113-1145 (--netD kernelGAN, :243-244): the KernelGAN patch discriminator, n_layers = 5 -- first_layer, a valid
+    Conv(input_nc, ndf, 7) with no norm or activation; feature_block, 3 x [Conv 1x1 (ndf -> ndf), norm, ReLU] (convs at Sequential
+    indices 0 / 3 / 6, norms at 1 / 4 / 7); final_layer, Conv 1x1 (ndf -> 1).  Every conv carries a bias only with instance norm.
+    With instance norm, one input channel, ndf = 64 and a CUDA input the whole network is one C call per direction (nc_kgan_fwd / _bwd,
+    fp32 under every conv precision, first two convs collapsed: DESIGN.md 4.9); NC_FUSED_KGAN=0 or any other configuration runs the
+    layered modules."""
+
+    def __init__(self, input_nc, ndf=64, n_layers=5, norm_layer=None, dimension=3):
+        super().__init__()
+        use_bias = _is_instance_norm(norm_layer)
+        self.dimension, self.instance = dimension, use_bias
+        self.batch = norm_layer is not None and not use_bias
+        self.first_layer = Conv(input_nc, ndf, 7, 1, 0, bias=use_bias, dimension=dimension)
+        seq = []
+        for _ in range(1, n_layers - 1):
+            seq += [Conv(ndf, ndf, 1, 1, 0, bias=use_bias, dimension=dimension)]
+            seq += [norm_layer(ndf, 0.0), FusedActivation()] if norm_layer else [Identity(), LeakyReLU(0.0)]
+        self.feature_block = nn.Sequential(*seq)
+        self.final_layer = Conv(ndf, 1, 1, 1, 0, bias=use_bias, dimension=dimension)
+        self._ndf = ndf
+        self._fusable = use_bias and input_nc == 1 and ndf == 64 and n_layers == 5
+
+    def _fused_on(self, input):
+        return self._fusable and input.is_cuda and os.environ.get('NC_FUSED_KGAN', '1') != '0'
+
+    def _check(self, input):
+        """The reference's errors, raised before any launch: an edge below 7 fails in first_layer, one value per channel in the norm."""
+        nd = self.dimension
+        sp = tuple(input.shape[2:])
+        if len(sp) != nd or min(sp) < 7:
+            raise ValueError('KernelPatchDiscriminator: input %s: every one of the %d spatial edges must be at least 7 '
+                             '(first_layer is a 7^%d conv with padding 0)' % (tuple(input.shape), nd, nd))
+        if self.instance:
+            ops.kgan_dims(input.shape, nd)
+        elif self.batch and self.training:
+            n = input.shape[0]
+            for e in sp:
+                n *= e - 6
+            if n < 2:
+                raise ValueError('Expected more than 1 value per channel when training, got input size %s'
+                                 % ((int(input.shape[0]), self._ndf) + tuple(int(e) - 6 for e in sp),))
+
+    def forward(self, input):
+        self._check(input)
+        if self._fused_on(input):
+            return ops.kernelgan(input, list(self.parameters()), self.dimension, self._ndf)
+        return self.final_layer(_run_linked(self.feature_block, self.first_layer(input)))
+
+
 class PixelDiscriminator(nn.Module):
     """networks.py:1147-1179 (1x1 PatchGAN): conv1x1(1->ndf) + LeakyReLU, conv1x1(ndf->2ndf) + norm + LeakyReLU,
     conv1x1(2ndf->1); Sequential indices 0 / 2 / 5 carry the convs.  With instance norm all convs have a bias."""
@@ -584,8 +634,8 @@ def define_D(input_nc, ndf, netD, n_layers_D=3, norm='batch', init_type='normal'
         net = NLayerDiscriminatorSN(input_nc, ndf, 3, norm_layer, use_sigmoid, dimension)
     elif netD == 'n_layers_SN':
         net = NLayerDiscriminatorSN(input_nc, ndf, n_layers_D, norm_layer, use_sigmoid, dimension)
-    elif netD in ('kernelGAN',):
-        raise NotImplementedError('Discriminator [%s] is outside the MI355X hot path (SURVEY.md 8a)' % netD)
+    elif netD == 'kernelGAN':  # n_layers is fixed at 5, n_layers_D is ignored (:243-244)
+        net = KernelPatchDiscriminator(input_nc, ndf, 5, norm_layer, dimension)
     else:
         raise NotImplementedError('Discriminator model name [%s] is not recognized' % netD)
     return init_net(net, init_type, init_gain, gpu_ids)

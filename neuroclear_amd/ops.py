@@ -1238,6 +1238,85 @@ def patchgan(x, params, n_layers, ndf, dimension):
     return _PatchGAN.apply(x, (int(n_layers), int(ndf), int(dimension)), *params)
 
 
+# ---- whole-network KernelGAN discriminator (nc_kgan_fwd / nc_kgan_bwd): one C call per direction ------------------------------
+def kgan_dims(shape, nd):
+    """(B, D, H, W) of a KernelPatchDiscriminator input; ValueError, before anything is launched, for the inputs the reference's
+    InstanceNorm refuses in training mode: an edge below 7 (the valid 7^nd first_layer leaves nothing) or a 7^nd input (one value per
+    channel)."""
+    if len(shape) != nd + 2:
+        raise ValueError('kernelGAN discriminator: expected a %d-D input [B, C, spatial...], got shape %s' % (nd + 2, tuple(shape)))
+    sp = tuple(int(s) for s in shape[2:])
+    if min(sp) < 7:
+        raise ValueError('kernelGAN discriminator: every spatial edge must be at least 7 (first_layer is a 7^%d conv with padding 0), '
+                         'got %s' % (nd, sp))
+    out = 1
+    for s in sp:
+        out *= s - 6
+    if out < 2:
+        raise ValueError('Expected more than 1 spatial element when training, got input size %s: the KernelGAN discriminator\'s '
+                         'InstanceNorm sees one value per channel' % ((int(shape[0]), 64) + tuple(s - 6 for s in sp),))
+    return (int(shape[0]), 1) + sp[-2:] if nd == 2 else (int(shape[0]),) + sp
+
+
+class _KernelGAN(torch.autograd.Function):
+    """KernelPatchDiscriminator.forward (networks.py:1141-1144) with InstanceNorm, 1 input channel, ndf = 64 on nc_kgan_fwd / _bwd:
+    always fp32.  The parameters are packed in state-dict order (zero-copy inside FlatAdam's buffer), their gradients go straight into
+    its flat gradient slice when every one of them wants one (_grad_target)."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        ndf, nd = cfg
+        x = x.contiguous()
+        _chk(x, *params)
+        _f32(x, *params)
+        if x.shape[1] != 1:
+            raise _lib.NcError('fused KernelGAN discriminator expects one input channel')
+        B, D, H, W = kgan_dims(x.shape, nd)
+        L = lib()
+        packed = _pack_params(params)
+        if packed.numel() != L.nc_kgan_param_floats(I(ndf), I(nd)):
+            raise _lib.NcError('fused KernelGAN discriminator: parameter count does not match (ndf=%d, nd=%d)' % (ndf, nd))
+        import ctypes
+        od, oh, ow = I(0), I(0), I(0)
+        check(L.nc_kgan_out_shape(I(B), I(D), I(H), I(W), I(ndf), I(nd), ctypes.byref(od), ctypes.byref(oh), ctypes.byref(ow)),
+              'nc_kgan_out_shape')
+        oshape = (B, 1, oh.value, ow.value) if nd == 2 else (B, 1, od.value, oh.value, ow.value)
+        y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+        saved = torch.empty(L.nc_kgan_saved_floats(I(B), I(D), I(H), I(W), I(ndf), I(nd)), dtype=torch.float32, device=x.device)
+        ws = workspace(L.nc_kgan_ws_bytes(I(B), I(D), I(H), I(W), I(ndf), I(nd)), x.device, 'kgan')
+        check(L.nc_kgan_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), I(B), I(D), I(H), I(W), I(ndf), I(nd), _ptr(ws),
+                            Z(ws.numel()), _stream()), 'nc_kgan_fwd')
+        ctx.save_for_backward(x, saved)
+        ctx.packed = packed
+        ctx.packed_gen = _param_generation(packed)
+        ctx.cfg = (cfg, (B, D, H, W), [tuple(p.shape) for p in params])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, saved = ctx.saved_tensors
+        (ndf, nd), (B, D, H, W), shapes = ctx.cfg
+        if _param_generation(ctx.packed) != ctx.packed_gen:
+            raise _lib.NcError('fused KernelGAN discriminator: the parameters were updated (optimizer step / checkpoint load) between '
+                               'this forward and its backward; the saved activations no longer match them')
+        dy = dy.contiguous()
+        want_p = any(ctx.needs_input_grad[2:])
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dpar = _grad_target(ctx, 2) if want_p else None  # (x, cfg, *params): the parameters start at input 2
+        L = lib()
+        ws = workspace(L.nc_kgan_ws_bytes(I(B), I(D), I(H), I(W), I(ndf), I(nd)), x.device, 'kgan')
+        check(L.nc_kgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), I(B), I(D), I(H), I(W), I(ndf),
+                            I(nd), _ptr(ws), Z(ws.numel()), _stream()), 'nc_kgan_bwd')
+        grads = _param_grads(ctx, dpar, shapes, 2) if want_p else [None] * len(shapes)
+        return (dx, None) + tuple(grads)
+
+
+def kernelgan(x, params, nd, ndf=64):
+    """KernelPatchDiscriminator.forward (networks.py:1141-1144) with InstanceNorm as one C call (and one for backward); `params` in
+    state-dict order."""
+    return _KernelGAN.apply(x, (int(ndf), int(nd)), *params)
+
+
 # ---- whole-network generators (nc_unet_deconv_train_fwd / _bwd, nc_deep_linear_fwd / _bwd): one C call per direction --
 def _grad_target(ctx, first):
     """Where a whole-network backward writes its packed parameter gradients: the optimizer's flat gradient slice when EVERY parameter

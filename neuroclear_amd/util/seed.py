@@ -62,6 +62,21 @@ def linear_kernel_spec(k=9):
     return [('convlayer.weight', (1, 1, k, k, k))]
 
 
+def kernelgan_spec(dimension=2, input_nc=1, ndf=64, norm='instance'):
+    """(key, shape) list of ``KernelPatchDiscriminator`` (``models/networks.py:1113-1145``, n_layers = 5): parameters only, in
+    state-dict order.  Every conv has a bias only with instance norm; batch norm adds weight / bias at ``feature_block.{1,4,7}``."""
+    k = (7,) * dimension
+    one = (1,) * dimension
+    bias = norm == 'instance'
+    spec = [('first_layer.weight', (ndf, input_nc) + k)] + ([('first_layer.bias', (ndf,))] if bias else [])
+    for i in (0, 3, 6):
+        spec += [('feature_block.%d.weight' % i, (ndf, ndf) + one)] + ([('feature_block.%d.bias' % i, (ndf,))] if bias else [])
+        if norm == 'batch':
+            spec += [('feature_block.%d.weight' % (i + 1), (ndf,)), ('feature_block.%d.bias' % (i + 1), (ndf,))]
+    spec += [('final_layer.weight', (1, ndf) + one)] + ([('final_layer.bias', (1,))] if bias else [])
+    return spec
+
+
 def patchgan_spec(dimension=2, input_nc=1, ndf=64, n_layers=3):
     """(key, shape) list of ``NLayerDiscriminator`` (``models/networks.py:1009-1061``) with instance norm
     (=> every conv carries a bias, ``:1025-1028``).  Sequential indices: conv at 0, then 2+3*(n-1) for the middle
