@@ -281,6 +281,19 @@ int nc_patchgan_fwd_part(const float* params, const float* x, float* y, float* s
                          int W, int n_layers, int ndf, int nd, void* ws, size_t ws_bytes, void* stream);
 int nc_patchgan_bwd_part(const float* params, const float* x, const float* saved, const float* dy, float* dx, int Btot, int b0,
                          int B, int D, int H, int W, int n_layers, int ndf, int nd, void* ws, size_t ws_bytes, void* stream);
+/* WGAN-GP gradient penalty of the same network (cal_gradient_penalty, networks.py:321-359), 2-D only (nd = 2, D = 1; anything
+ * else is NC_ERR_SHAPE).  fwd: D's forward on x, its backward with dy = 1 -> g = d(sum D)/dx (shape of x), and
+ * *pen = lambda_gp * mean_b (||g_b + 1e-16||_2 - constant)^2 (fp64 sums of squares); saved (nc_patchgan_gp_saved_floats) keeps
+ * what bwd needs.  bwd: *dpen (a device scalar) times the penalty's gradient -- dparams (OVERWRITTEN, packed like params; the head's
+ * bias and every bias in front of an InstanceNorm are exact zeros) and dx (the gradient with respect to x); either may be NULL.
+ * Bit-identical from run to run (csrc/patchgan_gp.hip; no float atomics).  Both need the workspace (nc_patchgan_gp_ws_bytes). */
+size_t nc_patchgan_gp_saved_floats(int B, int D, int H, int W, int n_layers, int ndf, int nd);
+size_t nc_patchgan_gp_ws_bytes(int B, int D, int H, int W, int n_layers, int ndf, int nd);
+int nc_patchgan_gp_fwd(const float* params, const float* x, float* g, float* pen, float* saved, int B, int D, int H, int W, int n_layers,
+                       int ndf, int nd, float constant, float lambda_gp, void* ws, size_t ws_bytes, void* stream);
+int nc_patchgan_gp_bwd(const float* params, const float* x, const float* saved, const float* g, const float* dpen, float* dparams, float* dx,
+                       int B, int D, int H, int W, int n_layers, int ndf, int nd, float constant, float lambda_gp, void* ws, size_t ws_bytes,
+                       void* stream);
 
 /* ---- Whole-network forward of Unet_deconv (networks.py:512-538; called from TestModel.forward test_model.py:60-62):
  *      params = the 28 tensors in state-dict order, packed back to back (see neuroclear_amd.models.networks).       */

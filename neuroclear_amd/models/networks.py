@@ -661,3 +661,48 @@ class GANLoss(nn.Module):
             return ops.bce_logits_const(prediction, self._real if target_is_real else self._fake)
         m = ops.mean(prediction)  # 'wgan*': networks.py:314-318
         return -m if target_is_real else m
+
+
+def _gp_unsupported(netD, xs):
+    """Why the fused penalty cannot run netD on the inputs xs, or None."""
+    name = type(netD).__name__
+    if not isinstance(netD, NLayerDiscriminator):
+        return '%s (only the PatchGAN NLayerDiscriminator, --netD basic | n_layers, has one)' % name
+    if not netD._fusable:
+        return '%s without instance norm or with input_nc != 1 (the fused path covers --norm instance, one input channel)' % name
+    if netD._cfg[2] != 2:
+        return '%s with dimension=%d (the penalty covers the 2-D discriminators)' % (name, netD._cfg[2])
+    for x in xs:
+        if not x.is_cuda:
+            return '%s on a %s input (there is no CPU path)' % (name, x.device.type)
+    if not netD._fused_on(xs[0]):
+        return '%s with NC_FUSED_PATCHGAN=0 (the penalty runs only on the fused path)' % name
+    return None
+
+
+def cal_gradient_penalty(netD, real_data, fake_data, device, type='mixed', constant=1.0, lambda_gp=10.0):
+    """networks.py:321-359 (same signature, defaults, return values and errors): the WGAN-GP penalty
+    lambda_gp * mean_b (||d(sum netD(x))/dx_b + 1e-16|| - constant)^2 on x = real, fake or alpha real + (1 - alpha) fake, returned with
+    the [B, -1] gradients.  The penalty and its second-order backward are one C call each (ops.patchgan_gp) for the 2-D PatchGAN
+    with instance norm on a CUDA input; every other netD raises NotImplementedError before anything is launched.  Unlike the
+    reference's, the returned gradients carry no graph."""
+    if lambda_gp > 0.0:
+        if type not in ('real', 'fake', 'mixed'):
+            raise NotImplementedError('{} not implemented'.format(type))
+        why = _gp_unsupported(netD, {'real': [real_data], 'fake': [fake_data], 'mixed': [real_data, fake_data]}[type])
+        if why is not None:
+            raise NotImplementedError('cal_gradient_penalty: no HIP path for %s' % why)
+        if type == 'real':   # either use real images, fake images, or a linear interpolation of two.
+            interpolatesv = real_data
+        elif type == 'fake':
+            interpolatesv = fake_data
+        else:
+            alpha = torch.rand(real_data.shape[0], 1, device=device)
+            alpha = alpha.expand(real_data.shape[0], real_data.nelement() // real_data.shape[0]).contiguous().view(*real_data.shape)
+            interpolatesv = alpha * real_data + ((1 - alpha) * fake_data)
+        interpolatesv.requires_grad_(True)
+        n_layers, ndf, nd = netD._cfg
+        gradient_penalty, gradients = ops.patchgan_gp(interpolatesv, list(netD.parameters()), n_layers, ndf, nd, constant, lambda_gp)
+        return gradient_penalty, gradients.view(real_data.size(0), -1)
+    else:
+        return 0.0, None

@@ -1238,6 +1238,67 @@ def patchgan(x, params, n_layers, ndf, dimension):
     return _PatchGAN.apply(x, (int(n_layers), int(ndf), int(dimension)), *params)
 
 
+class _PatchGANGP(torch.autograd.Function):
+    """WGAN-GP penalty of the 2-D PatchGAN (cal_gradient_penalty, networks.py:321-359) on nc_patchgan_gp_fwd / _bwd: returns
+    (penalty, g = d(sum D)/dx).  g is detached; the penalty's backward is its second-order gradient with respect to the parameters
+    (into the same destination as _PatchGAN's, so it accumulates with the rest of the backward) and to x."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *params):
+        n_layers, ndf, nd, constant, lambda_gp = cfg
+        x = x.contiguous()
+        _chk(x, *params)
+        _f32(x, *params)
+        if nd != 2 or x.dim() != 4 or x.shape[1] != 1:
+            raise _lib.NcError('patchgan_gp: the fused penalty covers 2-D inputs [B, 1, H, W], got %s (nd=%d)' % (tuple(x.shape), nd))
+        B, H, W = x.shape[0], x.shape[2], x.shape[3]
+        dims = (I(B), I(1), I(H), I(W), I(n_layers), I(ndf), I(nd))
+        L = lib()
+        packed = _pack_params(params)
+        if packed.numel() != L.nc_patchgan_param_floats(I(n_layers), I(ndf), I(nd)):
+            raise _lib.NcError('fused PatchGAN: parameter count does not match (n_layers=%d, ndf=%d)' % (n_layers, ndf))
+        nsaved = L.nc_patchgan_gp_saved_floats(*dims)
+        if nsaved == 0:
+            raise _lib.NcError('patchgan_gp: shape %s not covered (n_layers=%d)' % (tuple(x.shape), n_layers))
+        saved = torch.empty(nsaved, dtype=torch.float32, device=x.device)
+        g = torch.empty_like(x)
+        pen = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = workspace(L.nc_patchgan_gp_ws_bytes(*dims), x.device, 'patchgan')
+        check(L.nc_patchgan_gp_fwd(_ptr(packed), _ptr(x), _ptr(g), _ptr(pen), _ptr(saved), *dims, F(constant), F(lambda_gp), _ptr(ws),
+                                   Z(ws.numel()), _stream()), 'nc_patchgan_gp_fwd')
+        ctx.mark_non_differentiable(g)
+        ctx.save_for_backward(x, saved, g)
+        ctx.packed = packed
+        ctx.packed_gen = _param_generation(packed)
+        ctx.cfg = (cfg, dims, [tuple(p.shape) for p in params])
+        return pen, g
+
+    @staticmethod
+    def backward(ctx, dpen, dg):
+        x, saved, g = ctx.saved_tensors
+        (n_layers, ndf, nd, constant, lambda_gp), dims, shapes = ctx.cfg
+        if _param_generation(ctx.packed) != ctx.packed_gen:
+            raise _lib.NcError('fused PatchGAN gradient penalty: the parameters were updated (optimizer step / checkpoint load) between '
+                               'this forward and its backward; the saved activations no longer match them')
+        dpen = dpen.to(torch.float32).contiguous()
+        want_p = any(ctx.needs_input_grad[2:])
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dpar = _grad_target(ctx, 2) if want_p else None  # (x, cfg, *params): the parameters start at input 2
+        L = lib()
+        ws = workspace(L.nc_patchgan_gp_ws_bytes(*dims), x.device, 'patchgan')
+        check(L.nc_patchgan_gp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(g), _ptr(dpen), _ptr(dpar), _ptr(dx), *dims, F(constant),
+                                   F(lambda_gp), _ptr(ws), Z(ws.numel()), _stream()), 'nc_patchgan_gp_bwd')
+        grads = _param_grads(ctx, dpar, shapes, 2) if want_p else [None] * len(shapes)
+        return (dx, None) + tuple(grads)
+
+
+def patchgan_gp(x, params, n_layers, ndf, nd, constant, lambda_gp):
+    """(penalty, gradients) of cal_gradient_penalty (networks.py:321-359) for the 2-D PatchGAN with InstanceNorm on the interpolates
+    x [B, 1, H, W]: penalty = lambda_gp * mean_b (||g_b + 1e-16|| - constant)^2 with g = d(sum D(x))/dx, one C call per direction.
+    `gradients` (g, shape of x) is returned detached -- unlike the reference's, it carries no graph."""
+    return _PatchGANGP.apply(x, (int(n_layers), int(ndf), int(nd), float(constant), float(lambda_gp)), *params)
+
+
 # ---- whole-network KernelGAN discriminator (nc_kgan_fwd / nc_kgan_bwd): one C call per direction ------------------------------
 def kgan_dims(shape, nd):
     """(B, D, H, W) of a KernelPatchDiscriminator input; ValueError, before anything is launched, for the inputs the reference's
