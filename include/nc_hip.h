@@ -315,11 +315,21 @@ size_t nc_unet_deconv_saved_floats(int N, int S0, int S1, int S2);
 size_t nc_unet_deconv_train_ws_bytes(int N, int S0, int S1, int S2);
 /* `kept` (HOST word, out, may be NULL): bit i set = the forward left the three-term (S3) copy of layer i's input in `saved`; hand the
  * same word to the backward that reads this `saved` buffer (0 is always valid: the backward then converts the inputs again).  The
- * word travels with the caller's record of the forward (the autograd context), there is no library-side table. */
+ * word travels with the caller's record of the forward (the autograd context), there is no library-side table.
+ * Bits 16 + i: that copy is a two-term (H2) tensor.  Bits 10 .. 14 (the lean forward, below): the fp32 activation a1 / a2 / b1 / b2 / e2a
+ * (the input of block 1 / 3 / 5 / 6 / 8) was NOT written into `saved` -- the backward reads the kept H2 copy, or writes the tensor again from
+ * raw / mean / rstd into its own workspace when it cannot use that copy (the terms switch moved between the two calls) or when the range
+ * guard may switch to the three-term kernels inside the call (nc_set_h2_guard(2): those build their x operand from the fp32 tensor). */
 int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, float* saved, int N, int S0, int S1, int S2,
                              void* ws, size_t ws_bytes, void* stream, unsigned* kept);
 int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, const float* saved, const float* dy, float* dx,
                        float* dparams, int N, int S0, int S1, int S2, void* ws, size_t ws_bytes, void* stream, unsigned kept);
+/* The lean forms of the two-term training step (default on; NC_UNET_LEAN=0 at load time): the forward does not write fp32 activations whose only
+ * regular reader is a two-term convolution that has its own H2 copy, and the backward (one sample) never expands the rank-one data gradient
+ * behind one_by_one -- block 9's InstanceNorm backward forms w12[c] * s2[v] itself.  Outputs and gradients are bit for bit what the full forms
+ * give.  With nc_set_split_terms(3) or the split kernels off: no effect. */
+void nc_set_unet_lean(int on);
+int nc_get_unet_lean(void);
 size_t nc_deep_linear_param_floats(void);
 size_t nc_deep_linear_saved_floats(int N, int S0, int S1, int S2);
 size_t nc_deep_linear_ws_bytes(int N, int S0, int S1, int S2);

@@ -271,6 +271,10 @@ int instnorm_relu_tail_sigmoid(const float* x, const float* mean, const float* r
                                const float* b2, float* y, int C, long S, hipStream_t s);
 int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
                               float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard = nullptr);
+// The same for ONE sample whose incoming gradient is rank one, w1[c] * dy1[v] (dy1: one channel -- the data gradient of a C -> 1 pointwise
+// convolution, never expanded)
+int instnorm_act_bwd_dbias_h2_rank1(const float* dy1, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
+                                    float* dbias, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard);
 // conv_split.hip: where conv_bwd_s3 keeps the range guard's words of the dY operand at the head of its workspace `ws` (behind the operand's
 // S3 capacity) -- a producer that writes dY there itself (the norm backward) counts into them and conv_bwd_pre is told so (dy_guarded)
 unsigned* conv_bwd_guard_words(void* ws, int N, int K, long S);

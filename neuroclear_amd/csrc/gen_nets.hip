@@ -33,6 +33,23 @@ size_t s3_floats(size_t elems) { return up64((elems * 6 + 3) / 4); }
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- Unet_deconv ---------------------------------------------------------------------------------------------------
+// The LEAN forms of the two-term training step (nc_set_unet_lean, default on): fp32 tensors that only a fallback path reads are not written.
+//   forward   a1, a2, b1, b2, e2a (block outputs that feed neither a pool nor a concat) exist only as the H2 operand of the block behind
+//             them; `kept` bit 10 + j records that tensor j of that list was not written.  A backward that cannot use the kept H2 copy (the
+//             terms switch moved, the shape left the split kernels) or whose range guard may switch to the three-term kernels inside the call
+//             (nc_set_h2_guard(2)) first writes the tensor again from raw / mean / rstd into its own scratch.
+//   backward  the gradient at block 9's output is w12[c] * s2[v]: the InstanceNorm backward forms it from the one-channel s2 (norm_act.hip,
+//             the rank-one form) -- no 64-channel data gradient of one_by_one is written or read.
+// Every lean form applies to a block in the two-term form only; with three terms, the split kernels off or NC_S3_TRAIN_FUSE=0 the calls launch
+// what they launched before.
+std::atomic<int> g_unet_lean{getenv("NC_UNET_LEAN") ? (atoi(getenv("NC_UNET_LEAN")) != 0) : 1};
+constexpr int kLeanBit0 = 10;                     // kept bits 10 .. 14
+constexpr int kLeanBlocks[5] = {1, 3, 5, 6, 8};   // the blocks whose fp32 input the lean forward leaves out (a1, a2, b1, b2, e2a)
+int lean_index(int consumer) {
+  for (int j = 0; j < 5; ++j) if (kLeanBlocks[j] == consumer) return j;
+  return -1;
+}
+
 struct UBlock { int C, K, lvl; };  // 3^3 conv + InstanceNorm + ReLU; lvl 0 = full resolution, 1 = half, 2 = quarter
 const UBlock kUB[10] = {{1, 64, 0},    {64, 64, 0},    {64, 128, 1},  {128, 128, 1}, {128, 256, 2},
                         {256, 256, 2}, {256, 256, 2}, {256, 128, 1}, {128, 128, 1}, {128, 64, 0}};
@@ -130,6 +147,9 @@ size_t u_ws_bytes(const UPlan& p, bool bwd) {
 
 extern "C" {
 
+void nc_set_unet_lean(int on) { g_unet_lean.store(on != 0, std::memory_order_relaxed); }
+int nc_get_unet_lean(void) { return g_unet_lean.load(std::memory_order_relaxed); }
+
 size_t nc_unet_deconv_param_floats(void) { return u_offsets().total; }
 
 size_t nc_unet_deconv_saved_floats(int N, int S0, int S1, int S2) {
@@ -164,6 +184,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   // the S3 form straight into the consumer's slot of `saved` (xs3[i]) instead of a separate conversion pass over the fp32 tensor
   // (k_act_split3; a block fed by a max-pool still converts inside conv_fwd_keep).  NC_S3_TRAIN_FUSE=0: every block converts for itself.
   static const bool fuse_on = !(getenv("NC_S3_TRAIN_FUSE") && atoi(getenv("NC_S3_TRAIN_FUSE")) == 0);
+  const bool lean = g_unet_lean.load(std::memory_order_relaxed) != 0;
   bool use[10], pre[10], h2l[10];  // h2l: the block's operands in the two-term form (nc_set_split_terms(2); conv_split.hip s3_layer_h2)
   ConvDims cd[10];
   for (int i = 0; i < 10; ++i) {
@@ -200,6 +221,9 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     if (epi) NC_TRY(s3x_stats_finalize((const float*)iws, P + o.b[i], N, d[0], d[1], d[2], b.K, 3, 1e-5f, V + p.mean[i], V + p.rstd[i], hs));
     else NC_TRY(nc_instnorm_stats(V + p.raw[i], N * b.K, S, 1e-5f, V + p.mean[i], V + p.rstd[i], iws, p.in_ws, stream));
     if (to >= 0 && use[to]) {  // fp32 (the backward of the pool / the fallback paths read it) AND the consumer's S3 operand in one pass
+      // lean: a tensor whose only regular reader is the two-term block behind it stays unwritten (the backward takes the H2 copy)
+      const int lj = lean && h2l[to] && to_ctot == b.K ? lean_index(to) : -1;
+      if (lj >= 0) { out = nullptr; kept_mask |= 1u << (kLeanBit0 + lj); }
       NC_TRY(act_operand(cd[to], V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, out, (long)out_stride, V + p.xs3[to], N, b.K, S, to_ctot, 0, hs));
       if (to_ctot == b.K) pre[to] = true;  // (a concat input is complete once its second half has been converted, below)
       return NC_OK;
@@ -320,13 +344,28 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
                                true;
   // backward of block i: g = gradient at the block's (post-ReLU) output, dense [N][K][S]; `in` = the block's input.
   // draw <- InstanceNorm/ReLU backward (+ the conv's bias gradient); dW <- wgrad; gin (nullable) <- dgrad
-  auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin) -> int {
+  auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin, bool r1 = false) -> int {
     const UBlock& b = kUB[i];
     const int* d = p.d[b.lvl];
     const long Sl = p.S[b.lvl];
     ConvDims cdk;
     const bool now_h2 = make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk);
     const void* xs = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2 ? (const void*)(V + p.xs3[i]) : nullptr;
+    // a lean forward did not write this block's fp32 input.  The paths below leave `in` alone only when they have the kept copy AND the split
+    // weight gradient AND the range guard cannot switch inside this call: a flagged call builds its three-term x operand from the fp32 tensor
+    // (conv_split.hip run_ws_h2, "the flagged call").  In every other case the tensor is written again (the block in front's normalisation +
+    // ReLU: the bits the full forward stores) into scratch no block's backward uses.
+    const int lj = lean_index(i);
+    if (lj >= 0 && ((kept_mask >> (kLeanBit0 + lj)) & 1) &&
+        !(xs && !h2_guard_can_flip() && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, gin != nullptr, p.conv_ws))) {
+      NC_TRY(nc_instnorm_act_fwd(V + p.raw[i - 1], V + p.mean[i - 1], V + p.rstd[i - 1], 0.f, G + p.T, N * b.C, Sl, stream));
+      in = G + p.T;
+    }
+    if (r1) {  // (block 9, decided below: g is the one-channel s2)
+      NC_TRY(instnorm_act_bwd_dbias_h2_rank1(g, P + o.w[12], V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], b.K, Sl, iws, p.in_ws,
+                                             stream, conv_bwd_guard_words(cws, N, b.K, Sl)));
+      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, h2_guard_can_flip());
+    }
     // the norm's backward writes the convolution's dY straight in S3 form at the head of the convolution workspace (where the
     // conversion phase of the split-operand backward would put it): no fp32 tensor, no conversion pass
     if (fuse_bwd && i >= 1 && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, gin != nullptr, p.conv_ws) &&
@@ -354,10 +393,19 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   NC_TRY(nc_sigmoid_bwd(dy, y, G + p.s1, (long)N * S, stream));
   NC_TRY(nc_conv_wgrad(V + p.t1, G + p.s1, DP + o.w[13], DP + o.b[13], N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
   NC_TRY(nc_conv_dgrad(G + p.s1, P + o.w[13], G + p.s2, N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  // lean (one sample, block 9 in the two-term form with its dY written by the norm backward): one_by_one's data gradient is not expanded --
+  // block 9's InstanceNorm backward forms w12[c] * s2[v] itself; the conditions are block_bwd's own for that path.  (dW12 / db12 stay with the
+  // matrix kernel over e1: their summation order is part of what the step computes.)
+  ConvDims cd9;
+  const bool r1 = g_unet_lean.load(std::memory_order_relaxed) != 0 && N == 1 && fuse_bwd &&
+                  make_dims(cd9, N, 128, d0[0], d0[1], d0[2], 64, 3, 3, 3, 1, 1) && conv_layer_h2(cd9) &&
+                  conv_bwd_pre_supported(N, 128, d0[0], d0[1], d0[2], 64, 3, true, p.conv_ws) && instnorm_bwd_s3_supported(N, 64, S);
   NC_TRY(nc_conv_wgrad(V + p.e1, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
-  NC_TRY(nc_conv_dgrad(G + p.s2, P + o.w[12], G + p.G1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  if (!r1) {
+    NC_TRY(nc_conv_dgrad(G + p.s2, P + o.w[12], G + p.G1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  }
   // ex_conv1_1 (cat1 -> e1)
-  NC_TRY(block_bwd(9, G + p.G1, V + p.cat1, G + p.G2, G + p.G3));
+  NC_TRY(block_bwd(9, r1 ? G + p.s2 : G + p.G1, V + p.cat1, G + p.G2, G + p.G3, r1));
   // t_conv1 (e2b -> cat1[:, 64:])
   const float* g;
   NC_TRY(upper_half(G + p.G3, 128, S, &g));

@@ -413,11 +413,23 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_c8(const float* __restrict
 // of the convolution in front of the norm, and when that convolution's gradients run on the split-operand kernels nothing else reads
 // it -- no fp32 tensor, no separate conversion pass.  Arithmetic and partial-sum order are k_in_bwd_apply's (the same voxels per
 // thread, the same reduction tree per channel): the values split here are bit for bit the values the fp32 pass would have stored.
+// R1 (here and in the two H2 kernels below): the incoming gradient is RANK ONE, dy[c][v] = w1[c] * dy[v] with a one-channel dy -- the data
+// gradient of a K -> 1 pointwise convolution (Unet_deconv's one_by_one behind its last block), formed on the fly instead of read as a K-channel
+// tensor.  r1_product is the value the fp32 matrix kernel of that data gradient stores (one fused multiply-add onto a zero accumulator).
+// (Subnormal products included as long as this file is built with fp32 denormals on, the compiler's default for gfx9: the matrix instruction
+// keeps them whatever the MODE register says, a flush-to-zero build of this kernel would not -- tests/test_gpu_unet_lean.py has a tiny-w12 case.)
+__device__ __forceinline__ float r1_product(float w, float s) {
+  float g = __builtin_fmaf(w, s, 0.f);
+  asm("" : "+v"(g));  // (a rounded value of its own: never contracted into the arithmetic that consumes it)
+  return g;
+}
+
+template <bool R1 = false>
 __global__ __launch_bounds__(256) void k_in_bwd_apply_s3(const float* __restrict__ dy, const float* __restrict__ x,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          float slope, long S, int splits, const double* __restrict__ part,
                                                          uint4* __restrict__ dxs, int cblocks, double* __restrict__ rowpart,
-                                                         const unsigned* __restrict__ guard = nullptr) {
+                                                         const unsigned* __restrict__ guard = nullptr, const float* __restrict__ w1 = nullptr) {
   __shared__ float sm[2][8];
   __shared__ double red[8][4];
   if (guard_skip(guard, 1)) return;  // (the range guard's fallback of k_in_bwd_apply_h2: runs only for a flagged tensor)
@@ -437,15 +449,19 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_s3(const float* __restrict
 #pragma unroll
   for (int j = 0; j < 8; ++j) { m[j] = mean[ncb * 8 + j]; r[j] = rstd[ncb * 8 + j]; m1[j] = sm[0][j]; m2[j] = sm[1][j]; }
   const float* px = x + ncb * 8 * S;
-  const float* pg = dy + ncb * 8 * S;
+  const float* pg = R1 ? dy : dy + ncb * 8 * S;
+  float wj[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) wj[j] = R1 ? w1[ncb * 8 + j] : 0.f;
   double rs[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) rs[j] = 0.0;
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < S; v += (long)gridDim.x * 256) {
     unsigned short e[8][3];
+    const float sv = R1 ? pg[v] : 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float t = in_bwd_value(px[j * S + v], pg[j * S + v], m[j], r[j], m1[j], m2[j], slope);
+      const float t = in_bwd_value(px[j * S + v], R1 ? r1_product(wj[j], sv) : pg[j * S + v], m[j], r[j], m1[j], m2[j], slope);
       rs[j] += (double)t;
       s3_split(t, e[j]);
     }
@@ -471,20 +487,25 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_s3(const float* __restrict
 // before the first element is written, and dx is not: pass 1 also takes max |g| and max |xhat| per instance, and
 //   |dx| = r |g - mean(g) - xhat mean(g xhat)| <= r max|g| (2 + max|xhat|)      (|mean(g xhat)| <= rms(g) rms(xhat) <= max|g|)
 // bounds the tensor from above within a small factor -- fp16's exponent range has room for that (s3_common.hpp).
+// R1 (one sample: inst = channel): the K-channel gradient does not exist as a tensor
+template <bool R1 = false>
 __global__ __launch_bounds__(256) void k_in_bwd_sums_h2(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, float slope, long S, int splits,
-                                                        double* __restrict__ part, unsigned* __restrict__ gmax, unsigned* __restrict__ xmax) {
+                                                        double* __restrict__ part, unsigned* __restrict__ gmax, unsigned* __restrict__ xmax,
+                                                        const float* __restrict__ w1 = nullptr) {
   const int inst = blockIdx.y, sp = blockIdx.x;
   long b, e;
   chunk_range(S, splits, sp, b, e);
   const float m = mean[inst], r = rstd[inst];
   const float* px = x + (long)inst * S;
-  const float* pg = dy + (long)inst * S;
+  const float* pg = R1 ? dy : dy + (long)inst * S;
+  const float w = R1 ? w1[inst] : 0.f;
   double s1 = 0.0, s2 = 0.0;
   unsigned gm = 0, xm = 0;
   for (long i = b + threadIdx.x; i < e; i += 256) {
     const float xh = (px[i] - m) * r;
-    const float g = xh > 0.f ? pg[i] : pg[i] * slope;
+    const float gy = R1 ? r1_product(w, pg[i]) : pg[i];
+    const float g = xh > 0.f ? gy : gy * slope;
     s1 += (double)g;
     s2 = fma((double)g, (double)xh, s2);
     const unsigned gb = __float_as_uint(g) & 0x7fffffffu, xb = __float_as_uint(xh) & 0x7fffffffu;
@@ -528,11 +549,13 @@ __global__ void k_zero_u32(unsigned* p, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
 }
 
+template <bool R1 = false>
 __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict__ dy, const float* __restrict__ x,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          float slope, long S, int splits, const double* __restrict__ part,
                                                          uint4* __restrict__ dxs, int cblocks, double* __restrict__ rowpart,
-                                                         const unsigned* __restrict__ cell, unsigned* __restrict__ guard) {
+                                                         const unsigned* __restrict__ cell, unsigned* __restrict__ guard,
+                                                         const float* __restrict__ w1 = nullptr) {
   __shared__ float sm[2][8];
   __shared__ double red[8][4];
   const long ncb = blockIdx.y;
@@ -554,16 +577,20 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict
 #pragma unroll
   for (int j = 0; j < 8; ++j) { m[j] = mean[ncb * 8 + j]; r[j] = rstd[ncb * 8 + j]; m1[j] = sm[0][j]; m2[j] = sm[1][j]; }
   const float* px = x + ncb * 8 * S;
-  const float* pg = dy + ncb * 8 * S;
+  const float* pg = R1 ? dy : dy + ncb * 8 * S;
+  float wj[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) wj[j] = R1 ? w1[ncb * 8 + j] : 0.f;
   double rs[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) rs[j] = 0.0;
   for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < S; v += (long)gridDim.x * 256) {
     unsigned short e[8][3];
     unsigned mx = 0;
+    const float sv = R1 ? pg[v] : 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float t = in_bwd_value(px[j * S + v], pg[j * S + v], m[j], r[j], m1[j], m2[j], slope);
+      float t = in_bwd_value(px[j * S + v], R1 ? r1_product(wj[j], sv) : pg[j * S + v], m[j], r[j], m1[j], m2[j], slope);
       rs[j] += (double)t;
       asm("" : "+v"(t));
       const unsigned b = __float_as_uint(t) & 0x7fffffffu;
@@ -1006,18 +1033,20 @@ int instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean
   long bx = cdiv(S, 1024);
   if (bx > 1024) bx = 1024;
   double* rowpart = (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S));
-  hipLaunchKernelGGL(k_in_bwd_apply_s3, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                     (const double*)ws, (uint4*)dxs, C / 8, rowpart);
+  hipLaunchKernelGGL(k_in_bwd_apply_s3<false>, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
+                     (const double*)ws, (uint4*)dxs, C / 8, rowpart, (const unsigned*)nullptr, (const float*)nullptr);
   hipLaunchKernelGGL(k_in_dbias_final, dim3(C), dim3(256), 0, s, (const double*)rowpart, N, C, (int)bx, dbias);
   return check_launch("instnorm_act_bwd_dbias_s3");
 }
 // dxs: an H2 tensor [N][C/8][2][S] with its cell at byte offset h2_cells_offset(N * C * S) (cells[0] = cells[1] = the bound) and two
 // arrays of N * C words of scratch behind the cells -- all inside the N * C * S * 6 bytes an S3 tensor of the same shape takes.
-int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
-                              float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard) {
+// w1 != NULL (the rank-one form, N == 1): dy is ONE channel and the gradient at the norm's output is w1[c] * dy[v]
+static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
+                           float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard) {
   if (!dy || !x || !mean || !rstd || !dxs || !dbias) { set_error("instnorm_act_bwd_dbias_h2: null pointer"); return NC_ERR_ARG; }
   if (!instnorm_bwd_s3_supported(N, C, S)) { set_error("instnorm_act_bwd_dbias_h2: bad shape"); return NC_ERR_SHAPE; }
   const int NC = N * C;
+  if (w1 && N != 1) { set_error("instnorm_act_bwd_dbias_h2: the rank-one form takes one sample"); return NC_ERR_ARG; }
   if (!ws || ws_bytes < nc_instnorm_bwd_dbias_ws_bytes(NC, S)) { set_error("instnorm_act_bwd_dbias_h2: workspace too small"); return NC_ERR_WS; }
   if ((size_t)NC * S * 2 < 512 + (size_t)NC * 8) { set_error("instnorm_act_bwd_dbias_h2: tensor too small"); return NC_ERR_SHAPE; }
   hipStream_t s = (hipStream_t)stream;
@@ -1026,7 +1055,11 @@ int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean
   unsigned* xmax = gmax + NC;
   hipLaunchKernelGGL(k_zero_u32, dim3((unsigned)cdiv(64 + 2 * NC, 256)), dim3(256), 0, s, cells, 64 + 2 * NC);
   const int splits = pick_splits(NC, S);
-  hipLaunchKernelGGL(k_in_bwd_sums_h2, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax);
+  if (w1)
+    hipLaunchKernelGGL(k_in_bwd_sums_h2<true>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax, w1);
+  else
+    hipLaunchKernelGGL(k_in_bwd_sums_h2<false>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax,
+                       (const float*)nullptr);
   hipLaunchKernelGGL(k_in_bwd_bound, dim3(1), dim3(256), 0, s, rstd, gmax, xmax, NC, cells, cells + 1, guard);
   long bx = cdiv(S, 1024);
   if (bx > 1024) bx = 1024;
@@ -1036,8 +1069,12 @@ int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean
   // the apply pass counts its low chunks, the decision is taken on the device, and a flagged tensor is written AGAIN by the S3 twin of the
   // apply pass (same values, three exact bf16 terms, over the H2 form: the buffer has the S3 capacity) for the three-term kernels
   unsigned* g = guard && h2_guard_on() ? guard : nullptr;
-  hipLaunchKernelGGL(k_in_bwd_apply_h2, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                     (const double*)ws, (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g);
+  if (w1)
+    hipLaunchKernelGGL(k_in_bwd_apply_h2<true>, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
+                       (const double*)ws, (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g, w1);
+  else
+    hipLaunchKernelGGL(k_in_bwd_apply_h2<false>, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
+                       (const double*)ws, (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g, (const float*)nullptr);
   hipLaunchKernelGGL(k_in_dbias_final, dim3(C), dim3(256), 0, s, (const double*)rowpart, N, C, (int)bx, dbias);
   if (g) {
     // chunks: one per wave and loop iteration = (NC / 8) * sum over blocks of ceil(iterations): every 64-voxel group of every 8-channel block
@@ -1049,10 +1086,23 @@ int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean
     if (int e = h2_guard_decide(g, nullptr, nullptr, g + kGuardFlag, flip, s, total)) return e;
     if (!flip) return check_launch("instnorm_act_bwd_dbias_h2");
     long bx3 = bx < 128 ? bx : 128;  // (usually leaves at once; no row partials: the bias gradient is the H2 pass's)
-    hipLaunchKernelGGL(k_in_bwd_apply_s3, dim3((unsigned)bx3, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                       (const double*)ws, (uint4*)dxs, C / 8, (double*)nullptr, (const unsigned*)g);
+    if (w1)  // (the rewrite takes the gradient from the same source)
+      hipLaunchKernelGGL(k_in_bwd_apply_s3<true>, dim3((unsigned)bx3, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
+                         (const double*)ws, (uint4*)dxs, C / 8, (double*)nullptr, (const unsigned*)g, w1);
+    else
+      hipLaunchKernelGGL(k_in_bwd_apply_s3<false>, dim3((unsigned)bx3, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
+                         (const double*)ws, (uint4*)dxs, C / 8, (double*)nullptr, (const unsigned*)g, (const float*)nullptr);
   }
   return check_launch("instnorm_act_bwd_dbias_h2");
+}
+int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
+                              float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard) {
+  return in_bwd_dbias_h2(dy, nullptr, x, mean, rstd, slope, dxs, dbias, N, C, S, ws, ws_bytes, stream, guard);
+}
+int instnorm_act_bwd_dbias_h2_rank1(const float* dy1, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
+                                    float* dbias, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard) {
+  if (!w1) { set_error("instnorm_act_bwd_dbias_h2_rank1: null pointer"); return NC_ERR_ARG; }
+  return in_bwd_dbias_h2(dy1, w1, x, mean, rstd, slope, dxs, dbias, 1, C, S, ws, ws_bytes, stream, guard);
 }
 int instnorm_relu_tail_sigmoid(const float* x, const float* mean, const float* rstd, const float* w1, const float* b1, const float* w2,
                                const float* b2, float* y, int C, long S, hipStream_t s) {
