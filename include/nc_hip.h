@@ -330,6 +330,28 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
  * give.  With nc_set_split_terms(3) or the split kernels off: no effect. */
 void nc_set_unet_lean(int on);
 int nc_get_unet_lean(void);
+/* Prepared weights of the two-term training step (default on; NC_UNET_WPREP=0 at load time; process-wide, sampled once per call):
+ * nc_unet_deconv_train_fwd computes the weight cells and the two-term packed weights of blocks 1 .. 9 -- forward and data-gradient form, and
+ * the output bounds of the two transposed convolutions that the concat blocks' forward packs need -- in ONE batched pass at its start, into a
+ * region of `saved` (about 54 MB, independent of the crop; nc_unet_deconv_saved_floats counts it), instead of three small launches in front of
+ * every convolution.  `kept` bit 15: the packs are in `saved`.  The backward takes a block's data-gradient pack from there when the bit is set,
+ * the block's form is still the forward's (bits 16 + i, as for the kept operand) and the switch is still on; otherwise it launches what it
+ * launched before.  CONTRACT: with bit 15 set the data gradients of nc_unet_deconv_bwd use the weights AS THEY WERE AT FORWARD TIME (autograd's
+ * semantics); `params` must not change between a forward and its backward (neuroclear_amd.ops refuses such a backward).  Same bits as the
+ * per-layer preparation: outputs and gradients do not change.  Not prepared (per-layer launches as before): three-term blocks
+ * (nc_set_split_terms(3), a call the range guard flags in mode 2 packs its three-term weights itself), the split kernels off, NC_S3_TRAIN_FUSE=0,
+ * and with NC_CONVT_H2=0 the forward packs of blocks 7 and 9 (a measured cell). */
+void nc_set_unet_wprep(int on);
+int nc_get_unet_wprep(void);
+/* Test exports.  nc_unet_wprep_layout: where block `block`'s (1 .. 9) prepared pack of `form` (0 forward, 1 data gradient) lies in `saved`
+ * (byte offsets; cell_off: its weight cell; bound_off: the transposed convolution's bound of blocks 7 / 9, else 0).  nc_s3x_pack_h2_debug: the
+ * PER-LAYER preparation of w[K][C][27] (cell_a / cell_b: device words, the two scale groups of a forward input) into wp / wcell.
+ * nc_convT_h2_bound_debug: the per-layer bound into a zeroed cell. */
+int nc_unet_wprep_layout(int N, int S0, int S1, int S2, int block, int form, size_t* pack_off, size_t* pack_bytes, size_t* cell_off,
+                         size_t* bound_off);
+int nc_s3x_pack_h2_debug(const float* w, int C, int K, int form, const unsigned* cell_a, const unsigned* cell_b, void* wp, unsigned* wcell,
+                         void* stream);
+int nc_convT_h2_bound_debug(const float* w, const float* bias, int C, int K, float in_bound, unsigned* cell, void* stream);
 size_t nc_deep_linear_param_floats(void);
 size_t nc_deep_linear_saved_floats(int N, int S0, int S1, int S2);
 size_t nc_deep_linear_ws_bytes(int N, int S0, int S1, int S2);

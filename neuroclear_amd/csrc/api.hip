@@ -426,14 +426,14 @@ int nc_conv_bwd(const float* x, const float* dy, const float* w, float* dx, floa
 
 namespace nc {
 int conv_fwd_keep(const float* x, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K, int ks,
-                  void* ws, size_t ws_bytes, void* stream, void* xs_keep, bool* kept) {
+                  void* ws, size_t ws_bytes, void* stream, void* xs_keep, bool* kept, const S3xPrepared* prep) {
   ConvDims d;
   *kept = false;
   if (xs_keep && make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && fwd_path(d) == 9 && wgrad_path(d) == 9) {
     if (!x || !w || !y) { set_error("conv_fwd: null pointer"); return NC_ERR_ARG; }
     ProfScope ps(0, 9, d, 0, (hipStream_t)stream);
     *kept = true;
-    return conv_fwd_s3(x, nullptr, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream, xs_keep);
+    return conv_fwd_s3(x, nullptr, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream, xs_keep, nullptr, prep);
   }
   return nc_conv_fwd(x, w, bias, y, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2, ws, ws_bytes, stream);
 }
@@ -446,13 +446,13 @@ bool conv_keep_supported(int N, int C, int D, int H, int W, int K, int ks) {
 
 // forward of such a layer whose input already exists in S3 form (written by the producer: act_split3 / split3_into)
 int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K, int ks, void* ws,
-                 size_t ws_bytes, void* stream, float* stats_part) {
+                 size_t ws_bytes, void* stream, float* stats_part, const S3xPrepared* prep) {
   ConvDims d;
   if (!xs || !w || !y) { set_error("conv_fwd_pre: null pointer"); return NC_ERR_ARG; }
   if (!make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) || fwd_path(d) != 9) { set_error("conv_fwd_pre: layer not on the split-operand kernels"); return NC_ERR_SHAPE; }
   ProfScope ps(0, 9, d, 0, (hipStream_t)stream);
   if (stats_part && !(conv_layer_h2(d) && ks == 3)) { set_error("conv_fwd_pre: epilogue statistics exist for the two-term 3^3 layers only"); return NC_ERR_ARG; }
-  return conv_fwd_s3(nullptr, xs, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream, nullptr, stats_part);
+  return conv_fwd_s3(nullptr, xs, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream, nullptr, stats_part, prep);
 }
 
 // Can the backward of the layer take dY in S3 form at the head of its workspace (conv_bwd_pre)?  want_dx: the data gradient is needed too
@@ -464,7 +464,7 @@ bool conv_bwd_pre_supported(int N, int C, int D, int H, int W, int K, int ks, bo
 // data (dx nullable) + weight gradient with dY ALREADY in S3 form at the start of ws (where conv_bwd_s3's conversion phase puts it);
 // xs (nullable): the layer's input in S3 form, else it is converted from x
 int conv_bwd_pre(const float* x, const void* xs, const float* w, float* dx, float* dw, int N, int C, int D, int H, int W, int K, int ks,
-                 void* ws, size_t ws_bytes, void* stream, bool dy_guarded) {
+                 void* ws, size_t ws_bytes, void* stream, bool dy_guarded, const S3xPrepared* prep) {
   ConvDims d;
   hipStream_t s = (hipStream_t)stream;
   if (!conv_bwd_pre_supported(N, C, D, H, W, K, ks, dx != nullptr, ws_bytes) || !make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2)) {
@@ -474,7 +474,7 @@ int conv_bwd_pre(const float* x, const void* xs, const float* w, float* dx, floa
   if ((!x && !xs) || !w || !dw || !ws) { set_error("conv_bwd_pre: null pointer"); return NC_ERR_ARG; }
   if (dx) {
     ProfScope ps(1, 9, d, 0, s);
-    if (int e = conv_bwd_s3(x, nullptr, w, dx, dw, d, ws, ws_bytes, s, 1, nullptr, dy_guarded)) return e;
+    if (int e = conv_bwd_s3(x, nullptr, w, dx, dw, d, ws, ws_bytes, s, 1, nullptr, dy_guarded, prep)) return e;
   }
   ProfScope ps(2, 9, d, 0, s);
   return conv_bwd_s3(x, nullptr, w, dx, dw, d, ws, ws_bytes, s, 2, xs, dy_guarded);

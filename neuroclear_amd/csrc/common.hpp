@@ -216,8 +216,11 @@ int act_operand(const ConvDims& d, const float* x, const float* mean, const floa
                 long S, int ctot, int c0, hipStream_t s);
 int act_split3(const float* x, const float* mean, const float* rstd, float slope, float* y, long ystride, void* ys, int N, int C, long S,
                int ctot, int c0, hipStream_t s);
+// Two-term packed weights of ONE launch prepared ahead of it (w_prep.hip: the batched pass of the U-Net training step): the fragments
+// k_pack_w_s3x<2> would write and the weights' cell.  Handed down to conv_s3x_h2, which then launches the convolution alone.
+struct S3xPrepared { const void* wp; const unsigned* wcell; };
 int conv_fwd_s3(const float* x, const void* xs, const float* w, const float* b, float* y, const ConvDims& d, void* ws, size_t wsb,
-                hipStream_t s, void* xs_keep = nullptr, float* stats_part = nullptr);
+                hipStream_t s, void* xs_keep = nullptr, float* stats_part = nullptr, const S3xPrepared* prep = nullptr);
 bool epi_stats_on();  // nc_set_epi_stats / NC_EPI_STATS (conv_s3x.hip)
 void epi_stats_set(int on);
 int epi_stats_mode();
@@ -226,23 +229,36 @@ int s3x_w64_get();
 int conv_dgrad_s3(const float* dy, const void* dys, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 size_t s3_bwd_ws_bytes(const ConvDims& d);
 int conv_bwd_s3(const float* x, const float* dy, const float* w, float* dx, float* dw, const ConvDims& d, void* ws, size_t wsb,
-                hipStream_t s, int phase, const void* xs = nullptr, bool dy_guarded = false);
+                hipStream_t s, int phase, const void* xs = nullptr, bool dy_guarded = false, const S3xPrepared* prep = nullptr);  // prep: of the data gradient
 // api.hip: forward / backward of one layer for the whole-network training calls.  conv_fwd_keep: nc_conv_fwd; when the layer runs
 // on the split-operand kernels its converted input is written to xs_keep and *kept set.  conv_bwd_keep: nc_conv_bwd with that
 // tensor handed back (xs NULL: converted again).
 int conv_fwd_keep(const float* x, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K, int ks,
-                  void* ws, size_t ws_bytes, void* stream, void* xs_keep, bool* kept);
+                  void* ws, size_t ws_bytes, void* stream, void* xs_keep, bool* kept, const S3xPrepared* prep = nullptr);
 int conv_bwd_keep(const float* x, const void* xs, const float* dy, const float* w, float* dx, float* dw, int N, int C, int D, int H,
                   int W, int K, int ks, void* ws, size_t ws_bytes, void* stream);
 // conv_s3x.hip: the tap-stream form of the split-operand forward / data-gradient kernel (S3 input, packed weights in wp_ws)
 bool s3x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS);
 size_t s3x_packed_bytes(int Cin, int Kout, int KS, int NT = 3);
+int s3x_ksteps(int Cin, int KS);
+// w_prep.hip: the weight cells and two-term packs of many 3^3 launches in one pass (the U-Net training step).  A segment is one launch's
+// weights in one form: flip = 0 the forward layout of w[Kout][Cin][27] -- a_bits: the cell of the input's first half by value; b_cell: the word
+// of the region's cell block that holds the second half's cell (a transposed convolution's bound, kWPrepBoundCell0 + j), < 0: the same cell;
+// ext_cell (nullable) receives that second cell -- or flip = 1, the data-gradient layout of w[Cin][Kout][27] (Cin = ITS input channels).
+constexpr int kWPrepMaxSegs = 18, kWPrepMaxBounds = 2, kWPrepBoundCell0 = kWPrepMaxSegs, kWPrepCellBytes = 256;
+struct WPrepSeg { const float* w; int Cin, Kout, flip; unsigned a_bits; int b_cell; unsigned* ext_cell; };
+struct WPrepBound { const float* w; const float* bias; int C, K; float in_bound; int cell; };  // convT_h2_bound's arguments (cell: set by wprep_run)
+size_t wprep_bytes(const WPrepSeg* segs, int n);
+int wprep_run(const WPrepSeg* segs, int n, const WPrepBound* bounds, int nb, void* region, S3xPrepared* out, hipStream_t s);
+// the per-layer preparation conv_s3x_h2 launches when nothing was prepared: zero wcell, k_absmax_w, k_pack_w_s3x<2>
+int s3x_pack_h2(const float* w, int Cin, int Kout, int KS, long so, long si, int flip, int split_c, const unsigned* cell_a, const unsigned* cell_b,
+                unsigned* wcell, void* wp_ws, hipStream_t s);
 // NT = 2 (two-term fp16 split, three products; s3_common.hpp) from the fp32 input: ws >= s3x_h2_ws_bytes
 void s3x_set_terms(int t);
 int s3x_get_terms();
 int conv_s3x_h2(const void* xs, const unsigned* cell_a, const unsigned* cell_b, int split_c, const float* w, const float* bias, float* y, int N,
                 int Cin, int D, int H, int W, int Kout, int KS, long so, long si, int flip, unsigned* wcell, void* wp_ws, hipStream_t s,
-                const unsigned* guard = nullptr, float* stats_part = nullptr);
+                const unsigned* guard = nullptr, float* stats_part = nullptr, const S3xPrepared* prep = nullptr);
 // InstanceNorm statistics from the convolution's own epilogue (conv_s3x.hip, template parameter ST): stats_part >= s3x_stats_bytes
 size_t s3x_stats_bytes(int N, int D, int H, int W, int Kout, int KS);
 int s3x_stats_finalize(const float* stats_part, const float* bias, int N, int D, int H, int W, int Kout, int KS, float eps, float* mean, float* rstd,
@@ -320,10 +336,10 @@ bool conv_keep_supported(int N, int C, int D, int H, int W, int K, int ks);
 // stats_part (nullable; two-term 3^3 layers only -- conv_layer_h2): the convolution leaves the partial InstanceNorm sums of its output there
 // (s3x_stats_bytes; s3x_stats_finalize turns them into mean / rstd)
 int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K, int ks, void* ws,
-                 size_t ws_bytes, void* stream, float* stats_part = nullptr);
+                 size_t ws_bytes, void* stream, float* stats_part = nullptr, const S3xPrepared* prep = nullptr);
 bool conv_bwd_pre_supported(int N, int C, int D, int H, int W, int K, int ks, bool want_dx, size_t ws_bytes);
 int conv_bwd_pre(const float* x, const void* xs, const float* w, float* dx, float* dw, int N, int C, int D, int H, int W, int K, int ks,
-                 void* ws, size_t ws_bytes, void* stream, bool dy_guarded = false);
+                 void* ws, size_t ws_bytes, void* stream, bool dy_guarded = false, const S3xPrepared* prep = nullptr);  // prep: of the data gradient
 // norm_act.hip: InstanceNorm + activation backward with dx written in S3 form only
 bool instnorm_bwd_s3_supported(int N, int C, long S);
 int instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,

@@ -40,6 +40,7 @@
 
 #include "common.hpp"
 #include "s3_common.hpp"
+#include "w_prep.hpp"
 
 namespace nc {
 namespace {
@@ -87,59 +88,17 @@ __global__ void __launch_bounds__(256) k_pack_w_s3x(const float* __restrict__ w,
                                                     const unsigned* __restrict__ cell_a, const unsigned* __restrict__ cell_b) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  const int T2 = KS * KS, T3 = T2 * KS, NB = NCH * KS;
-  const int j = (int)(i & 7);
-  long q = i >> 3;
-  const int lane = (int)(q & 63); q >>= 6;
-  const int f = (int)(q % (2 * NT)); q /= 2 * NT;
-  const int s = (int)(q % NS); q /= NS;
-  const int half = (int)(q & 1);
-  const int cot = (int)(q >> 1);
-  const int rb = f / NT, term = f % NT;
-  const int g = lane >> 4, m = lane & 15;
-  const int T = 4 * s + g;
-  const int bi = T / T2, tp = T % T2;
-  unsigned short t[3] = {0, 0, 0};
-  if (bi < NB) {
-    const int chunk = bi / KS, dz = bi % KS;
-#ifdef NC_S3X_B128
-    const int jj = j;  // (experiment: one 16-byte read per B fragment, natural channel order)
-#else
-    const int jj = (g & 1) ? ((j + 4) & 7) : j;
-#endif
-    const long co = cot * 64 + half * 32 + rb * 16 + m, ci = chunk * 8 + jj;
-    const int tap = dz * T2 + tp;
-    const float v = w[co * so + ci * si + (flip ? T3 - 1 - tap : tap)];
-    if constexpr (NT == 3) split3(v, t);
-    else h2_split(v * (ci >= split_c ? h2_group_factor(*cell_a, *cell_b) : 1.f) * h2_scale(*amax), t);
-  }
-  wp[i] = t[term];
+  // (the element itself: w_prep.hpp -- the batched pass of the U-Net training step writes the same bits)
+  if constexpr (NT == 3) wp[i] = pack_w_s3x_elem<3>(w, i, NCH, KS, NS, so, si, flip, 0u, split_c, 0u, 0u);
+  else wp[i] = pack_w_s3x_elem<2>(w, i, NCH, KS, NS, so, si, flip, *amax, split_c, *cell_a, *cell_b);
 }
 
 // Largest finite |w'| of the weights as the pack sees them: w' = w * 2^(kA - kB) for the input channels of the second scale group (a
 // concatenation whose halves were converted with different powers of two: folding the ratio into the weights makes the sum uniform in 2^kA).
 __global__ void __launch_bounds__(256) k_absmax_w(const float* __restrict__ w, long n, int T3, int C, int split_c, const unsigned* __restrict__ cell_a,
                                                   const unsigned* __restrict__ cell_b, unsigned* __restrict__ out) {
-  unsigned m = 0;
-  const float gf = split_c < C ? h2_group_factor(*cell_a, *cell_b) : 1.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int ci = (int)((i / T3) % C);
-    const unsigned b = __float_as_uint(w[i] * (ci >= split_c ? gf : 1.f)) & 0x7fffffffu;
-    if (b < 0x7f800000u && b > m) m = b;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned q = (unsigned)__shfl_xor((int)m, o);
-    m = q > m ? q : m;
-  }
-  __shared__ unsigned wm[4];  // one atomic per block (h2.hip k_absmax)
-  if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned b = wm[0];
-    for (int k = 1; k < 4; ++k) b = wm[k] > b ? wm[k] : b;
-    if (b) atomicMax(out, b);
-  }
+  __shared__ unsigned wm[4];
+  absmax_w_block(w, n, T3, C, split_c, *cell_a, *cell_b, out, blockIdx.x, gridDim.x, wm);  // (w_prep.hpp)
 }
 
 // ---- the pseudo-channel form of a one-input-channel 7^3 layer (k_conv_s3x PC)
@@ -1383,30 +1342,39 @@ bool s3x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS) {
   return x_plan(N, D, H, W, Kout / 64, KS).ok;
 }
 
-// The convolution from an H2 input (h2.hip).  cell_a: the input's cell; a concatenated input whose channels [split_c, Cin) were converted with
-// another cell passes that as cell_b (forward layout of w only), else split_c = Cin.  wcell: one zeroed-by-us cell for the weights,
-// wp_ws >= s3x_packed_bytes(.., 2).
-int conv_s3x_h2(const void* xs, const unsigned* cell_a, const unsigned* cell_b, int split_c, const float* w, const float* bias, float* y, int N,
-                int Cin, int D, int H, int W, int Kout, int KS, long so, long si, int flip, unsigned* wcell, void* wp_ws, hipStream_t s,
-                const unsigned* guard, float* stats_part) {
-  const bool k32 = Kout == 32;  // one 32-channel slice per tile (k_conv_s3x K32): 5^3, no epilogue statistics
-  if (k32 && (KS != 5 || stats_part || guard)) { set_error("conv_s3x_h2: 32 output channels for unguarded 5^3 launches only"); return NC_ERR_SHAPE; }
-  const XPlan pl = x_plan(N, D, H, W, k32 ? 1 : Kout / 64, KS, 2, k32);
-  if (!pl.ok) { set_error("conv_s3x_h2: shape not covered"); return NC_ERR_SHAPE; }
-  if (split_c < Cin && (flip || !cell_b || split_c % 8)) { set_error("conv_s3x_h2: scale groups only for the forward weight layout"); return NC_ERR_ARG; }
-  if (stats_part && KS != 3) { set_error("conv_s3x_h2: epilogue statistics exist for the 3^3 layers only (the layers in front of an InstanceNorm)"); return NC_ERR_ARG; }
+// One layer's two-term weight preparation: its cell (zeroed here), then the packed fragments.  split_c / cell_a / cell_b as conv_s3x_h2.
+int s3x_pack_h2(const float* w, int Cin, int Kout, int KS, long so, long si, int flip, int split_c, const unsigned* cell_a, const unsigned* cell_b,
+                unsigned* wcell, void* wp_ws, hipStream_t s) {
   const int NCH = Cin / 8, NS = s3x_ksteps(Cin, KS), T3 = KS * KS * KS;
-  if (Cin % 32) { set_error("conv_s3x_h2: channels must be a multiple of 32"); return NC_ERR_SHAPE; }
   if (int e = h2_zero_cells(wcell, 1, s)) return e;
   const long nw = (long)Kout * Cin * T3;
-  if (!cell_b) cell_b = cell_a;
   // (the group test below reads the input channel as (i / T3) % Cin: the forward layout [co][ci][tap]; data gradients have no groups)
   hipLaunchKernelGGL(k_absmax_w, dim3((unsigned)(cdiv(nw, 256 * 8) < 256 ? cdiv(nw, 256 * 8) : 256)), dim3(256), 0, s, w, nw, T3, Cin,
                      flip ? Cin : split_c, cell_a, cell_b, wcell);
   const long total = (long)(s3x_packed_bytes(Cin, Kout, KS, 2) / 2);
   hipLaunchKernelGGL(k_pack_w_s3x<2>, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, (unsigned short*)wp_ws, NCH, KS, NS, so, si, flip, total,
                      (const unsigned*)wcell, flip ? Cin : split_c, cell_a, cell_b);
-  if (int e = check_launch("conv_s3x_h2 pack")) return e;
+  return check_launch("conv_s3x_h2 pack");
+}
+
+// The convolution from an H2 input (h2.hip).  cell_a: the input's cell; a concatenated input whose channels [split_c, Cin) were converted with
+// another cell passes that as cell_b (forward layout of w only), else split_c = Cin.  wcell: one zeroed-by-us cell for the weights,
+// wp_ws >= s3x_packed_bytes(.., 2).  prep (nullable): the packed weights and their cell exist already (w_prep.hip) -- no preparation launches.
+int conv_s3x_h2(const void* xs, const unsigned* cell_a, const unsigned* cell_b, int split_c, const float* w, const float* bias, float* y, int N,
+                int Cin, int D, int H, int W, int Kout, int KS, long so, long si, int flip, unsigned* wcell, void* wp_ws, hipStream_t s,
+                const unsigned* guard, float* stats_part, const S3xPrepared* prep) {
+  const bool k32 = Kout == 32;  // one 32-channel slice per tile (k_conv_s3x K32): 5^3, no epilogue statistics
+  if (k32 && (KS != 5 || stats_part || guard)) { set_error("conv_s3x_h2: 32 output channels for unguarded 5^3 launches only"); return NC_ERR_SHAPE; }
+  const XPlan pl = x_plan(N, D, H, W, k32 ? 1 : Kout / 64, KS, 2, k32);
+  if (!pl.ok) { set_error("conv_s3x_h2: shape not covered"); return NC_ERR_SHAPE; }
+  if (split_c < Cin && (flip || !cell_b || split_c % 8)) { set_error("conv_s3x_h2: scale groups only for the forward weight layout"); return NC_ERR_ARG; }
+  if (stats_part && KS != 3) { set_error("conv_s3x_h2: epilogue statistics exist for the 3^3 layers only (the layers in front of an InstanceNorm)"); return NC_ERR_ARG; }
+  const int NCH = Cin / 8, NS = s3x_ksteps(Cin, KS);
+  if (Cin % 32) { set_error("conv_s3x_h2: channels must be a multiple of 32"); return NC_ERR_SHAPE; }
+  if (!cell_b) cell_b = cell_a;
+  if (prep) {  // (k_conv_s3x only reads both)
+    wcell = const_cast<unsigned*>(prep->wcell); wp_ws = const_cast<void*>(prep->wp);
+  } else if (int e = s3x_pack_h2(w, Cin, Kout, KS, so, si, flip, split_c, cell_a, cell_b, wcell, wp_ws, s)) return e;
   XParams p{};
   p.xs = (const uint4*)xs; p.wp = (const uint4*)wp_ws; p.bias = bias; p.y = y; p.amax_x = cell_a; p.amax_w = wcell; p.guard = guard;
   p.N = N; p.NCH = NCH; p.D = D; p.H = H; p.W = W; p.K = Kout;

@@ -498,7 +498,7 @@ bool s3_layer_h2(const ConvDims& d);
 // weight gradient of the same layer wants the same S3 tensor)
 int run_s3(const float* x, const void* xs_pre, const float* w, const float* bias, float* y, const ConvDims& d, int Cin, int Kout,
            long so, long si, int flip, void* ws, size_t wsb, hipStream_t s, void* xs_keep = nullptr, bool h2 = false, unsigned* guard_pre = nullptr,
-           float* stats_part = nullptr) {
+           float* stats_part = nullptr, const S3xPrepared* prep = nullptr) {
   const int KS = d.kd;
   const SPlan pl = s_plan(d.H, d.W, KS);
   const long S = (long)d.D * d.H * d.W;
@@ -532,7 +532,7 @@ int run_s3(const float* x, const void* xs_pre, const float* w, const float* bias
     }
     if (stats_part && dual) { set_error("conv_s3 (two-term): epilogue statistics need an operand that cannot fall back"); return NC_ERR_ARG; }
     if (int e = conv_s3x_h2(xs, cells, cells + 1, flip ? Cin : Cin / 2, w, bias, y, d.N, Cin, d.D, d.H, d.W, Kout, KS, so, si, flip, gw + 16,
-                            (char*)ws + xb + 256, s, dual ? guard : nullptr, stats_part)) return e;
+                            (char*)ws + xb + 256, s, dual ? guard : nullptr, stats_part, prep)) return e;
     if (dual) return conv_s3x(xs, w, bias, y, d.N, Cin, d.D, d.H, d.W, Kout, KS, so, si, flip, (char*)ws + xb + 256, s, guard);
     return NC_OK;
   }
@@ -1517,7 +1517,7 @@ size_t s3_bwd_ws_bytes(const ConvDims& d) {
 }
 unsigned* conv_bwd_guard_words(void* ws, int N, int K, long S) { return (unsigned*)((char*)ws + align256((size_t)N * K * S * 6)); }
 int conv_bwd_s3(const float* x, const float* dy, const float* w, float* dx, float* dw, const ConvDims& d, void* ws, size_t wsb,
-                hipStream_t s, int phase, const void* xs, bool dy_guarded) {  // phase 0: convert dY; 1: data gradient; 2: weight gradient (xs: x in S3, or NULL)
+                hipStream_t s, int phase, const void* xs, bool dy_guarded, const S3xPrepared* prep) {  // phase 0: convert dY; 1: data gradient; 2: weight gradient (xs: x in S3, or NULL)
   const long S = (long)d.D * d.H * d.W;
   const size_t A = align256((size_t)d.N * d.K * S * 6) + 256;
   if (!ws || wsb < s3_bwd_ws_bytes(d)) { set_error("conv_bwd_s3: workspace too small"); return NC_ERR_WS; }
@@ -1546,7 +1546,8 @@ int conv_bwd_s3(const float* x, const float* dy, const float* w, float* dx, floa
     ConvDims t = d;
     t.C = d.K; t.K = d.C;
     const int T3 = d.kd * d.kh * d.kw;
-    return run_s3(dy, ws, w, nullptr, dx, t, d.K, d.C, T3, (long)d.C * T3, 1, (char*)ws + A, wsb - A, s, nullptr, h2, guarded ? yg : nullptr);
+    return run_s3(dy, ws, w, nullptr, dx, t, d.K, d.C, T3, (long)d.C * T3, 1, (char*)ws + A, wsb - A, s, nullptr, h2, guarded ? yg : nullptr, nullptr,
+                  h2 ? prep : nullptr);
   }
   return run_ws(x, xs, dy, ws, dw, d, (char*)ws + A, wsb - A, s, guarded ? yg : nullptr);
 }
@@ -1619,9 +1620,10 @@ ForceThreeTerm::ForceThreeTerm() { ++tl_force3; }
 ForceThreeTerm::~ForceThreeTerm() { --tl_force3; }
 
 int conv_fwd_s3(const float* x, const void* xs, const float* w, const float* b, float* y, const ConvDims& d, void* ws, size_t wsb,
-                hipStream_t s, void* xs_keep, float* stats_part) {
+                hipStream_t s, void* xs_keep, float* stats_part, const S3xPrepared* prep) {
   const int T3 = d.kd * d.kh * d.kw;
-  return run_s3(x, xs, w, b, y, d, d.C, d.K, (long)d.C * T3, T3, 0, ws, wsb, s, xs_keep, s3_layer_h2(d), nullptr, stats_part);
+  return run_s3(x, xs, w, b, y, d, d.C, d.K, (long)d.C * T3, T3, 0, ws, wsb, s, xs_keep, s3_layer_h2(d), nullptr, stats_part,
+                s3_layer_h2(d) ? prep : nullptr);
 }
 
 int conv_dgrad_s3(const float* dy, const void* dys, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {

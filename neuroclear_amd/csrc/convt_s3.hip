@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "s3_common.hpp"
+#include "w_prep.hpp"
 
 namespace nc {
 namespace {
@@ -209,25 +210,7 @@ __global__ void __launch_bounds__(256) k_convT_bound(const float* __restrict__ w
                                                      unsigned* __restrict__ cell) {
   __shared__ float part[4][64];
   __shared__ float red[64];
-  const int col = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int kq = blockIdx.x * 64 + col;  // one (output channel, tap) column: coalesced over the columns
-  float sabs = 0.f;
-  if (kq < K * 8) {
-#pragma unroll 8
-    for (int ci = sl; ci < C; ci += 4) sabs += fabsf(w[(long)ci * K * 8 + kq]);
-  }
-  part[sl][col] = sabs;
-  __syncthreads();
-  if (sl == 0) {
-    const float t = (part[0][col] + part[1][col]) + (part[2][col] + part[3][col]);
-    red[col] = kq < K * 8 ? t * in_bound + (bias ? fabsf(bias[kq >> 3]) : 0.f) : 0.f;
-  }
-  __syncthreads();
-  for (int o = 32; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x + o] > red[threadIdx.x] ? red[threadIdx.x + o] : red[threadIdx.x];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) atomicMax(cell, __float_as_uint(red[0] * 1.001f) & 0x7fffffffu);  // (the cell was zeroed by the caller)
+  convT_bound_block(w, bias, C, K, in_bound, cell, (int)blockIdx.x, part, red);  // (w_prep.hpp: the batched pass computes the same bits)
 }
 
 int qn_for(int C) { return (C / 32) * 8 * 3 * 1024 <= 128 * 1024 ? 8 : 4; }

@@ -54,12 +54,33 @@ struct UBlock { int C, K, lvl; };  // 3^3 conv + InstanceNorm + ReLU; lvl 0 = fu
 const UBlock kUB[10] = {{1, 64, 0},    {64, 64, 0},    {64, 128, 1},  {128, 128, 1}, {128, 256, 2},
                         {256, 256, 2}, {256, 256, 2}, {256, 128, 1}, {128, 128, 1}, {128, 64, 0}};
 
+// PREPARED WEIGHTS of the two-term training step (nc_set_unet_wprep, default on; w_prep.hip): the forward computes the weight cells and the packed
+// weights of blocks 1 .. 9, forward AND data-gradient form, in one batched pass at its start and keeps them in `saved` (UPlan::wprep); every
+// two-term convolution of the forward and of the backward then launches alone.  `kept` bit 15 records that the packs exist; the backward uses a
+// block's data-gradient pack when the block's form is still the forward's (kept bit 16 + i against the terms switch now, the test its kept H2
+// operand gets).  The data gradients therefore see the weights of FORWARD time -- autograd's semantics; the weight tensors are not read again
+// for them.  Blocks 7 and 9 take a concatenation: their forward packs fold in the ratio of the two halves' cells, the InstanceNorm bound and the
+// transposed convolution's output bound (convt_s3.hip), which the pass computes from the weights as well; with NC_CONVT_H2=0 that half's cell is
+// measured, and those two forward packs stay with the per-layer launches.
+std::atomic<int> g_unet_wprep{getenv("NC_UNET_WPREP") ? (atoi(getenv("NC_UNET_WPREP")) != 0) : 1};
+constexpr unsigned kKeptWPrep = 1u << 15;
+// segment 2 (i - 1) + form of block i (form 0: forward, 1: data gradient); all 18 have their place in the region whichever of them a call prepares
+void wprep_segs(WPrepSeg (&sg)[18]) {
+  for (int i = 1; i < 10; ++i) {
+    sg[2 * (i - 1)] = WPrepSeg{nullptr, kUB[i].C, kUB[i].K, 0, 0u, -1, nullptr};
+    sg[2 * (i - 1) + 1] = WPrepSeg{nullptr, kUB[i].K, kUB[i].C, 1, 0u, -1, nullptr};
+  }
+}
+unsigned f32_bits(float f) { unsigned b; __builtin_memcpy(&b, &f, 4); return b; }
+
+
 struct UPlan {
   int N, d[3][3];      // spatial size per level
   long S[3];           // voxels per level
   // saved (floats): activations, raw conv outputs, statistics
   size_t a1, cat1, p1, a2, cat2, p2, b1, b2, b3, e2a, e2b, e1, t1, raw[10], mean[10], rstd[10], saved;
   size_t xs3[10];      // S3 copy of block i's input (i >= 1), see `kept`
+  size_t wprep;        // the prepared weights (w_prep.hip wprep_run's region), see kKeptWPrep
   // backward scratch (floats)
   size_t G1, G2, G3, H1, H2, H3, Q1, Q2, s1, s2, T, grads;
   size_t conv_ws, in_ws, convT_ws;  // bytes
@@ -86,6 +107,12 @@ bool u_plan(UPlan& p, int N, int S0, int S1, int S2) {
     p.rstd[i] = take(n * kUB[i].K);
   }
   for (int i = 1; i < 10; ++i) { p.xs3[i] = off; off += s3_floats(n * kUB[i].C * (size_t)p.S[kUB[i].lvl]); }
+  {
+    WPrepSeg sg[18];
+    wprep_segs(sg);
+    p.wprep = off;
+    off += up64((wprep_bytes(sg, 18) + 3) / 4);
+  }
   p.saved = off;
   off = 0;
   p.G1 = take(n * 64 * S); p.G2 = take(n * 64 * S); p.G3 = take(n * 128 * S);
@@ -147,10 +174,40 @@ size_t u_ws_bytes(const UPlan& p, bool bwd) {
 
 extern "C" {
 
+void nc_set_unet_wprep(int on) { g_unet_wprep.store(on != 0, std::memory_order_relaxed); }
+int nc_get_unet_wprep(void) { return g_unet_wprep.load(std::memory_order_relaxed); }
 void nc_set_unet_lean(int on) { g_unet_lean.store(on != 0, std::memory_order_relaxed); }
 int nc_get_unet_lean(void) { return g_unet_lean.load(std::memory_order_relaxed); }
 
 size_t nc_unet_deconv_param_floats(void) { return u_offsets().total; }
+
+int nc_unet_wprep_layout(int N, int S0, int S1, int S2, int block, int form, size_t* pack_off, size_t* pack_bytes, size_t* cell_off,
+                         size_t* bound_off) {
+  UPlan p;
+  if (!u_plan(p, N, S0, S1, S2) || block < 1 || block > 9 || form < 0 || form > 1) { set_error("unet_wprep_layout: bad argument"); return NC_ERR_ARG; }
+  WPrepSeg sg[18];
+  wprep_segs(sg);
+  const int k = 2 * (block - 1) + form;
+  size_t off = kWPrepCellBytes;
+  for (int j = 0; j < k; ++j) off += s3x_packed_bytes(sg[j].Cin, sg[j].Kout, 3, 2);
+  if (pack_off) *pack_off = p.wprep * 4 + off;
+  if (pack_bytes) *pack_bytes = s3x_packed_bytes(sg[k].Cin, sg[k].Kout, 3, 2);
+  if (cell_off) *cell_off = p.wprep * 4 + (size_t)k * 4;
+  // (bounds are numbered in block order: 7 first when both are computed -- the default configuration)
+  if (bound_off) *bound_off = block == 7 ? p.wprep * 4 + (size_t)kWPrepBoundCell0 * 4 : block == 9 ? p.wprep * 4 + (size_t)(kWPrepBoundCell0 + 1) * 4 : 0;
+  return NC_OK;
+}
+int nc_s3x_pack_h2_debug(const float* w, int C, int K, int form, const unsigned* cell_a, const unsigned* cell_b, void* wp, unsigned* wcell,
+                         void* stream) {
+  if (!w || !cell_a || !cell_b || !wp || !wcell || C % 64 || K % 64) { set_error("s3x_pack_h2_debug: bad argument"); return NC_ERR_ARG; }
+  if (form) return s3x_pack_h2(w, K, C, 3, 27, (long)C * 27, 1, K, cell_a, cell_a, wcell, wp, (hipStream_t)stream);
+  return s3x_pack_h2(w, C, K, 3, (long)C * 27, 27, 0, C / 2, cell_a, cell_b, wcell, wp, (hipStream_t)stream);
+}
+int nc_convT_h2_bound_debug(const float* w, const float* bias, int C, int K, float in_bound, unsigned* cell, void* stream) {
+  if (!w || !cell) { set_error("convT_h2_bound_debug: null pointer"); return NC_ERR_ARG; }
+  NC_TRY(h2_zero_cells(cell, 1, (hipStream_t)stream));
+  return convT_h2_bound(w, bias, C, K, in_bound, cell, (hipStream_t)stream);
+}
 
 size_t nc_unet_deconv_saved_floats(int N, int S0, int S1, int S2) {
   UPlan p;
@@ -194,10 +251,62 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     pre[i] = false;
     h2l[i] = make_dims(cd[i], N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && use[i] && conv_layer_h2(cd[i]);
   }
+  const long S = p.S[0], Sh = p.S[1], Sq = p.S[2];
+  const int *d0 = p.d[0], *d1 = p.d[1], *d2 = p.d[2];
+  // The transposed convolutions run on the bf16 matrix cores from an S3 copy of their input (convt_s3.hip; the fp32 input stays in
+  // `saved` for their backward) whenever the split-operand kernels are on (the layer-by-layer host path makes the same choice:
+  // nc_convT_k2s2_split_active), and write the S3 form of their half of the concatenation themselves when the consuming block takes it
+  const bool ct2 = nc_convT_k2s2_split_active(1, 256, d2[0], d2[1], d2[2], 128) &&
+                   p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 256, d2[0], d2[1], d2[2], 128);
+  // Two-term form: the transposed convolution writes the H2 form of its half itself -- its power of two comes from a BOUND (one tap per input
+  // channel and output voxel: max column sum of |w| times the InstanceNorm bound of its input, convt_s3.hip), so nothing is measured and the
+  // whole forward is independent of what else is in the batch.  NC_CONVT_H2=0: fp32 output, measured and converted.
+  static const bool ct_h2 = !(getenv("NC_CONVT_H2") && atoi(getenv("NC_CONVT_H2")) == 0);
+  const bool ct2h = ct2 && h2l[7] && ct_h2;
+  const bool ct1 = nc_convT_k2s2_split_active(1, 128, d1[0], d1[1], d1[2], 64) &&
+                   p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 128, d1[0], d1[1], d1[2], 64);
+  const bool ct1h = ct1 && h2l[9] && ct_h2;
+  unsigned* cell7 = h2_cells_of(V + p.xs3[7], (size_t)N * 256 * Sh) + 1;
+  unsigned* cell9 = h2_cells_of(V + p.xs3[9], (size_t)N * 128 * S) + 1;
+  unsigned kept_mask = 0;
+  // the prepared weights (see kKeptWPrep): every two-term block's cells and packs, both forms, before the first convolution
+  S3xPrepared prep[18] = {};
+  bool bound7 = false, bound9 = false;  // the pass set cell7 / cell9
+  if (g_unet_wprep.load(std::memory_order_relaxed) != 0) {
+    WPrepSeg sg[18];
+    wprep_segs(sg);
+    WPrepBound wb[2];
+    int nb = 0, any = 0;
+    for (int i = 1; i < 10; ++i) {
+      if (!h2l[i]) continue;
+      WPrepSeg& f = sg[2 * (i - 1)];
+      // the input's first cell: the InstanceNorm bound of its level (h2.hip act_split2h) -- or, behind a max-pool, a measured cell that both
+      // halves share: the ratio is 1 whatever the value
+      f.a_bits = f32_bits(sqrtf((float)p.S[kUB[i].lvl]));
+      f.w = P + o.w[i];
+      if (i == 7 || i == 9) {
+        if (i == 7 ? ct2h : ct1h) {
+          f.b_cell = kWPrepBoundCell0 + nb;
+          f.ext_cell = i == 7 ? cell7 : cell9;
+          wb[nb++] = i == 7 ? WPrepBound{P + o.w[10], P + o.b[10], 256, 128, sqrtf((float)Sq), 0}
+                            : WPrepBound{P + o.w[11], P + o.b[11], 128, 64, sqrtf((float)Sh), 0};
+          (i == 7 ? bound7 : bound9) = true;
+        } else {
+          f.w = nullptr;  // (a measured second cell: the per-layer launches)
+        }
+      }
+      sg[2 * (i - 1) + 1].w = P + o.w[i];
+      any = 1;
+    }
+    if (any) {
+      NC_TRY(wprep_run(sg, 18, wb, nb, V + p.wprep, prep, hs));
+      kept_mask |= kKeptWPrep;
+    }
+  }
+  auto prep_of = [&](int seg) -> const S3xPrepared* { return prep[seg].wp ? &prep[seg] : nullptr; };
   // conv (3^3, pad 1) -> raw; statistics; normalise + ReLU into `out`, where sample n's K planes start at
   // out + n * out_stride (out_stride = K * S for a dense tensor, Ctot * S for a half of a concat buffer).
   // to >= 0: block `to` consumes this output as channels [0, K) of its `to_ctot`-channel input
-  unsigned kept_mask = 0;
   auto block = [&](int i, const float* in, float* out, size_t out_stride, int to, int to_ctot) -> int {
     const UBlock& b = kUB[i];
     const int* d = p.d[b.lvl];
@@ -208,13 +317,13 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     const bool epi = pre[i] && h2l[i] && epi_stats_mode() == 2 && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) <= p.in_ws;
     if (pre[i]) {  // the producers left the S3 input in saved
       NC_TRY(conv_fwd_pre(V + p.xs3[i], P + o.w[i], P + o.b[i], V + p.raw[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream,
-                          epi ? (float*)iws : nullptr));
+                          epi ? (float*)iws : nullptr, i >= 1 ? prep_of(2 * (i - 1)) : nullptr));
       kept_mask |= 1u << i;
       if (h2l[i]) kept_mask |= 1u << (16 + i);  // (bits 16..: the kept copy is an H2 tensor -- a backward under another setting of the switch ignores it)
     } else {
       bool kept1 = false;
       NC_TRY(conv_fwd_keep(in, P + o.w[i], P + o.b[i], V + p.raw[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream,
-                           i >= 1 ? (void*)(V + p.xs3[i]) : nullptr, &kept1));
+                           i >= 1 ? (void*)(V + p.xs3[i]) : nullptr, &kept1, i >= 1 ? prep_of(2 * (i - 1)) : nullptr));
       if (kept1) kept_mask |= 1u << i;
       if (kept1 && i >= 1 && conv_layer_h2(cd[i])) kept_mask |= 1u << (16 + i);
     }
@@ -235,8 +344,6 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
                                  out + n * out_stride, b.K, S, stream));
     return NC_OK;
   };
-  const long S = p.S[0], Sh = p.S[1], Sq = p.S[2];
-  const int *d0 = p.d[0], *d1 = p.d[1], *d2 = p.d[2];
   NC_TRY(block(0, x, V + p.a1, (size_t)64 * S, 1, 64));
   NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128));
   for (int n = 0; n < N; ++n)
@@ -248,18 +355,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   NC_TRY(block(4, V + p.p2, V + p.b1, (size_t)256 * Sq, 5, 256));
   NC_TRY(block(5, V + p.b1, V + p.b2, (size_t)256 * Sq, 6, 256));
   NC_TRY(block(6, V + p.b2, V + p.b3, (size_t)256 * Sq, -1, 0));
-  // The transposed convolutions run on the bf16 matrix cores from an S3 copy of their input (convt_s3.hip; the fp32 input stays in
-  // `saved` for their backward) whenever the split-operand kernels are on (the layer-by-layer host path makes the same choice:
-  // nc_convT_k2s2_split_active), and write the S3 form of their half of the concatenation themselves when the consuming block takes it
-  const bool ct2 = nc_convT_k2s2_split_active(1, 256, d2[0], d2[1], d2[2], 128) &&
-                   p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 256, d2[0], d2[1], d2[2], 128);
-  // Two-term form: the transposed convolution writes the H2 form of its half itself -- its power of two comes from a BOUND (one tap per input
-  // channel and output voxel: max column sum of |w| times the InstanceNorm bound of its input, convt_s3.hip), so nothing is measured and the
-  // whole forward is independent of what else is in the batch.  NC_CONVT_H2=0: fp32 output, measured and converted.
-  static const bool ct_h2 = !(getenv("NC_CONVT_H2") && atoi(getenv("NC_CONVT_H2")) == 0);
-  const bool ct2h = ct2 && h2l[7] && ct_h2;
-  unsigned* cell7 = h2_cells_of(V + p.xs3[7], (size_t)N * 256 * Sh) + 1;
-  if (ct2h) {
+  if (ct2h && !bound7) {  // (the prepared pass leaves the bound in cell7 itself)
     NC_TRY(h2_zero_cells(cell7, 1, hs));
     NC_TRY(convT_h2_bound(P + o.w[10], P + o.b[10], 256, 128, sqrtf((float)Sq), cell7, hs));
   }
@@ -282,12 +378,8 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   }
   NC_TRY(block(7, V + p.cat2, V + p.e2a, (size_t)128 * Sh, 8, 128));
   NC_TRY(block(8, V + p.e2a, V + p.e2b, (size_t)128 * Sh, -1, 0));
-  const bool ct1 = nc_convT_k2s2_split_active(1, 128, d1[0], d1[1], d1[2], 64) &&
-                   p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 128, d1[0], d1[1], d1[2], 64);
   const bool ct_s3 = use[9] && !h2l[9] && (ct1 || convT_fwd_s3_supported(1, 128, d1[0], d1[1], d1[2], 64));  // t_conv1 writes the S3 form of its output itself
-  const bool ct1h = ct1 && h2l[9] && ct_h2;
-  unsigned* cell9 = h2_cells_of(V + p.xs3[9], (size_t)N * 128 * S) + 1;
-  if (ct1h) {
+  if (ct1h && !bound9) {
     NC_TRY(h2_zero_cells(cell9, 1, hs));
     NC_TRY(convT_h2_bound(P + o.w[11], P + o.b[11], 128, 64, sqrtf((float)Sh), cell9, hs));
   }
@@ -342,6 +434,18 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   const unsigned kept_mask = kept;
   static const bool fuse_bwd = !(getenv("NC_S3_TRAIN_FUSE") && atoi(getenv("NC_S3_TRAIN_FUSE")) == 0) &&
                                true;
+  const bool wprep_now = g_unet_wprep.load(std::memory_order_relaxed) != 0;
+  S3xPrepared prepd[10] = {};  // block i's data-gradient pack in `saved` (wprep_run's layout: cells, then the segments in order)
+  {
+    WPrepSeg sg[18];
+    wprep_segs(sg);
+    const char* region = (const char*)(V + p.wprep);
+    size_t off = kWPrepCellBytes;
+    for (int k = 0; k < 18; ++k) {
+      if (k & 1) prepd[k / 2 + 1] = S3xPrepared{region + off, (const unsigned*)region + k};
+      off += s3x_packed_bytes(sg[k].Cin, sg[k].Kout, 3, 2);
+    }
+  }
   // backward of block i: g = gradient at the block's (post-ReLU) output, dense [N][K][S]; `in` = the block's input.
   // draw <- InstanceNorm/ReLU backward (+ the conv's bias gradient); dW <- wgrad; gin (nullable) <- dgrad
   auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin, bool r1 = false) -> int {
@@ -351,6 +455,8 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
     ConvDims cdk;
     const bool now_h2 = make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk);
     const void* xs = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2 ? (const void*)(V + p.xs3[i]) : nullptr;
+    // the data-gradient pack the forward prepared, under the same test (see kKeptWPrep); nc_set_unet_wprep(0) now: the per-layer launches
+    const S3xPrepared* pd = i >= 1 && gin && now_h2 && (kept_mask & kKeptWPrep) && ((kept_mask >> (16 + i)) & 1) && wprep_now ? &prepd[i] : nullptr;
     // a lean forward did not write this block's fp32 input.  The paths below leave `in` alone only when they have the kept copy AND the split
     // weight gradient AND the range guard cannot switch inside this call: a flagged call builds its three-term x operand from the fp32 tensor
     // (conv_split.hip run_ws_h2, "the flagged call").  In every other case the tensor is written again (the block in front's normalisation +
@@ -364,7 +470,7 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
     if (r1) {  // (block 9, decided below: g is the one-channel s2)
       NC_TRY(instnorm_act_bwd_dbias_h2_rank1(g, P + o.w[12], V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], b.K, Sl, iws, p.in_ws,
                                              stream, conv_bwd_guard_words(cws, N, b.K, Sl)));
-      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, h2_guard_can_flip());
+      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, h2_guard_can_flip(), pd);
     }
     // the norm's backward writes the convolution's dY straight in S3 form at the head of the convolution workspace (where the
     // conversion phase of the split-operand backward would put it): no fp32 tensor, no conversion pass
@@ -375,7 +481,7 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
                                          conv_bwd_guard_words(cws, N, b.K, Sl)));
       else
         NC_TRY(instnorm_act_bwd_dbias_s3(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream));
-      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, now_h2 && h2_guard_can_flip());
+      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, now_h2 && h2_guard_can_flip(), pd);
     }
     NC_TRY(nc_instnorm_act_bwd_dbias(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, draw, DP + o.b[i], N, b.K, Sl, iws,
                                      p.in_ws, stream));

@@ -970,16 +970,25 @@ def _param_generation(t):
     return _param_gen.get(t.untyped_storage().data_ptr(), 0)
 
 
+def _param_versions(packed):
+    """Autograd's version counters of the packed parameters: of the view itself (it shares the first parameter's) and, when the parameters
+    live in a registered flat buffer (FlatAdam: p.data are views of it, with counters of their own), of that buffer."""
+    flat = _flat_bufs.get(packed.untyped_storage().data_ptr())
+    return packed._version, (flat._version if flat is not None else None)
+
+
 # Direct gradient destination of the whole-network calls.  FlatAdam registers its flat gradient buffer under its flat
 # parameter buffer's storage; when a whole-network backward finds that its packed parameters ARE a slice of such a
 # buffer, it lets the kernels write the parameter gradients straight into the matching slice of the gradient buffer
 # (they overwrite, so only the first backward of a slice per optimizer step may do that) and returns views of it: with
 # p.grad = None autograd's AccumulateGrad adopts them -- no per-parameter add kernels, no extra copy.
 _flat_grads = {}   # storage ptr of the flat parameter buffer -> [grad buffer, set of slices written this step]
+_flat_bufs = {}    # the same key -> the flat parameter buffer itself (its version counter: _param_versions)
 
 
 def register_flat_grad(flat, grad):
     _flat_grads[flat.untyped_storage().data_ptr()] = [grad, set()]
+    _flat_bufs[flat.untyped_storage().data_ptr()] = flat
 
 
 def flat_grad_step_begin(flat):
@@ -1430,13 +1439,15 @@ class _UnetDeconvTrain(torch.autograd.Function):
         ctx.save_for_backward(x, y, saved)
         ctx.packed = packed
         ctx.packed_gen = _param_generation(packed)
+        ctx.packed_version = _param_versions(packed)
         ctx.shapes = [tuple(p.shape) for p in params]
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, saved = ctx.saved_tensors
-        if _param_generation(ctx.packed) != ctx.packed_gen:
+        # (the backward's data gradients take the packed weights the forward prepared, its weight-space reads the live buffer: nc_hip.h)
+        if _param_generation(ctx.packed) != ctx.packed_gen or _param_versions(ctx.packed) != ctx.packed_version:
             raise _lib.NcError('fused Unet_deconv: the parameters were updated between this forward and its backward')
         dy = dy.contiguous()
         N, _, S0, S1, S2 = x.shape
