@@ -552,6 +552,39 @@ size_t nc_convT_k2s2_split_ws_bytes(int N, int C, int D, int H, int W, int K);
 int nc_convT_k2s2_fwd_split(const float* x, const void* xs, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0,
                             int N, int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
 
+/* Test exports of the WRITERS of the two-term form (csrc/h2_debug.hip; tests/test_gpu_h2_writers.py): each validates its arguments and forwards,
+ * unchanged, to the internal function the whole-network calls use.  "H2" tensor: [N][ctot/8][2 terms][S][8] fp16 = the two terms of the element
+ * times 2^k, k from a CELL (the float bits of a magnitude that bounds the tensor); the cells -- [0] for the first half of the channels, [1] for
+ * the second -- sit nc_h2_cells_offset(N * ctot * S) bytes behind the start, nc_h2_bytes = that offset + 256.  cell / cell2 / out_cell / guard
+ * are device words; a part is channels [c0, c0 + C) of a ctot-channel tensor, everything % 8.
+ * nc_to_h2_debug: bound > 0: h2_set_cell(cell, bound), else the cell is measured (h2_zero_cells, h2_absmax per sample); guard (nullable, 8
+ *   words, zeroed here) receives the range guard's chunk counts; then split2h_into.
+ * nc_act_split2h_debug: act_split2h (InstanceNorm normalisation + (Leaky)ReLU; y, cell, cell2 nullable).
+ * nc_act_split2h_pool_debug: act_split2h_pool (the same and MaxPool3d(2) of the result into `pooled`, a DENSE C-channel tensor; cell nullable).
+ * nc_maxpool2_h2_debug: maxpool2_h2 (channels [0, C) of a ctot-channel tensor -> a dense C-channel tensor).
+ * nc_h2_to_s3_if_debug: h2_to_s3_if (the S3 form of an H2 tensor; runs when guard is NULL or its flag word [2] is set).
+ * nc_instnorm_act_bwd_dbias_h2_debug: instnorm_act_bwd_dbias_h2, or with w1 != NULL instnorm_act_bwd_dbias_h2_rank1 (N == 1, dy one channel,
+ *   the gradient is w1[c] * dy[v]); dxs has the capacity of the S3 tensor (nc_s3_bytes), its cells at nc_h2_cells_offset(N * C * S); workspace
+ *   nc_instnorm_bwd_dbias_ws_bytes; guard nullable.
+ * nc_convT_k2s2_fwd_split_h2_debug: convT_h2_bound(w, bias, in_bound = sqrt(D H W)) into the zeroed *out_cell, then convT_fwd_split_h2 (x fp32,
+ *   |x| <= sqrt(D H W), converted into the workspace; y nullable; ys = channels [ys_c0, ys_c0 + K) of a ys_ctot-channel H2 tensor of the output
+ *   volume, converted with *out_cell). */
+size_t nc_h2_bytes(int N, int C, long S);
+size_t nc_h2_cells_offset(size_t elems);
+int nc_to_h2_debug(const float* x, long xstride, void* xs, int N, int C, long S, int ctot, int c0, unsigned* cell, float bound, unsigned* guard,
+                   void* stream);
+int nc_act_split2h_debug(const float* x, const float* mean, const float* rstd, float slope, float* y, long ystride, void* ys, int N, int C, long S,
+                         int ctot, int c0, float bound, unsigned* cell, unsigned* cell2, void* stream);
+int nc_act_split2h_pool_debug(const float* x, const float* mean, const float* rstd, float slope, void* ys, void* pooled, int N, int C, int D, int H,
+                              int W, int ctot, int c0, float bound, unsigned* cell, void* stream);
+int nc_maxpool2_h2_debug(const void* in, void* out, int N, int C, int ctot, int D, int H, int W, void* stream);
+int nc_h2_to_s3_if_debug(const void* xh, void* xs, int N, int C, long S, const unsigned* cells, const unsigned* guard, void* stream);
+int nc_instnorm_act_bwd_dbias_h2_debug(const float* dy, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
+                                       float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, unsigned* guard, void* stream);
+size_t nc_convT_k2s2_split_h2_ws_bytes(int N, int C, int D, int H, int W, int K);
+int nc_convT_k2s2_fwd_split_h2_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C,
+                                     int D, int H, int W, int K, unsigned* out_cell, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Learned-PSF generators (--netG_B linearkernel / linearkernel_double / linearkernel_LK31): LinearKernel and LinearKernel_double at
  *      models/networks.py:840-871, one bias-free Conv3d(1, 1, k, stride 1, padding (k - 1) / 2) -- applied twice with one weight in the
  *      _double form -- and its autograd backward (loss.backward(), apollo:283).  x, y, dy, dx: [N][1][D][H][W]; w, dw: [1][1][k][k][k].
