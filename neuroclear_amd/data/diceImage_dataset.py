@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from .._lib import I, P, check, lib
+from .._lib import P, check, lib
 from ..util import util
 
 
@@ -71,8 +71,8 @@ class DiceImageDataSet:
         E = self.roi_size + 2 * self.border_cut
         cube = torch.empty((1, E, E, E), dtype=torch.float32, device=self.device)
         L0, L1, L2 = self.image_size_original
-        check(lib().nc_dice_cut_cube(P(self.volume.data_ptr()), I(1 if self.is_u16 else 0), I(L0), I(L1), I(L2),
-                                     I(self.roi_size), I(self.overlap), I(self.border_cut), I(int(index)),
+        check(lib().nc_dice_cut_cube(P(self.volume.data_ptr()), 1 if self.is_u16 else 0, L0, L1, L2,
+                                     self.roi_size, self.overlap, self.border_cut, int(index),
                                      P(cube.data_ptr()), P(torch.cuda.current_stream().cuda_stream)),
               'nc_dice_cut_cube')
         return {'A': cube, 'A_paths': str(index)}

@@ -14,7 +14,7 @@ import random
 import numpy as np
 import torch
 
-from .._lib import I, P, check, lib
+from .._lib import P, check, lib
 from . import rotation
 from .diceImage_dataset import _load_volume
 
@@ -66,8 +66,8 @@ class SingleVolumeDataset:
         x = random.randint(0, rw - cx)
         out = torch.empty((cz, cy, cx), dtype=torch.float32, device=self.device)
         m = inv.ctypes.data_as(P)
-        check(lib().nc_rotate_crop(P(self.raw.data_ptr()), I(1 if self.is_u16 else 0), I(D), I(H), I(W), I(z), I(y1 + y),
-                                   I(x1 + x), I(cz), I(cy), I(cx), m, P(out.data_ptr()),
+        check(lib().nc_rotate_crop(P(self.raw.data_ptr()), 1 if self.is_u16 else 0, D, H, W, z, y1 + y,
+                                   x1 + x, cz, cy, cx, m, P(out.data_ptr()),
                                    P(torch.cuda.current_stream().cuda_stream)), 'nc_rotate_crop')
         return out
 

@@ -2,6 +2,7 @@
 optimize_parameters / test / setup / eval / get_current_visuals / get_current_losses / save_networks / load_networks /
 update_learning_rate / set_requires_grad -- same names, same semantics, same checkpoint file naming
 (`<checkpoints_dir>/<name>/<epoch>_net_<Name>.pth`, plain state dicts with the reference's keys)."""
+import ctypes
 import os
 from abc import ABC, abstractmethod
 from collections import OrderedDict
@@ -108,7 +109,6 @@ class BaseModel(ABC):
         process-wide (one library, one arithmetic), which is why every model that observes a flag repeats the warning instead of inheriting the
         state silently.  Data-parallel runs: the flag is all-reduced (MAX) so that every rank switches at the same step -- every rank has to
         call get_current_losses() at the same iterations (train_onecube.py and bench.py do)."""
-        import ctypes
         from .._lib import lib
         L = lib()
         two_term = L.nc_get_split_terms() == 2 and bool(L.nc_get_h2_guard())

@@ -19,7 +19,7 @@ from torch.nn import init
 from torch.optim import lr_scheduler
 
 from .. import ops
-from .._lib import F, I, P, Z, check, lib
+from .._lib import P, check, lib
 
 
 class Identity(nn.Module):
@@ -363,14 +363,14 @@ class Unet_deconv(nn.Module):
     def _forward_fused(self, x):
         x = x.contiguous()
         N, _, S0, S1, S2 = x.shape
-        nb = lib().nc_unet_deconv_fwd_ws_bytes(I(N), I(S0), I(S1), I(S2))
+        nb = lib().nc_unet_deconv_fwd_ws_bytes(N, S0, S1, S2)
         if nb == 0:
             raise ValueError('Unet_deconv: every edge must be a positive multiple of 4, got %s '
                              '(MaxPool3d floors, torch.cat at networks.py:526,531 would fail)' % ((S0, S1, S2),))
         ws = ops.workspace(nb, x.device, 'unet')
         y = torch.empty_like(x)
-        check(lib().nc_unet_deconv_fwd(P(self._packed_params().data_ptr()), P(x.data_ptr()), P(y.data_ptr()), I(N),
-                                       I(S0), I(S1), I(S2), P(ws.data_ptr()), Z(ws.numel()),
+        check(lib().nc_unet_deconv_fwd(P(self._packed_params().data_ptr()), P(x.data_ptr()), P(y.data_ptr()), N,
+                                       S0, S1, S2, P(ws.data_ptr()), ws.numel(),
                                        P(torch.cuda.current_stream().cuda_stream)), 'nc_unet_deconv_fwd')
         return y
 

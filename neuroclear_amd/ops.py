@@ -9,7 +9,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import F, I, L_, P, Z, check, lib
+from ._lib import I, P, check, lib
 
 _ws_cache = {}
 
@@ -22,7 +22,7 @@ prof = None
 def prof_start(min_flop=0.0):
     global prof
     prof = []
-    lib().nc_prof_begin(ctypes.c_double(min_flop))
+    lib().nc_prof_begin(min_flop)
 
 
 _PATH = {0: 'direct', 1: 'mfma', 2: 'gemm', 3: 'flat', 4: 'taps', 5: 'k1', 6: 'to1', 7: 'img', 8: 'pg1', 9: 'split', 10: 'split2d', 11: 'split',
@@ -36,7 +36,7 @@ def prof_stop():
     L = lib()
     cap = 1 << 16
     cls, flop, ms, ab = (ctypes.c_int * cap)(), (ctypes.c_double * cap)(), (ctypes.c_float * cap)(), (ctypes.c_double * cap)()
-    n = min(L.nc_prof_end2(I(cap), cls, flop, ms, ab), cap)
+    n = min(L.nc_prof_end2(cap, cls, flop, ms, ab), cap)
     stats = {}
     for i in range(n):
         c = cls[i]
@@ -52,8 +52,8 @@ def prof_stop():
     return stats, whole
 
 
-def _prof_begin(flop=None):
-    if prof is None or flop is not None:  # per-convolution brackets live in the library
+def _prof_begin():
+    if prof is None:
         return None
     e = torch.cuda.Event(enable_timing=True)
     e.record()
@@ -65,16 +65,6 @@ def _prof_end(e0, tag, flop):
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()
         prof.append((tag, flop, e0, e1))
-
-
-def _conv_tag(op, C, K, k3, stride, pad, out_vox):
-    mf = lib().nc_conv_wgrad_path if op == 'wgrad' else lib().nc_conv_fwd_path
-    if op == 'dgrad':
-        path = lib().nc_conv_fwd_path(I(K), I(C), I(k3[0]), I(k3[1]), I(k3[2]), I(stride), I(pad))
-    else:
-        path = mf(I(C), I(K), I(k3[0]), I(k3[1]), I(k3[2]), I(stride), I(pad))
-    tag = '%s_%s_k%d' % (op, {1: 'mfma', 2: 'gemm', 3: 'flat', 4: 'taps', 9: 'split'}.get(path, 'direct'), k3[1])
-    return tag, 2.0 * C * K * k3[0] * k3[1] * k3[2] * out_vox
 
 
 def _stream():
@@ -136,12 +126,6 @@ def _conv_out_shape(xs, ws, stride, pad):
     return (xs[0], ws[0]) + tuple((xs[2 + i] + 2 * pad - ws[2 + i]) // stride + 1 for i in range(nsp))
 
 
-def _conv_ws(dims, K, k3, stride, pad, device, tag='ws'):
-    N, C, D, H, W = dims
-    nb = lib().nc_conv_ws_bytes(I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]), I(k3[1]), I(k3[2]), I(stride), I(pad))
-    return workspace(nb, device, tag)
-
-
 # Backward runs the weight gradient of a layer on a side stream, concurrently with the data gradient of the same layer
 # (they are independent given dy): the two kernels' workgroups interleave on the 256 CUs, which fills the idle tail
 # each of them leaves when its tile count is not a multiple of the CU count (e.g. 1296 tiles = 5.06 rounds at 108^3).
@@ -169,7 +153,7 @@ def set_conv_split(on):
     """fp32 3^3 / 5^3 convolutions as six bf16 MFMA products of an exact three-term operand split (csrc/conv_split.hip; the
     library default) or, with on=False, on the fp32 MFMA kernels.  Returns the previous setting."""
     prev = bool(lib().nc_get_conv_split())
-    lib().nc_set_conv_split(I(1 if on else 0))
+    lib().nc_set_conv_split(1 if on else 0)
     return prev
 
 
@@ -190,9 +174,7 @@ def _lp(what, dims, K, k3, stride, pad):
     key = (what, dims, K, k3, stride, pad)
     ok = _lp_cache.get(key)
     if ok is None:
-        N, C, D, H, W = dims
-        ok = _lp_cache[key] = bool(lib().nc_conv_lp_supported(I(what), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]),
-                                                              I(k3[1]), I(k3[2]), I(stride), I(pad)))
+        ok = _lp_cache[key] = bool(lib().nc_conv_lp_supported(what, *dims, K, *k3, stride, pad))
     if not ok:
         return 0
     # 'fp16': forward operands in fp16 (11-bit significand); backward operands (dy, and w / x next to it) in bf16 --
@@ -211,16 +193,19 @@ def to_c8(x, dt):
     S = x.numel() // (N * C)
     out = torch.empty(N * C * S * 2, dtype=torch.uint8, device=x.device)
     e0 = _prof_begin()
-    check(lib().nc_to_c8(_ptr(x), _ptr(out), I(N), I(C), L_(S), I(dt), _stream()), 'nc_to_c8')
-    if e0 is not None:
-        _prof_end(e0, 'to_c8', 0.0)
+    check(lib().nc_to_c8(_ptr(x), _ptr(out), N, C, S, dt, _stream()), 'nc_to_c8')
+    _prof_end(e0, 'to_c8', 0.0)
     return out
 
 
-def _lp_ws(dims, K, k3, stride, pad, device, tag='ws_lp'):
-    N, C, D, H, W = dims
-    nb = lib().nc_conv_lp_ws_bytes(I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]), I(k3[1]), I(k3[2]), I(stride), I(pad))
-    return workspace(nb, device, tag)
+def _conv_launch(op, dt, tensors, dims, K, k3, stride, pad, device, ws_tag='ws'):
+    """One convolution launch: nc_conv_<op> on the fp32 kernels, or nc_conv_<op>_lp with the 16-bit dtype code dt (_lp), on the
+    workspace of that path.  The profiler brackets the launch inside the library (nc_prof_begin), not here."""
+    name = 'nc_conv_' + op + ('_lp' if dt else '')
+    ws_bytes = lib().nc_conv_lp_ws_bytes if dt else lib().nc_conv_ws_bytes
+    ws = workspace(ws_bytes(*dims, K, *k3, stride, pad), device, ws_tag + '_lp' if dt else ws_tag)
+    check(getattr(lib(), name)(*map(_ptr, tensors), *dims, K, *k3, stride, pad, *((dt,) if dt else ()), _ptr(ws), ws.numel(),
+                               _stream()), name)
 
 
 def conv_fwd_raw(x, w, b, stride, pad, xh=None):
@@ -228,28 +213,13 @@ def conv_fwd_raw(x, w, b, stride, pad, xh=None):
     _chk(x, w, b)
     _f32(x, w, b)
     dims = _dims5(x.shape)
-    N, C, D, H, W = dims
     k3 = _kdims(w.shape)
     K = w.shape[0]
-    if w.shape[1] != C:
-        raise _lib.NcError('conv: weight expects %d input channels, got %d' % (w.shape[1], C))
+    if w.shape[1] != dims[1]:
+        raise _lib.NcError('conv: weight expects %d input channels, got %d' % (w.shape[1], dims[1]))
     y = torch.empty(_conv_out_shape(x.shape, w.shape, stride, pad), dtype=torch.float32, device=x.device)
     dt = _lp(0, dims, K, k3, stride, pad)
-    if dt:
-        ws = _lp_ws(dims, K, k3, stride, pad, x.device)
-        e0 = _prof_begin(2.0 * C * K * k3[0] * k3[1] * k3[2] * (y.numel() // K))
-        check(lib().nc_conv_fwd_lp(_ptr(x), _ptr(xh), _ptr(w), _ptr(b), _ptr(y), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]),
-                                   I(k3[1]), I(k3[2]), I(stride), I(pad), I(dt), _ptr(ws), Z(ws.numel()), _stream()),
-              'nc_conv_fwd_lp')
-        if e0 is not None:
-            _prof_end(e0, 'fwd_lp_k%d' % k3[1], 2.0 * C * K * k3[0] * k3[1] * k3[2] * (y.numel() // K))
-        return y
-    ws = _conv_ws(dims, K, k3, stride, pad, x.device)
-    e0 = _prof_begin(2.0 * C * K * k3[0] * k3[1] * k3[2] * (y.numel() // K))
-    check(lib().nc_conv_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]),
-                            I(k3[1]), I(k3[2]), I(stride), I(pad), _ptr(ws), Z(ws.numel()), _stream()), 'nc_conv_fwd')
-    if e0 is not None:
-        _prof_end(e0, *_conv_tag('fwd', C, K, k3, stride, pad, y.numel() // K))
+    _conv_launch('fwd', dt, (x, xh, w, b, y) if dt else (x, w, b, y), dims, K, k3, stride, pad, x.device)
     return y
 
 
@@ -258,25 +228,10 @@ def conv_dgrad_raw(dy, w, x_shape, stride, pad, dyh=None):
     _f32(dy, w)
     dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
     dims = _dims5(x_shape)
-    N, C, D, H, W = dims
     k3 = _kdims(w.shape)
     K = w.shape[0]
     dt = _lp(1, dims, K, k3, stride, pad)
-    if dt:
-        ws = _lp_ws(dims, K, k3, stride, pad, dy.device)
-        e0 = _prof_begin(2.0 * C * K * k3[0] * k3[1] * k3[2] * (dy.numel() // K))
-        check(lib().nc_conv_dgrad_lp(_ptr(dy), _ptr(dyh), _ptr(w), _ptr(dx), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]),
-                                     I(k3[1]), I(k3[2]), I(stride), I(pad), I(dt), _ptr(ws), Z(ws.numel()), _stream()),
-              'nc_conv_dgrad_lp')
-        if e0 is not None:
-            _prof_end(e0, 'dgrad_lp_k%d' % k3[1], 2.0 * C * K * k3[0] * k3[1] * k3[2] * (dy.numel() // K))
-        return dx
-    ws = _conv_ws(dims, K, k3, stride, pad, dy.device)
-    e0 = _prof_begin(2.0 * C * K * k3[0] * k3[1] * k3[2] * (dy.numel() // K))
-    check(lib().nc_conv_dgrad(_ptr(dy), _ptr(w), _ptr(dx), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]), I(k3[1]),
-                              I(k3[2]), I(stride), I(pad), _ptr(ws), Z(ws.numel()), _stream()), 'nc_conv_dgrad')
-    if e0 is not None:
-        _prof_end(e0, *_conv_tag('dgrad', C, K, k3, stride, pad, dy.numel() // K))
+    _conv_launch('dgrad', dt, (dy, dyh, w, dx) if dt else (dy, w, dx), dims, K, k3, stride, pad, dy.device)
     return dx
 
 
@@ -285,7 +240,6 @@ def conv_wgrad_raw(x, dy, w_shape, stride, pad, want_bias, ws_tag='ws', xh=None,
     _chk(x, dy)
     _f32(x, dy)
     dims = _dims5(x.shape if x is not None else x_shape)
-    N, C, D, H, W = dims
     K = w_shape[0]
     k3 = _kdims(w_shape)
     dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=dy.device)
@@ -293,22 +247,7 @@ def conv_wgrad_raw(x, dy, w_shape, stride, pad, want_bias, ws_tag='ws', xh=None,
     dt = _lp(2, dims, K, k3, stride, pad)
     if x is None and not dt:
         raise _lib.NcError('conv_wgrad: the fp32 x is needed for the fp32 kernels')
-    if dt:
-        ws = _lp_ws(dims, K, k3, stride, pad, dy.device, ws_tag + '_lp')
-        e0 = _prof_begin(2.0 * C * K * k3[0] * k3[1] * k3[2] * (dy.numel() // K))
-        check(lib().nc_conv_wgrad_lp(_ptr(x), _ptr(xh), _ptr(dy), _ptr(dyh), _ptr(dw), _ptr(db), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]),
-                                     I(k3[1]), I(k3[2]), I(stride), I(pad), I(dt), _ptr(ws), Z(ws.numel()), _stream()),
-              'nc_conv_wgrad_lp')
-        if e0 is not None:
-            _prof_end(e0, 'wgrad_lp_k%d' % k3[1], 2.0 * C * K * k3[0] * k3[1] * k3[2] * (dy.numel() // K))
-        return dw, db
-    ws = _conv_ws(dims, K, k3, stride, pad, x.device, ws_tag)
-    e0 = _prof_begin(2.0 * C * K * k3[0] * k3[1] * k3[2] * (dy.numel() // K))
-    check(lib().nc_conv_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), I(N), I(C), I(D), I(H), I(W), I(K), I(k3[0]),
-                              I(k3[1]), I(k3[2]), I(stride), I(pad), _ptr(ws), Z(ws.numel()), _stream()),
-          'nc_conv_wgrad')
-    if e0 is not None:
-        _prof_end(e0, *_conv_tag('wgrad', C, K, k3, stride, pad, dy.numel() // K))
+    _conv_launch('wgrad', dt, (x, xh, dy, dyh, dw, db) if dt else (x, dy, dw, db), dims, K, k3, stride, pad, dy.device, ws_tag)
     return dw, db
 
 
@@ -440,7 +379,7 @@ def _lk_ok(x, w):
 
 def _lk_call(fn, a, b, out, k, ws, what):
     N, _, D, H, W = out.shape
-    check(fn(_ptr(a), _ptr(b), _ptr(out), I(N), I(D), I(H), I(W), I(k), _ptr(ws), Z(0 if ws is None else ws.numel()), _stream()), what)
+    check(fn(_ptr(a), _ptr(b), _ptr(out), N, D, H, W, k, _ptr(ws), (0 if ws is None else ws.numel()), _stream()), what)
     return out
 
 
@@ -465,9 +404,9 @@ class _LinearKernel(torch.autograd.Function):
             dx = _lk_call(lib().nc_lk_dgrad, dy, w, torch.empty_like(dy), k, None, 'nc_lk_dgrad')
         if ctx.needs_input_grad[1]:
             N, _, D, H, W = x.shape
-            ws = workspace(lib().nc_lk_ws_bytes(I(N), I(D), I(H), I(W), I(k)), x.device, 'ws_lk')
+            ws = workspace(lib().nc_lk_ws_bytes(N, D, H, W, k), x.device, 'ws_lk')
             dw = torch.empty_like(w)
-            check(lib().nc_lk_wgrad(_ptr(x), _ptr(dy), _ptr(dw), I(N), I(D), I(H), I(W), I(k), _ptr(ws), Z(ws.numel()), _stream()),
+            check(lib().nc_lk_wgrad(_ptr(x), _ptr(dy), _ptr(dw), N, D, H, W, k, _ptr(ws), ws.numel(), _stream()),
                   'nc_lk_wgrad')
         return dx, dw
 
@@ -491,14 +430,14 @@ class _ConvT(torch.autograd.Function):
         N, C, D, H, W = x.shape
         K = w.shape[1]
         y = torch.empty((N, K, 2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-        if lib().nc_convT_k2s2_split_active(I(1), I(C), I(D), I(H), I(W), I(K)):
+        if lib().nc_convT_k2s2_split_active(1, C, D, H, W, K):
             # the split-operand kernel of csrc/convt_s3.hip, sample by sample: exactly what the whole-network calls do
-            ws = workspace(lib().nc_convT_k2s2_split_ws_bytes(I(1), I(C), I(D), I(H), I(W), I(K)), x.device, 'ws_convT_split')
+            ws = workspace(lib().nc_convT_k2s2_split_ws_bytes(1, C, D, H, W, K), x.device, 'ws_convT_split')
             for n in range(N):
-                check(lib().nc_convT_k2s2_fwd_split(_ptr(x[n]), None, _ptr(w), _ptr(b), _ptr(y[n]), None, I(0), I(0), I(1), I(C), I(D), I(H), I(W),
-                                                    I(K), _ptr(ws), Z(ws.numel()), _stream()), 'nc_convT_k2s2_fwd_split')
+                check(lib().nc_convT_k2s2_fwd_split(_ptr(x[n]), None, _ptr(w), _ptr(b), _ptr(y[n]), None, 0, 0, 1, C, D, H, W,
+                                                    K, _ptr(ws), ws.numel(), _stream()), 'nc_convT_k2s2_fwd_split')
         else:
-            check(lib().nc_convT_k2s2_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), I(N), I(C), I(D), I(H), I(W), I(K),
+            check(lib().nc_convT_k2s2_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), N, C, D, H, W, K,
                                           _stream()), 'nc_convT_k2s2_fwd')
         ctx.save_for_backward(x, w)
         ctx.has_b = b is not None
@@ -513,16 +452,16 @@ class _ConvT(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            nb = lib().nc_convT_ws_bytes(I(N), I(C), I(D), I(H), I(W), I(K))
+            nb = lib().nc_convT_ws_bytes(N, C, D, H, W, K)
             ws = workspace(nb, x.device, 'ws_convT')
-            check(lib().nc_convT_k2s2_dgrad(_ptr(dy), _ptr(w), _ptr(dx), I(N), I(C), I(D), I(H), I(W), I(K), _ptr(ws),
-                                            Z(ws.numel()), _stream()), 'nc_convT_k2s2_dgrad')
+            check(lib().nc_convT_k2s2_dgrad(_ptr(dy), _ptr(w), _ptr(dx), N, C, D, H, W, K, _ptr(ws),
+                                            ws.numel(), _stream()), 'nc_convT_k2s2_dgrad')
         if ctx.needs_input_grad[1]:
             dw = torch.empty_like(w)
             db = torch.empty(K, dtype=torch.float32, device=x.device) if ctx.has_b else None
-            ws = workspace(lib().nc_convT_ws_bytes(I(N), I(C), I(D), I(H), I(W), I(K)), x.device)
-            check(lib().nc_convT_k2s2_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), I(N), I(C), I(D), I(H), I(W), I(K),
-                                            _ptr(ws), Z(ws.numel()), _stream()), 'nc_convT_k2s2_wgrad')
+            ws = workspace(lib().nc_convT_ws_bytes(N, C, D, H, W, K), x.device)
+            check(lib().nc_convT_k2s2_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, C, D, H, W, K,
+                                            _ptr(ws), ws.numel(), _stream()), 'nc_convT_k2s2_wgrad')
         return dx, dw, db
 
 
@@ -538,8 +477,8 @@ def instnorm_stats(x, eps=1e-5):
     S = x.numel() // NC
     mean = torch.empty(NC, dtype=torch.float32, device=x.device)
     rstd = torch.empty(NC, dtype=torch.float32, device=x.device)
-    ws = workspace(lib().nc_instnorm_ws_bytes(I(NC), L_(S)), x.device, 'in')
-    check(lib().nc_instnorm_stats(_ptr(x), I(NC), L_(S), F(eps), _ptr(mean), _ptr(rstd), _ptr(ws), Z(ws.numel()),
+    ws = workspace(lib().nc_instnorm_ws_bytes(NC, S), x.device, 'in')
+    check(lib().nc_instnorm_stats(_ptr(x), NC, S, eps, _ptr(mean), _ptr(rstd), _ptr(ws), ws.numel(),
                                   _stream()), 'nc_instnorm_stats')
     return mean, rstd
 
@@ -555,8 +494,8 @@ class _InstNormAct(torch.autograd.Function):
             NC = mean.numel()
             S = x.numel() // NC
             yh = torch.empty(x.numel() * 2, dtype=torch.uint8, device=x.device)
-            check(lib().nc_instnorm_act_fwd_c8(_ptr(x), _ptr(mean), _ptr(rstd), F(slope), _ptr(y), _ptr(yh), I(x.shape[0]),
-                                               I(x.shape[1]), L_(S), I(nxt.want_xh), _stream()), 'nc_instnorm_act_fwd_c8')
+            check(lib().nc_instnorm_act_fwd_c8(_ptr(x), _ptr(mean), _ptr(rstd), slope, _ptr(y), _ptr(yh), x.shape[0],
+                                               x.shape[1], S, nxt.want_xh, _stream()), 'nc_instnorm_act_fwd_c8')
             nxt.xh, nxt.xh_dt = yh, nxt.want_xh
         else:
             _chk(x)
@@ -565,9 +504,9 @@ class _InstNormAct(torch.autograd.Function):
             S = x.numel() // NC
             mean = torch.empty(NC, dtype=torch.float32, device=x.device)
             rstd = torch.empty(NC, dtype=torch.float32, device=x.device)
-            ws = workspace(lib().nc_instnorm_ws_bytes(I(NC), L_(S)), x.device, 'in')
-            check(lib().nc_instnorm_fwd(_ptr(x), F(eps), F(slope), _ptr(mean), _ptr(rstd), _ptr(y), I(NC), L_(S), _ptr(ws),
-                                        Z(ws.numel()), _stream()), 'nc_instnorm_fwd')
+            ws = workspace(lib().nc_instnorm_ws_bytes(NC, S), x.device, 'in')
+            check(lib().nc_instnorm_fwd(_ptr(x), eps, slope, _ptr(mean), _ptr(rstd), _ptr(y), NC, S, _ptr(ws),
+                                        ws.numel(), _stream()), 'nc_instnorm_fwd')
         ctx.save_for_backward(x, mean, rstd)
         ctx.slope = slope
         return y
@@ -584,24 +523,24 @@ class _InstNormAct(torch.autograd.Function):
             N, C = x.shape[0], x.shape[1]
             db = torch.empty(C, dtype=torch.float32, device=x.device) if link.want else None
             dxh = torch.empty(x.numel() * 2, dtype=torch.uint8, device=x.device)
-            ws = workspace(lib().nc_instnorm_bwd_dbias_ws_bytes(I(NC), L_(S)), x.device, 'in')
-            check(lib().nc_instnorm_act_bwd_c8(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), F(ctx.slope), _ptr(dx), _ptr(dxh),
-                                               _ptr(db), I(N), I(C), L_(S), I(link.want_dyh), _ptr(ws), Z(ws.numel()),
+            ws = workspace(lib().nc_instnorm_bwd_dbias_ws_bytes(NC, S), x.device, 'in')
+            check(lib().nc_instnorm_act_bwd_c8(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), ctx.slope, _ptr(dx), _ptr(dxh),
+                                               _ptr(db), N, C, S, link.want_dyh, _ptr(ws), ws.numel(),
                                                _stream()), 'nc_instnorm_act_bwd_c8')
             link.dyh, link.dyh_dt, link.dbias = dxh, link.want_dyh, db
             return dx, None, None, None, None
         if link is not None and link.want:
             N, C = x.shape[0], x.shape[1]
             db = torch.empty(C, dtype=torch.float32, device=x.device)
-            ws = workspace(lib().nc_instnorm_bwd_dbias_ws_bytes(I(NC), L_(S)), x.device, 'in')
-            check(lib().nc_instnorm_act_bwd_dbias(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), F(ctx.slope), _ptr(dx), _ptr(db),
-                                                  I(N), I(C), L_(S), _ptr(ws), Z(ws.numel()), _stream()),
+            ws = workspace(lib().nc_instnorm_bwd_dbias_ws_bytes(NC, S), x.device, 'in')
+            check(lib().nc_instnorm_act_bwd_dbias(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), ctx.slope, _ptr(dx), _ptr(db),
+                                                  N, C, S, _ptr(ws), ws.numel(), _stream()),
                   'nc_instnorm_act_bwd_dbias')
             link.dbias = db
             return dx, None, None, None, None
-        ws = workspace(lib().nc_instnorm_ws_bytes(I(NC), L_(S)), x.device, 'in')
-        check(lib().nc_instnorm_act_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), F(ctx.slope), _ptr(dx), I(NC),
-                                        L_(S), _ptr(ws), Z(ws.numel()), _stream()), 'nc_instnorm_act_bwd')
+        ws = workspace(lib().nc_instnorm_ws_bytes(NC, S), x.device, 'in')
+        check(lib().nc_instnorm_act_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), ctx.slope, _ptr(dx), NC,
+                                        S, _ptr(ws), ws.numel(), _stream()), 'nc_instnorm_act_bwd')
         return dx, None, None, None, None
 
 
@@ -622,11 +561,11 @@ class _BatchNormAct(torch.autograd.Function):
         L = lib()
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         rstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_instnorm_ws_bytes(I(N * C), L_(S)), x.device, 'bn')
-        check(L.nc_batchnorm_stats(_ptr(x), I(N), I(C), L_(S), F(eps), F(momentum), I(1 if training else 0), _ptr(mean), _ptr(rstd),
-                                   _ptr(running_mean), _ptr(running_var), _ptr(ws), Z(ws.numel()), _stream()), 'nc_batchnorm_stats')
+        ws = workspace(L.nc_instnorm_ws_bytes(N * C, S), x.device, 'bn')
+        check(L.nc_batchnorm_stats(_ptr(x), N, C, S, eps, momentum, 1 if training else 0, _ptr(mean), _ptr(rstd),
+                                   _ptr(running_mean), _ptr(running_var), _ptr(ws), ws.numel(), _stream()), 'nc_batchnorm_stats')
         y = torch.empty_like(x)
-        check(L.nc_batchnorm_act_fwd(_ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), F(slope), _ptr(y), I(N), I(C), L_(S), _stream()),
+        check(L.nc_batchnorm_act_fwd(_ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), slope, _ptr(y), N, C, S, _stream()),
               'nc_batchnorm_act_fwd')
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.cfg = (bool(training), float(slope))
@@ -643,9 +582,9 @@ class _BatchNormAct(torch.autograd.Function):
         dx = torch.empty_like(x)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         coef = torch.empty(2 * C, dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_instnorm_ws_bytes(I(N * C), L_(S)), x.device, 'bn')
-        check(L.nc_batchnorm_act_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), F(slope), I(1 if training else 0),
-                                     _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(coef), I(N), I(C), L_(S), _ptr(ws), Z(ws.numel()), _stream()),
+        ws = workspace(L.nc_instnorm_ws_bytes(N * C, S), x.device, 'bn')
+        check(L.nc_batchnorm_act_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), slope, 1 if training else 0,
+                                     _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(coef), N, C, S, _ptr(ws), ws.numel(), _stream()),
               'nc_batchnorm_act_bwd')
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
@@ -663,7 +602,7 @@ class _LeakyReLU(torch.autograd.Function):
         _chk(x)
         _f32(x)
         y = torch.empty_like(x)
-        check(lib().nc_leaky_relu_fwd(_ptr(x), F(slope), _ptr(y), L_(x.numel()), _stream()), 'nc_leaky_relu_fwd')
+        check(lib().nc_leaky_relu_fwd(_ptr(x), slope, _ptr(y), x.numel(), _stream()), 'nc_leaky_relu_fwd')
         ctx.save_for_backward(x)
         ctx.slope = slope
         return y
@@ -673,7 +612,7 @@ class _LeakyReLU(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        check(lib().nc_leaky_relu_bwd(_ptr(dy), _ptr(x), F(ctx.slope), _ptr(dx), L_(x.numel()), _stream()),
+        check(lib().nc_leaky_relu_bwd(_ptr(dy), _ptr(x), ctx.slope, _ptr(dx), x.numel(), _stream()),
               'nc_leaky_relu_bwd')
         return dx, None
 
@@ -689,7 +628,7 @@ class _Sigmoid(torch.autograd.Function):
         _chk(x)
         _f32(x)
         y = torch.empty_like(x)
-        check(lib().nc_sigmoid_fwd(_ptr(x), _ptr(y), L_(x.numel()), _stream()), 'nc_sigmoid_fwd')
+        check(lib().nc_sigmoid_fwd(_ptr(x), _ptr(y), x.numel(), _stream()), 'nc_sigmoid_fwd')
         ctx.save_for_backward(y)
         return y
 
@@ -698,7 +637,7 @@ class _Sigmoid(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(y)
-        check(lib().nc_sigmoid_bwd(_ptr(dy), _ptr(y), _ptr(dx), L_(y.numel()), _stream()), 'nc_sigmoid_bwd')
+        check(lib().nc_sigmoid_bwd(_ptr(dy), _ptr(y), _ptr(dx), y.numel(), _stream()), 'nc_sigmoid_bwd')
         return dx
 
 
@@ -716,7 +655,7 @@ class _MaxPool2(torch.autograd.Function):
         wd = 2 if D > 1 else 1
         oshape = (N, C, D // wd, H // 2, W // 2) if x.dim() == 5 else (N, C, H // 2, W // 2)
         y = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        check(lib().nc_maxpool2_fwd(_ptr(x), _ptr(y), I(N * C), I(D), I(H), I(W), _stream()), 'nc_maxpool2_fwd')
+        check(lib().nc_maxpool2_fwd(_ptr(x), _ptr(y), N * C, D, H, W, _stream()), 'nc_maxpool2_fwd')
         ctx.save_for_backward(x)
         return y
 
@@ -726,7 +665,7 @@ class _MaxPool2(torch.autograd.Function):
         dy = dy.contiguous()
         N, C, D, H, W = _dims5(x.shape)
         dx = torch.empty_like(x)
-        check(lib().nc_maxpool2_bwd(_ptr(dy), _ptr(x), _ptr(dx), I(N * C), I(D), I(H), I(W), _stream()),
+        check(lib().nc_maxpool2_bwd(_ptr(dy), _ptr(x), _ptr(dx), N * C, D, H, W, _stream()),
               'nc_maxpool2_bwd')
         return dx
 
@@ -747,7 +686,7 @@ class _Slice(torch.autograd.Function):
         _f32(vol)
         N, C, D, H, W = vol.shape
         out = torch.empty(_PLANE[axis](N, C, D, H, W), dtype=torch.float32, device=vol.device)
-        check(lib().nc_slice_fwd(_ptr(vol), _ptr(out), I(N * C), I(D), I(H), I(W), I(axis), I(index), _stream()),
+        check(lib().nc_slice_fwd(_ptr(vol), _ptr(out), N * C, D, H, W, axis, index, _stream()),
               'nc_slice_fwd')
         ctx.cfg = (tuple(vol.shape), axis, index)
         return out
@@ -758,7 +697,7 @@ class _Slice(torch.autograd.Function):
         dout = dout.contiguous()
         N, C, D, H, W = shape
         dvol = torch.empty(shape, dtype=torch.float32, device=dout.device)
-        check(lib().nc_slice_bwd(_ptr(dout), _ptr(dvol), I(N * C), I(D), I(H), I(W), I(axis), I(index), _stream()),
+        check(lib().nc_slice_bwd(_ptr(dout), _ptr(dvol), N * C, D, H, W, axis, index, _stream()),
               'nc_slice_bwd')
         return dvol, None, None
 
@@ -778,8 +717,8 @@ class _Mip(torch.autograd.Function):
         oshape = _PLANE[axis](N, C, D, H, W)
         out = torch.empty(oshape, dtype=torch.float32, device=vol.device)
         arg = torch.empty(oshape, dtype=torch.int32, device=vol.device)
-        check(lib().nc_mip_fwd(_ptr(vol), _ptr(out), _ptr(arg), I(N * C), I(D), I(H), I(W), I(axis), I(start),
-                               I(depth), _stream()), 'nc_mip_fwd')
+        check(lib().nc_mip_fwd(_ptr(vol), _ptr(out), _ptr(arg), N * C, D, H, W, axis, start,
+                               depth, _stream()), 'nc_mip_fwd')
         ctx.save_for_backward(arg)
         ctx.cfg = (tuple(vol.shape), axis)
         return out
@@ -791,7 +730,7 @@ class _Mip(torch.autograd.Function):
         dout = dout.contiguous()
         N, C, D, H, W = shape
         dvol = torch.empty(shape, dtype=torch.float32, device=dout.device)
-        check(lib().nc_mip_bwd(_ptr(dout), _ptr(arg), _ptr(dvol), I(N * C), I(D), I(H), I(W), I(axis), _stream()),
+        check(lib().nc_mip_bwd(_ptr(dout), _ptr(arg), _ptr(dvol), N * C, D, H, W, axis, _stream()),
               'nc_mip_bwd')
         return dvol, None, None, None
 
@@ -811,7 +750,7 @@ class _AllSlices(torch.autograd.Function):
         L = (D, H, W)[axis]
         pn, pc, pa, pb = _PLANE[axis](N, C, D, H, W)
         out = torch.empty((N * L, C, pa, pb), dtype=torch.float32, device=vol.device)
-        check(lib().nc_volume_slices(_ptr(vol), _ptr(out), I(N), I(C), I(D), I(H), I(W), I(axis), I(0), _stream()),
+        check(lib().nc_volume_slices(_ptr(vol), _ptr(out), N, C, D, H, W, axis, 0, _stream()),
               'nc_volume_slices')
         ctx.cfg = (tuple(vol.shape), axis)
         return out
@@ -822,7 +761,7 @@ class _AllSlices(torch.autograd.Function):
         dout = dout.contiguous()
         N, C, D, H, W = shape
         dvol = torch.empty(shape, dtype=torch.float32, device=dout.device)
-        check(lib().nc_volume_slices(_ptr(dout), _ptr(dvol), I(N), I(C), I(D), I(H), I(W), I(axis), I(1), _stream()),
+        check(lib().nc_volume_slices(_ptr(dout), _ptr(dvol), N, C, D, H, W, axis, 1, _stream()),
               'nc_volume_slices')
         return dvol, None
 
@@ -840,8 +779,8 @@ class _MseConst(torch.autograd.Function):
         _chk(pred)
         _f32(pred)
         out = torch.empty((), dtype=torch.float32, device=pred.device)
-        ws = workspace(lib().nc_loss_ws_bytes(L_(pred.numel())), pred.device, 'loss')
-        check(lib().nc_mse_const_fwd(_ptr(pred), L_(pred.numel()), F(target), _ptr(out), _ptr(ws), Z(ws.numel()),
+        ws = workspace(lib().nc_loss_ws_bytes(pred.numel()), pred.device, 'loss')
+        check(lib().nc_mse_const_fwd(_ptr(pred), pred.numel(), target, _ptr(out), _ptr(ws), ws.numel(),
                                      _stream()), 'nc_mse_const_fwd')
         ctx.save_for_backward(pred)
         ctx.target = target
@@ -852,7 +791,7 @@ class _MseConst(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         g = g.contiguous()
         dp = torch.empty_like(pred)
-        check(lib().nc_mse_const_bwd(_ptr(pred), L_(pred.numel()), F(ctx.target), _ptr(g), _ptr(dp), _stream()),
+        check(lib().nc_mse_const_bwd(_ptr(pred), pred.numel(), ctx.target, _ptr(g), _ptr(dp), _stream()),
               'nc_mse_const_bwd')
         return dp, None
 
@@ -869,8 +808,8 @@ class _BceLogitsConst(torch.autograd.Function):
         _chk(pred)
         _f32(pred)
         out = torch.empty((), dtype=torch.float32, device=pred.device)
-        ws = workspace(lib().nc_loss_ws_bytes(L_(pred.numel())), pred.device, 'loss')
-        check(lib().nc_bce_logits_const_fwd(_ptr(pred), L_(pred.numel()), F(target), _ptr(out), _ptr(ws), Z(ws.numel()), _stream()),
+        ws = workspace(lib().nc_loss_ws_bytes(pred.numel()), pred.device, 'loss')
+        check(lib().nc_bce_logits_const_fwd(_ptr(pred), pred.numel(), target, _ptr(out), _ptr(ws), ws.numel(), _stream()),
               'nc_bce_logits_const_fwd')
         ctx.save_for_backward(pred)
         ctx.target = target
@@ -881,7 +820,7 @@ class _BceLogitsConst(torch.autograd.Function):
         (pred,) = ctx.saved_tensors
         g = g.contiguous()
         dp = torch.empty_like(pred)
-        check(lib().nc_bce_logits_const_bwd(_ptr(pred), L_(pred.numel()), F(ctx.target), _ptr(g), _ptr(dp), _stream()),
+        check(lib().nc_bce_logits_const_bwd(_ptr(pred), pred.numel(), ctx.target, _ptr(g), _ptr(dp), _stream()),
               'nc_bce_logits_const_bwd')
         return dp, None
 
@@ -898,8 +837,8 @@ class _Mean(torch.autograd.Function):
         _chk(pred)
         _f32(pred)
         out = torch.empty((), dtype=torch.float32, device=pred.device)
-        ws = workspace(lib().nc_loss_ws_bytes(L_(pred.numel())), pred.device, 'loss')
-        check(lib().nc_mean_fwd(_ptr(pred), L_(pred.numel()), _ptr(out), _ptr(ws), Z(ws.numel()), _stream()), 'nc_mean_fwd')
+        ws = workspace(lib().nc_loss_ws_bytes(pred.numel()), pred.device, 'loss')
+        check(lib().nc_mean_fwd(_ptr(pred), pred.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream()), 'nc_mean_fwd')
         ctx.shape = pred.shape
         return out
 
@@ -907,7 +846,7 @@ class _Mean(torch.autograd.Function):
     def backward(ctx, g):
         g = g.contiguous()
         dp = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
-        check(lib().nc_mean_bwd(L_(dp.numel()), _ptr(g), _ptr(dp), _stream()), 'nc_mean_bwd')
+        check(lib().nc_mean_bwd(dp.numel(), _ptr(g), _ptr(dp), _stream()), 'nc_mean_bwd')
         return dp
 
 
@@ -923,8 +862,8 @@ class _L1(torch.autograd.Function):
         _chk(a, b)
         _f32(a, b)
         out = torch.empty((), dtype=torch.float32, device=a.device)
-        ws = workspace(lib().nc_loss_ws_bytes(L_(a.numel())), a.device, 'loss')
-        check(lib().nc_l1_fwd(_ptr(a), _ptr(b), L_(a.numel()), _ptr(out), _ptr(ws), Z(ws.numel()), _stream()),
+        ws = workspace(lib().nc_loss_ws_bytes(a.numel()), a.device, 'loss')
+        check(lib().nc_l1_fwd(_ptr(a), _ptr(b), a.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream()),
               'nc_l1_fwd')
         ctx.save_for_backward(a, b)
         return out
@@ -934,7 +873,7 @@ class _L1(torch.autograd.Function):
         a, b = ctx.saved_tensors
         g = g.contiguous()
         da = torch.empty_like(a)
-        check(lib().nc_l1_bwd(_ptr(a), _ptr(b), L_(a.numel()), _ptr(g), _ptr(da), _stream()), 'nc_l1_bwd')
+        check(lib().nc_l1_bwd(_ptr(a), _ptr(b), a.numel(), _ptr(g), _ptr(da), _stream()), 'nc_l1_bwd')
         return da, None
 
 
@@ -947,12 +886,12 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
     """torch.optim.Adam.step over one flat buffer (apollo_model.py:131-136)."""
     _chk(p, g, m, v)
     _f32(p, g, m, v)
-    check(lib().nc_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), L_(p.numel()), F(lr), F(beta1), F(beta2), F(eps),
-                             I(step), _stream()), 'nc_adam_step')
+    check(lib().nc_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, beta1, beta2, eps,
+                             step, _stream()), 'nc_adam_step')
 
 
 def set_force_direct(on):
-    lib().nc_set_force_direct(I(1 if on else 0))
+    lib().nc_set_force_direct(1 if on else 0)
 
 
 # Generation counter per parameter storage: nc_adam_step (and checkpoint loads) write parameters through raw pointers,
@@ -1009,7 +948,7 @@ def _grad_destination(packed):
     return torch.empty_like(packed)
 
 
-# ---- whole-network PatchGAN (nc_patchgan_fwd / nc_patchgan_bwd): one C call per direction -------------------------
+# ---- whole-network calls: one C call per direction; the plumbing the Functions below share ---------------------------------
 def _pack_params(params):
     """The parameter tensors as ONE flat fp32 tensor in the given order: a zero-copy view when they already sit back
     to back in one storage (FlatAdam's flat buffer), otherwise a concatenated copy."""
@@ -1028,65 +967,114 @@ def _pack_params(params):
     return torch.cat([p.detach().reshape(-1) for p in params])
 
 
+def _grad_target(ctx, first):
+    """Where a whole-network backward writes its packed parameter gradients: the optimizer's flat gradient slice when EVERY parameter
+    wants a gradient (the kernels OVERWRITE the whole slice), a scratch tensor otherwise -- with all parameters frozen
+    (set_requires_grad(False)) nothing is handed on; with SOME frozen, autograd receives views of the scratch tensor for the others
+    (FlatAdam._collect copies them into the flat buffer) and the frozen ranges of the flat gradient keep the zeros of zero_grad, so
+    FlatAdam.step leaves those parameters where they are."""
+    if all(ctx.needs_input_grad[first:]):
+        return _grad_destination(ctx.packed)
+    return torch.empty_like(ctx.packed)
+
+
+def _param_grads(ctx, dpar, shapes, first):
+    grads = [None] * len(shapes)
+    off = 0
+    for i, shp in enumerate(shapes):
+        n = 1
+        for s in shp:
+            n *= s
+        if ctx.needs_input_grad[first + i]:
+            grads[i] = dpar[off:off + n].view(shp)
+        off += n
+    return grads
+
+
+def _net_forward(ctx, x, params, *, first, dims, ws_bytes, tag, n_params=None, count_msg=None):
+    """Forward side of a whole-network Function, x contiguous and `params` its inputs from position `first` on, in this order: dense fp32
+    CUDA tensors; dims() -- the Function's own shape checks, returning the scalar arguments of its C calls; the parameters as one packed
+    tensor of the n_params floats the library expects (NcError(count_msg) otherwise); and on ctx what the backward side needs -- among
+    it the workspace query ws_bytes(*dims) with its cache tag, which _net_ws answers in both directions.  -> packed, dims"""
+    _chk(x, *params)
+    _f32(x, *params)
+    dims = dims()
+    packed = _pack_params(params)
+    if n_params is not None and packed.numel() != n_params:
+        raise _lib.NcError(count_msg)
+    ctx.packed, ctx.packed_gen = packed, _param_generation(packed)
+    ctx.shapes = [tuple(p.shape) for p in params]
+    ctx.net = (first, ws_bytes, dims, tag)
+    return packed, dims
+
+
+def _net_ws(ctx, device):
+    _, ws_bytes, dims, tag = ctx.net
+    return workspace(ws_bytes(*dims), device, tag)
+
+
+def _net_out_shape(out_shape, dims, nd):
+    """[B, 1, (od,) oh, ow] from the library's nc_*_out_shape(*dims, &od, &oh, &ow); dims[0] is the batch."""
+    od, oh, ow = I(0), I(0), I(0)
+    check(out_shape(*dims, ctypes.byref(od), ctypes.byref(oh), ctypes.byref(ow)), out_shape.__name__)
+    return (dims[0], 1, oh.value, ow.value) if nd == 2 else (dims[0], 1, od.value, oh.value, ow.value)
+
+
+def _net_backward(ctx, device, stale_msg, always_dpar=False):
+    """Backward side: refuses (NcError(stale_msg)) when the parameters were written -- optimizer step, checkpoint load -- since the forward
+    packed them; -> (the tensor the packed parameter gradients go to, see _grad_target -- None when no parameter wants one, unless the
+    entry point needs it regardless -- and the workspace)."""
+    if _param_generation(ctx.packed) != ctx.packed_gen:
+        raise _lib.NcError(stale_msg)
+    first = ctx.net[0]
+    dpar = _grad_target(ctx, first) if always_dpar or any(ctx.needs_input_grad[first:]) else None
+    return dpar, _net_ws(ctx, device)
+
+
+def _net_grads(ctx, dx, dpar):
+    """What backward returns: dx, None for the non-tensor inputs in front of the parameters, then one view of dpar per parameter that wants
+    a gradient."""
+    first = ctx.net[0]
+    grads = _param_grads(ctx, dpar, ctx.shapes, first) if dpar is not None else [None] * len(ctx.shapes)
+    return (dx,) + (None,) * (first - 1) + tuple(grads)
+
+
+_PG_COUNT = 'fused PatchGAN: parameter count does not match (n_layers=%d, ndf=%d)'
+_UPDATED = ': the parameters were updated (optimizer step / checkpoint load) between this forward and its backward; the saved ' \
+           'activations no longer match them'
+
+
+def _pg_dims(x, cfg, B):
+    """(B, D, H, W, n_layers, ndf, nd) of the PatchGAN calls on planes or volumes shaped like x."""
+    if x.shape[1] != 1:
+        raise _lib.NcError('fused PatchGAN expects one input channel')
+    return (B,) + ((1, x.shape[2], x.shape[3]) if cfg[2] == 2 else tuple(x.shape[2:])) + cfg
+
+
 class _PatchGAN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, *params):
         n_layers, ndf, nd = cfg
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        if x.shape[1] != 1:
-            raise _lib.NcError('fused PatchGAN expects one input channel')
-        B = x.shape[0]
-        D, H, W = (1, x.shape[2], x.shape[3]) if nd == 2 else tuple(x.shape[2:])
         L = lib()
-        packed = _pack_params(params)
-        if packed.numel() != L.nc_patchgan_param_floats(I(n_layers), I(ndf), I(nd)):
-            raise _lib.NcError('fused PatchGAN: parameter count does not match (n_layers=%d, ndf=%d)' % (n_layers, ndf))
-        od, oh, ow = I(0), I(0), I(0)
-        import ctypes
-        check(L.nc_patchgan_out_shape(I(B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd), ctypes.byref(od),
-                                      ctypes.byref(oh), ctypes.byref(ow)), 'nc_patchgan_out_shape')
-        oshape = (B, 1, oh.value, ow.value) if nd == 2 else (B, 1, od.value, oh.value, ow.value)
-        y = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        saved = torch.empty(L.nc_patchgan_saved_floats(I(B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)),
-                            dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_patchgan_ws_bytes(I(B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)), x.device, 'patchgan')
-        check(L.nc_patchgan_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), I(B), I(D), I(H), I(W), I(n_layers), I(ndf),
-                                I(nd), _ptr(ws), Z(ws.numel()), _stream()), 'nc_patchgan_fwd')
+        packed, dims = _net_forward(ctx, x, params, first=2, dims=lambda: _pg_dims(x, cfg, x.shape[0]), ws_bytes=L.nc_patchgan_ws_bytes,
+                                    tag='patchgan', n_params=L.nc_patchgan_param_floats(*cfg), count_msg=_PG_COUNT % (n_layers, ndf))
+        y = torch.empty(_net_out_shape(L.nc_patchgan_out_shape, dims, nd), dtype=torch.float32, device=x.device)
+        saved = torch.empty(L.nc_patchgan_saved_floats(*dims), dtype=torch.float32, device=x.device)
+        ws = _net_ws(ctx, x.device)
+        check(L.nc_patchgan_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), *dims, _ptr(ws), ws.numel(), _stream()), 'nc_patchgan_fwd')
         ctx.save_for_backward(x, saved)
-        ctx.packed = packed
-        ctx.packed_gen = _param_generation(packed)
-        ctx.cfg = (cfg, (B, D, H, W), [tuple(p.shape) for p in params])
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, saved = ctx.saved_tensors
-        (n_layers, ndf, nd), (B, D, H, W), shapes = ctx.cfg
-        if _param_generation(ctx.packed) != ctx.packed_gen:
-            raise _lib.NcError('fused PatchGAN: the parameters were updated (optimizer step / checkpoint load) between '
-                               'this forward and its backward; the saved activations no longer match them')
         dy = dy.contiguous()
-        want_x = ctx.needs_input_grad[0]
-        want_p = any(ctx.needs_input_grad[2:])
-        dx = torch.empty_like(x) if want_x else None
-        dpar = _grad_target(ctx, 2) if want_p else None  # (x, cfg, *params): the parameters start at input 2
-        L = lib()
-        ws = workspace(L.nc_patchgan_ws_bytes(I(B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)), x.device, 'patchgan')
-        check(L.nc_patchgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), I(B), I(D), I(H),
-                                I(W), I(n_layers), I(ndf), I(nd), _ptr(ws), Z(ws.numel()), _stream()), 'nc_patchgan_bwd')
-        grads = [None] * len(shapes)
-        if want_p:
-            off = 0
-            for i, shp in enumerate(shapes):
-                n = 1
-                for s in shp:
-                    n *= s
-                if ctx.needs_input_grad[2 + i]:
-                    grads[i] = dpar[off:off + n].view(shp)
-                off += n
-        return (dx, None) + tuple(grads)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dpar, ws = _net_backward(ctx, x.device, 'fused PatchGAN' + _UPDATED)
+        check(lib().nc_patchgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *ctx.net[2], _ptr(ws),
+                                    ws.numel(), _stream()), 'nc_patchgan_bwd')
+        return _net_grads(ctx, dx, dpar)
 
 
 class PatchGANShare:
@@ -1110,65 +1098,45 @@ class PatchGANShare:
         self.saved = self.x = self.y = self.src = None
 
 
-def _pg_dims(x, nd):
-    return (1, x.shape[2], x.shape[3]) if nd == 2 else tuple(x.shape[2:])
-
-
 class _PatchGANFakeHalf(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg, share, *params):
         n_layers, ndf, nd = cfg
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        if x.shape[1] != 1:
-            raise _lib.NcError('fused PatchGAN expects one input channel')
         B = x.shape[0]
-        D, H, W = _pg_dims(x, nd)
         L = lib()
-        packed = _pack_params(params)
-        if packed.numel() != L.nc_patchgan_param_floats(I(n_layers), I(ndf), I(nd)):
-            raise _lib.NcError('fused PatchGAN: parameter count does not match (n_layers=%d, ndf=%d)' % (n_layers, ndf))
-        import ctypes
-        od, oh, ow = I(0), I(0), I(0)
-        check(L.nc_patchgan_out_shape(I(2 * B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd), ctypes.byref(od),
-                                      ctypes.byref(oh), ctypes.byref(ow)), 'nc_patchgan_out_shape')
-        oshape = (2 * B, 1, oh.value, ow.value) if nd == 2 else (2 * B, 1, od.value, oh.value, ow.value)
-        share.saved = torch.empty(L.nc_patchgan_saved_floats(I(2 * B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)),
-                                  dtype=torch.float32, device=x.device)
+        # (dims: of the whole (real, fake) batch)
+        packed, dims = _net_forward(ctx, x, params, first=3, dims=lambda: _pg_dims(x, cfg, 2 * B), ws_bytes=L.nc_patchgan_ws_bytes,
+                                    tag='patchgan', n_params=L.nc_patchgan_param_floats(*cfg), count_msg=_PG_COUNT % (n_layers, ndf))
+        oshape = _net_out_shape(L.nc_patchgan_out_shape, dims, nd)
+        share.saved = torch.empty(L.nc_patchgan_saved_floats(*dims), dtype=torch.float32, device=x.device)
         share.x = torch.empty((2 * B,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
         share.x[B:].copy_(x)
         share.y = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_patchgan_ws_bytes(I(2 * B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)), x.device, 'patchgan')
-        check(L.nc_patchgan_fwd_part(_ptr(packed), _ptr(share.x[B:]), _ptr(share.y[B:]), _ptr(share.saved), I(2 * B), I(B), I(B),
-                                     I(D), I(H), I(W), I(n_layers), I(ndf), I(nd), _ptr(ws), Z(ws.numel()), _stream()),
-              'nc_patchgan_fwd_part')
-        share.gen, share.packed_ptr, share.cfg, share.dims = _param_generation(packed), packed.data_ptr(), tuple(cfg), (B, D, H, W)
-        ctx.share, ctx.packed, ctx.cfg = share, packed, cfg
+        ws = _net_ws(ctx, x.device)
+        check(L.nc_patchgan_fwd_part(_ptr(packed), _ptr(share.x[B:]), _ptr(share.y[B:]), _ptr(share.saved), 2 * B, B, B, *dims[1:],
+                                     _ptr(ws), ws.numel(), _stream()), 'nc_patchgan_fwd_part')
+        share.gen, share.packed_ptr, share.cfg, share.dims = ctx.packed_gen, packed.data_ptr(), tuple(cfg), (B,) + dims[1:4]
         ctx.saved_ref = share.saved  # keeps the buffers alive for this backward even if the share is released first
         ctx.x_ref = share.x
         return share.y[B:].clone()
 
     @staticmethod
     def backward(ctx, dy):
-        n_layers, ndf, nd = ctx.cfg
-        share = ctx.share
-        B, D, H, W = share.dims
-        if _param_generation(ctx.packed) != share.gen:
-            raise _lib.NcError('fused PatchGAN: the parameters were updated between this forward and its backward')
+        stale = 'fused PatchGAN: the parameters were updated between this forward and its backward'
+        if _param_generation(ctx.packed) != ctx.packed_gen:
+            raise _lib.NcError(stale)
         if any(ctx.needs_input_grad[3:]):
             raise _lib.NcError('patchgan_fake_half: the discriminator must be frozen (generator loss)')
-        if not ctx.needs_input_grad[0]:
-            return (None,) * (3 + len(ctx.needs_input_grad[3:]))
+        dims = ctx.net[2]
+        B = dims[0] // 2
         dy = dy.contiguous()
         xs = ctx.x_ref[B:]
         dx = torch.empty_like(xs)
-        L = lib()
-        ws = workspace(L.nc_patchgan_ws_bytes(I(2 * B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)), dy.device, 'patchgan')
-        check(L.nc_patchgan_bwd_part(_ptr(ctx.packed), _ptr(xs), _ptr(ctx.saved_ref), _ptr(dy), _ptr(dx), I(2 * B), I(B), I(B),
-                                     I(D), I(H), I(W), I(n_layers), I(ndf), I(nd), _ptr(ws), Z(ws.numel()), _stream()),
-              'nc_patchgan_bwd_part')
-        return (dx, None, None) + (None,) * len(ctx.needs_input_grad[3:])
+        dpar, ws = _net_backward(ctx, dy.device, stale)
+        check(lib().nc_patchgan_bwd_part(_ptr(ctx.packed), _ptr(xs), _ptr(ctx.saved_ref), _ptr(dy), _ptr(dx), 2 * B, B, B, *dims[1:],
+                                         _ptr(ws), ws.numel(), _stream()), 'nc_patchgan_bwd_part')
+        return _net_grads(ctx, dx, dpar)
 
 
 class _PatchGANJoinReal(torch.autograd.Function):
@@ -1176,26 +1144,26 @@ class _PatchGANJoinReal(torch.autograd.Function):
     def forward(ctx, x, cfg, share, *params):
         n_layers, ndf, nd = cfg
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        B, D, H, W = share.dims
-        if tuple(x.shape) != tuple(share.x.shape[1:]) and tuple(x.shape) != (B,) + tuple(share.x.shape[1:]):
-            raise _lib.NcError('patchgan_join_real: the real planes do not have the shape of the cached fake planes')
-        packed = _pack_params(params)
-        if packed.data_ptr() != share.packed_ptr or _param_generation(packed) != share.gen:
+        B = share.dims[0]
+
+        def dims():
+            if tuple(x.shape) != tuple(share.x.shape[1:]) and tuple(x.shape) != (B,) + tuple(share.x.shape[1:]):
+                raise _lib.NcError('patchgan_join_real: the real planes do not have the shape of the cached fake planes')
+            return (2 * B,) + share.dims[1:] + cfg
+
+        L = lib()
+        # (no parameter count here: the packed tensor must BE the one the pass over the fake planes counted)
+        packed, dims = _net_forward(ctx, x, params, first=3, dims=dims, ws_bytes=L.nc_patchgan_ws_bytes, tag='patchgan')
+        if packed.data_ptr() != share.packed_ptr or ctx.packed_gen != share.gen:
             raise _lib.NcError('patchgan_join_real: the parameters changed since the pass over the fake planes')
         cur = torch.cuda.current_stream()
         for t in (share.saved, share.x, share.y):
             t.record_stream(cur)
         share.x[:B].copy_(x)
-        L = lib()
-        ws = workspace(L.nc_patchgan_ws_bytes(I(2 * B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)), x.device, 'patchgan')
-        check(L.nc_patchgan_fwd_part(_ptr(packed), _ptr(share.x), _ptr(share.y), _ptr(share.saved), I(2 * B), I(0), I(B), I(D),
-                                     I(H), I(W), I(n_layers), I(ndf), I(nd), _ptr(ws), Z(ws.numel()), _stream()),
-              'nc_patchgan_fwd_part')
+        ws = _net_ws(ctx, x.device)
+        check(L.nc_patchgan_fwd_part(_ptr(packed), _ptr(share.x), _ptr(share.y), _ptr(share.saved), 2 * B, 0, B, *dims[1:], _ptr(ws),
+                                     ws.numel(), _stream()), 'nc_patchgan_fwd_part')
         ctx.save_for_backward(share.x, share.saved)
-        ctx.packed, ctx.gen, ctx.cfg, ctx.dims = packed, share.gen, cfg, share.dims
-        ctx.shapes = [tuple(p.shape) for p in params]
         y = share.y
         share.release()  # the autograd graph owns the buffers from here
         return y
@@ -1203,29 +1171,12 @@ class _PatchGANJoinReal(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, saved = ctx.saved_tensors
-        n_layers, ndf, nd = ctx.cfg
-        B, D, H, W = ctx.dims
-        if _param_generation(ctx.packed) != ctx.gen:
-            raise _lib.NcError('fused PatchGAN: the parameters were updated between this forward and its backward')
         dy = dy.contiguous()
-        want_p = any(ctx.needs_input_grad[3:])
-        dpar = _grad_target(ctx, 3) if want_p else None
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        L = lib()
-        ws = workspace(L.nc_patchgan_ws_bytes(I(2 * B), I(D), I(H), I(W), I(n_layers), I(ndf), I(nd)), x.device, 'patchgan')
-        check(L.nc_patchgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), I(2 * B), I(D), I(H),
-                                I(W), I(n_layers), I(ndf), I(nd), _ptr(ws), Z(ws.numel()), _stream()), 'nc_patchgan_bwd')
-        grads = [None] * len(ctx.shapes)
-        if want_p:
-            off = 0
-            for i, shp in enumerate(ctx.shapes):
-                n = 1
-                for s_ in shp:
-                    n *= s_
-                if ctx.needs_input_grad[3 + i]:
-                    grads[i] = dpar[off:off + n].view(shp)
-                off += n
-        return (dx[:B] if dx is not None else None, None, None) + tuple(grads)
+        dpar, ws = _net_backward(ctx, x.device, 'fused PatchGAN: the parameters were updated between this forward and its backward')
+        check(lib().nc_patchgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *ctx.net[2], _ptr(ws),
+                                    ws.numel(), _stream()), 'nc_patchgan_bwd')
+        return _net_grads(ctx, dx[:x.shape[0] // 2] if dx is not None else None, dpar)
 
 
 def patchgan_fake_half(x, params, n_layers, ndf, dimension, share, src=None, axis=None):
@@ -1256,49 +1207,38 @@ class _PatchGANGP(torch.autograd.Function):
     def forward(ctx, x, cfg, *params):
         n_layers, ndf, nd, constant, lambda_gp = cfg
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        if nd != 2 or x.dim() != 4 or x.shape[1] != 1:
-            raise _lib.NcError('patchgan_gp: the fused penalty covers 2-D inputs [B, 1, H, W], got %s (nd=%d)' % (tuple(x.shape), nd))
-        B, H, W = x.shape[0], x.shape[2], x.shape[3]
-        dims = (I(B), I(1), I(H), I(W), I(n_layers), I(ndf), I(nd))
+
+        def dims():
+            if nd != 2 or x.dim() != 4 or x.shape[1] != 1:
+                raise _lib.NcError('patchgan_gp: the fused penalty covers 2-D inputs [B, 1, H, W], got %s (nd=%d)' % (tuple(x.shape), nd))
+            return (x.shape[0], 1, x.shape[2], x.shape[3], n_layers, ndf, nd)
+
         L = lib()
-        packed = _pack_params(params)
-        if packed.numel() != L.nc_patchgan_param_floats(I(n_layers), I(ndf), I(nd)):
-            raise _lib.NcError('fused PatchGAN: parameter count does not match (n_layers=%d, ndf=%d)' % (n_layers, ndf))
+        packed, dims = _net_forward(ctx, x, params, first=2, dims=dims, ws_bytes=L.nc_patchgan_gp_ws_bytes, tag='patchgan',
+                                    n_params=L.nc_patchgan_param_floats(n_layers, ndf, nd), count_msg=_PG_COUNT % (n_layers, ndf))
         nsaved = L.nc_patchgan_gp_saved_floats(*dims)
         if nsaved == 0:
             raise _lib.NcError('patchgan_gp: shape %s not covered (n_layers=%d)' % (tuple(x.shape), n_layers))
         saved = torch.empty(nsaved, dtype=torch.float32, device=x.device)
         g = torch.empty_like(x)
         pen = torch.empty((), dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_patchgan_gp_ws_bytes(*dims), x.device, 'patchgan')
-        check(L.nc_patchgan_gp_fwd(_ptr(packed), _ptr(x), _ptr(g), _ptr(pen), _ptr(saved), *dims, F(constant), F(lambda_gp), _ptr(ws),
-                                   Z(ws.numel()), _stream()), 'nc_patchgan_gp_fwd')
+        ws = _net_ws(ctx, x.device)
+        check(L.nc_patchgan_gp_fwd(_ptr(packed), _ptr(x), _ptr(g), _ptr(pen), _ptr(saved), *dims, constant, lambda_gp, _ptr(ws),
+                                   ws.numel(), _stream()), 'nc_patchgan_gp_fwd')
         ctx.mark_non_differentiable(g)
         ctx.save_for_backward(x, saved, g)
-        ctx.packed = packed
-        ctx.packed_gen = _param_generation(packed)
-        ctx.cfg = (cfg, dims, [tuple(p.shape) for p in params])
+        ctx.gp = (constant, lambda_gp)
         return pen, g
 
     @staticmethod
     def backward(ctx, dpen, dg):
         x, saved, g = ctx.saved_tensors
-        (n_layers, ndf, nd, constant, lambda_gp), dims, shapes = ctx.cfg
-        if _param_generation(ctx.packed) != ctx.packed_gen:
-            raise _lib.NcError('fused PatchGAN gradient penalty: the parameters were updated (optimizer step / checkpoint load) between '
-                               'this forward and its backward; the saved activations no longer match them')
         dpen = dpen.to(torch.float32).contiguous()
-        want_p = any(ctx.needs_input_grad[2:])
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dpar = _grad_target(ctx, 2) if want_p else None  # (x, cfg, *params): the parameters start at input 2
-        L = lib()
-        ws = workspace(L.nc_patchgan_gp_ws_bytes(*dims), x.device, 'patchgan')
-        check(L.nc_patchgan_gp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(g), _ptr(dpen), _ptr(dpar), _ptr(dx), *dims, F(constant),
-                                   F(lambda_gp), _ptr(ws), Z(ws.numel()), _stream()), 'nc_patchgan_gp_bwd')
-        grads = _param_grads(ctx, dpar, shapes, 2) if want_p else [None] * len(shapes)
-        return (dx, None) + tuple(grads)
+        dpar, ws = _net_backward(ctx, x.device, 'fused PatchGAN gradient penalty' + _UPDATED)
+        check(lib().nc_patchgan_gp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(g), _ptr(dpen), _ptr(dpar), _ptr(dx), *ctx.net[2],
+                                       *ctx.gp, _ptr(ws), ws.numel(), _stream()), 'nc_patchgan_gp_bwd')
+        return _net_grads(ctx, dx, dpar)
 
 
 def patchgan_gp(x, params, n_layers, ndf, nd, constant, lambda_gp):
@@ -1308,7 +1248,6 @@ def patchgan_gp(x, params, n_layers, ndf, nd, constant, lambda_gp):
     return _PatchGANGP.apply(x, (int(n_layers), int(ndf), int(nd), float(constant), float(lambda_gp)), *params)
 
 
-# ---- whole-network KernelGAN discriminator (nc_kgan_fwd / nc_kgan_bwd): one C call per direction ------------------------------
 def kgan_dims(shape, nd):
     """(B, D, H, W) of a KernelPatchDiscriminator input; ValueError, before anything is launched, for the inputs the reference's
     InstanceNorm refuses in training mode: an edge below 7 (the valid 7^nd first_layer leaves nothing) or a 7^nd input (one value per
@@ -1337,48 +1276,32 @@ class _KernelGAN(torch.autograd.Function):
     def forward(ctx, x, cfg, *params):
         ndf, nd = cfg
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        if x.shape[1] != 1:
-            raise _lib.NcError('fused KernelGAN discriminator expects one input channel')
-        B, D, H, W = kgan_dims(x.shape, nd)
+
+        def dims():
+            if x.shape[1] != 1:
+                raise _lib.NcError('fused KernelGAN discriminator expects one input channel')
+            return kgan_dims(x.shape, nd) + cfg
+
         L = lib()
-        packed = _pack_params(params)
-        if packed.numel() != L.nc_kgan_param_floats(I(ndf), I(nd)):
-            raise _lib.NcError('fused KernelGAN discriminator: parameter count does not match (ndf=%d, nd=%d)' % (ndf, nd))
-        import ctypes
-        od, oh, ow = I(0), I(0), I(0)
-        check(L.nc_kgan_out_shape(I(B), I(D), I(H), I(W), I(ndf), I(nd), ctypes.byref(od), ctypes.byref(oh), ctypes.byref(ow)),
-              'nc_kgan_out_shape')
-        oshape = (B, 1, oh.value, ow.value) if nd == 2 else (B, 1, od.value, oh.value, ow.value)
-        y = torch.empty(oshape, dtype=torch.float32, device=x.device)
-        saved = torch.empty(L.nc_kgan_saved_floats(I(B), I(D), I(H), I(W), I(ndf), I(nd)), dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_kgan_ws_bytes(I(B), I(D), I(H), I(W), I(ndf), I(nd)), x.device, 'kgan')
-        check(L.nc_kgan_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), I(B), I(D), I(H), I(W), I(ndf), I(nd), _ptr(ws),
-                            Z(ws.numel()), _stream()), 'nc_kgan_fwd')
+        packed, dims = _net_forward(ctx, x, params, first=2, dims=dims, ws_bytes=L.nc_kgan_ws_bytes, tag='kgan',
+                                    n_params=L.nc_kgan_param_floats(ndf, nd),
+                                    count_msg='fused KernelGAN discriminator: parameter count does not match (ndf=%d, nd=%d)' % (ndf, nd))
+        y = torch.empty(_net_out_shape(L.nc_kgan_out_shape, dims, nd), dtype=torch.float32, device=x.device)
+        saved = torch.empty(L.nc_kgan_saved_floats(*dims), dtype=torch.float32, device=x.device)
+        ws = _net_ws(ctx, x.device)
+        check(L.nc_kgan_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), *dims, _ptr(ws), ws.numel(), _stream()), 'nc_kgan_fwd')
         ctx.save_for_backward(x, saved)
-        ctx.packed = packed
-        ctx.packed_gen = _param_generation(packed)
-        ctx.cfg = (cfg, (B, D, H, W), [tuple(p.shape) for p in params])
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, saved = ctx.saved_tensors
-        (ndf, nd), (B, D, H, W), shapes = ctx.cfg
-        if _param_generation(ctx.packed) != ctx.packed_gen:
-            raise _lib.NcError('fused KernelGAN discriminator: the parameters were updated (optimizer step / checkpoint load) between '
-                               'this forward and its backward; the saved activations no longer match them')
         dy = dy.contiguous()
-        want_p = any(ctx.needs_input_grad[2:])
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dpar = _grad_target(ctx, 2) if want_p else None  # (x, cfg, *params): the parameters start at input 2
-        L = lib()
-        ws = workspace(L.nc_kgan_ws_bytes(I(B), I(D), I(H), I(W), I(ndf), I(nd)), x.device, 'kgan')
-        check(L.nc_kgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), I(B), I(D), I(H), I(W), I(ndf),
-                            I(nd), _ptr(ws), Z(ws.numel()), _stream()), 'nc_kgan_bwd')
-        grads = _param_grads(ctx, dpar, shapes, 2) if want_p else [None] * len(shapes)
-        return (dx, None) + tuple(grads)
+        dpar, ws = _net_backward(ctx, x.device, 'fused KernelGAN discriminator' + _UPDATED)
+        check(lib().nc_kgan_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *ctx.net[2], _ptr(ws),
+                                ws.numel(), _stream()), 'nc_kgan_bwd')
+        return _net_grads(ctx, dx, dpar)
 
 
 def kernelgan(x, params, nd, ndf=64):
@@ -1387,80 +1310,52 @@ def kernelgan(x, params, nd, ndf=64):
     return _KernelGAN.apply(x, (int(ndf), int(nd)), *params)
 
 
-# ---- whole-network generators (nc_unet_deconv_train_fwd / _bwd, nc_deep_linear_fwd / _bwd): one C call per direction --
-def _grad_target(ctx, first):
-    """Where a whole-network backward writes its packed parameter gradients: the optimizer's flat gradient slice when EVERY parameter
-    wants a gradient (the kernels OVERWRITE the whole slice), a scratch tensor otherwise -- with all parameters frozen
-    (set_requires_grad(False)) nothing is handed on; with SOME frozen, autograd receives views of the scratch tensor for the others
-    (FlatAdam._collect copies them into the flat buffer) and the frozen ranges of the flat gradient keep the zeros of zero_grad, so
-    FlatAdam.step leaves those parameters where they are."""
-    if all(ctx.needs_input_grad[first:]):
-        return _grad_destination(ctx.packed)
-    return torch.empty_like(ctx.packed)
-
-
-def _param_grads(ctx, dpar, shapes, first):
-    grads = [None] * len(shapes)
-    off = 0
-    for i, shp in enumerate(shapes):
-        n = 1
-        for s in shp:
-            n *= s
-        if ctx.needs_input_grad[first + i]:
-            grads[i] = dpar[off:off + n].view(shp)
-        off += n
-    return grads
+# ---- whole-network generators (nc_unet_deconv_train_fwd / _bwd, nc_deep_linear_fwd / _bwd) ------------------------------------
+def _gen_dims(x):
+    N, _, S0, S1, S2 = x.shape
+    return N, S0, S1, S2
 
 
 class _UnetDeconvTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, *params):
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        N, _, S0, S1, S2 = x.shape
         L = lib()
-        packed = _pack_params(params)
-        if packed.numel() != L.nc_unet_deconv_param_floats():
-            raise _lib.NcError('fused Unet_deconv: parameter count does not match')
-        nsv = L.nc_unet_deconv_saved_floats(I(N), I(S0), I(S1), I(S2))
+        packed, dims = _net_forward(ctx, x, params, first=1, dims=lambda: _gen_dims(x), ws_bytes=L.nc_unet_deconv_train_ws_bytes,
+                                    tag='unet_train', n_params=L.nc_unet_deconv_param_floats(),
+                                    count_msg='fused Unet_deconv: parameter count does not match')
+        nsv = L.nc_unet_deconv_saved_floats(*dims)
         if nsv == 0:
-            raise _lib.NcError('fused Unet_deconv: every edge must be a positive multiple of 4, got %s' % ((S0, S1, S2),))
+            raise _lib.NcError('fused Unet_deconv: every edge must be a positive multiple of 4, got %s' % (dims[1:],))
         saved = torch.empty(nsv, dtype=torch.float32, device=x.device)
-        ws = workspace(L.nc_unet_deconv_train_ws_bytes(I(N), I(S0), I(S1), I(S2)), x.device, 'unet_train')
+        ws = _net_ws(ctx, x.device)
         y = torch.empty_like(x)
         e0 = _prof_begin()
         kept = ctypes.c_uint(0)  # which three-term input copies the forward left in `saved`: travels with this context
-        check(L.nc_unet_deconv_train_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), I(N), I(S0), I(S1), I(S2), _ptr(ws),
-                                         Z(ws.numel()), _stream(), ctypes.byref(kept)), 'nc_unet_deconv_train_fwd')
+        check(L.nc_unet_deconv_train_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), *dims, _ptr(ws), ws.numel(), _stream(),
+                                         ctypes.byref(kept)), 'nc_unet_deconv_train_fwd')
         ctx.kept = kept.value
-        if e0 is not None:
-            _prof_end(e0, 'unet_fwd', 2.0 * 663809 * x.numel())
+        _prof_end(e0, 'unet_fwd', 2.0 * 663809 * x.numel())
         ctx.save_for_backward(x, y, saved)
-        ctx.packed = packed
-        ctx.packed_gen = _param_generation(packed)
         ctx.packed_version = _param_versions(packed)
-        ctx.shapes = [tuple(p.shape) for p in params]
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, saved = ctx.saved_tensors
+        stale = 'fused Unet_deconv: the parameters were updated between this forward and its backward'
         # (the backward's data gradients take the packed weights the forward prepared, its weight-space reads the live buffer: nc_hip.h)
-        if _param_generation(ctx.packed) != ctx.packed_gen or _param_versions(ctx.packed) != ctx.packed_version:
-            raise _lib.NcError('fused Unet_deconv: the parameters were updated between this forward and its backward')
+        if _param_versions(ctx.packed) != ctx.packed_version:
+            raise _lib.NcError(stale)
         dy = dy.contiguous()
-        N, _, S0, S1, S2 = x.shape
-        L = lib()
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dpar = _grad_target(ctx, 1)
-        ws = workspace(L.nc_unet_deconv_train_ws_bytes(I(N), I(S0), I(S1), I(S2)), x.device, 'unet_train')
+        dpar, ws = _net_backward(ctx, x.device, stale, always_dpar=True)
         e0 = _prof_begin()
-        check(L.nc_unet_deconv_bwd(_ptr(ctx.packed), _ptr(x), _ptr(y), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), I(N),
-                                   I(S0), I(S1), I(S2), _ptr(ws), Z(ws.numel()), _stream(), ctypes.c_uint(ctx.kept)), 'nc_unet_deconv_bwd')
-        if e0 is not None:  # dgrad + wgrad of every layer but the first one's data gradient
-            _prof_end(e0, 'unet_bwd', 2.0 * (2 * 663809 - 1728) * x.numel())
-        return (dx,) + tuple(_param_grads(ctx, dpar, ctx.shapes, 1))
+        check(lib().nc_unet_deconv_bwd(_ptr(ctx.packed), _ptr(x), _ptr(y), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *ctx.net[2],
+                                       _ptr(ws), ws.numel(), _stream(), ctx.kept), 'nc_unet_deconv_bwd')
+        # dgrad + wgrad of every layer but the first one's data gradient
+        _prof_end(e0, 'unet_bwd', 2.0 * (2 * 663809 - 1728) * x.numel())
+        return _net_grads(ctx, dx, dpar)
 
 
 def unet_deconv_train(x, params):
@@ -1472,49 +1367,36 @@ class _DeepLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, *params):
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        N, _, S0, S1, S2 = x.shape
         L = lib()
-        packed = _pack_params(params)
-        if packed.numel() != L.nc_deep_linear_param_floats():
-            raise _lib.NcError('fused DeepLinearGenerator: parameter count does not match')
+        packed, dims = _net_forward(ctx, x, params, first=1, dims=lambda: _gen_dims(x), ws_bytes=L.nc_deep_linear_ws_bytes,
+                                    tag='deep_linear', n_params=L.nc_deep_linear_param_floats(),
+                                    count_msg='fused DeepLinearGenerator: parameter count does not match')
         need = any(ctx.needs_input_grad)
-        saved = torch.empty(L.nc_deep_linear_saved_floats(I(N), I(S0), I(S1), I(S2)), dtype=torch.float32,
-                            device=x.device) if need else None
-        ws = workspace(L.nc_deep_linear_ws_bytes(I(N), I(S0), I(S1), I(S2)), x.device, 'deep_linear')
+        saved = torch.empty(L.nc_deep_linear_saved_floats(*dims), dtype=torch.float32, device=x.device) if need else None
+        ws = _net_ws(ctx, x.device)
         y = torch.empty_like(x)
         e0 = _prof_begin()
         kept = ctypes.c_uint(0)
-        check(L.nc_deep_linear_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), I(N), I(S0), I(S1), I(S2), _ptr(ws),
-                                   Z(ws.numel()), _stream(), ctypes.byref(kept)), 'nc_deep_linear_fwd')
+        check(L.nc_deep_linear_fwd(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), *dims, _ptr(ws), ws.numel(), _stream(),
+                                   ctypes.byref(kept)), 'nc_deep_linear_fwd')
         ctx.kept = kept.value
-        if e0 is not None:
-            _prof_end(e0, 'deep_linear_fwd', 2.0 * 647120 * x.numel())
+        _prof_end(e0, 'deep_linear_fwd', 2.0 * 647120 * x.numel())
         if need:
             ctx.save_for_backward(x, saved)
-            ctx.packed = packed
-            ctx.packed_gen = _param_generation(packed)
-            ctx.shapes = [tuple(p.shape) for p in params]
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, saved = ctx.saved_tensors
-        if _param_generation(ctx.packed) != ctx.packed_gen:
-            raise _lib.NcError('fused DeepLinearGenerator: the parameters were updated between this forward and its backward')
         dy = dy.contiguous()
-        N, _, S0, S1, S2 = x.shape
-        L = lib()
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dpar = _grad_target(ctx, 1)
-        ws = workspace(L.nc_deep_linear_ws_bytes(I(N), I(S0), I(S1), I(S2)), x.device, 'deep_linear')
+        dpar, ws = _net_backward(ctx, x.device, 'fused DeepLinearGenerator: the parameters were updated between this forward and its '
+                                 'backward', always_dpar=True)
         e0 = _prof_begin()
-        check(L.nc_deep_linear_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), I(N), I(S0), I(S1),
-                                   I(S2), _ptr(ws), Z(ws.numel()), _stream(), ctypes.c_uint(ctx.kept)), 'nc_deep_linear_bwd')
-        if e0 is not None:
-            _prof_end(e0, 'deep_linear_bwd', 2.0 * (2 * 647120 - (0 if dx is not None else 21952)) * x.numel())
-        return (dx,) + tuple(_param_grads(ctx, dpar, ctx.shapes, 1))
+        check(lib().nc_deep_linear_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *ctx.net[2], _ptr(ws),
+                                       ws.numel(), _stream(), ctx.kept), 'nc_deep_linear_bwd')
+        _prof_end(e0, 'deep_linear_bwd', 2.0 * (2 * 647120 - (0 if dx is not None else 21952)) * x.numel())
+        return _net_grads(ctx, dx, dpar)
 
 
 def deep_linear(x, params):
@@ -1529,7 +1411,7 @@ def gen_lp_supported(kind, shape):
         return False
     N, _, S0, S1, S2 = shape
     fn = lib().nc_unet_deconv_lp_supported if kind == 'unet' else lib().nc_deep_linear_lp_supported
-    return bool(fn(I(N), I(S0), I(S1), I(S2), I(_DT['bf16'])))
+    return bool(fn(N, S0, S1, S2, _DT['bf16']))
 
 
 class _GenLp(torch.autograd.Function):
@@ -1538,63 +1420,46 @@ class _GenLp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kind, *params):
         x = x.contiguous()
-        _chk(x, *params)
-        _f32(x, *params)
-        N, _, S0, S1, S2 = x.shape
         L = lib()
-        pre = 'nc_unet_deconv_lp' if kind == 'unet' else 'nc_deep_linear_lp'
-        packed = _pack_params(params)
-        want = L.nc_unet_deconv_param_floats() if kind == 'unet' else L.nc_deep_linear_param_floats()
-        if packed.numel() != want:
-            raise _lib.NcError('%s: parameter count does not match' % pre)
-        dims = (I(N), I(S0), I(S1), I(S2))
+        net = 'unet_deconv' if kind == 'unet' else 'deep_linear'
+        pre = 'nc_%s_lp' % net
+        packed, dims = _net_forward(ctx, x, params, first=2, dims=lambda: _gen_dims(x), ws_bytes=getattr(L, pre + '_ws_bytes'), tag=pre,
+                                    n_params=getattr(L, 'nc_%s_param_floats' % net)(), count_msg='%s: parameter count does not match' % pre)
         nsv = getattr(L, pre + '_saved_bytes')(*dims)
         if nsv == 0:
-            raise _lib.NcError('%s: shape %s is not covered by the 16-bit kernels' % (pre, (S0, S1, S2)))
+            raise _lib.NcError('%s: shape %s is not covered by the 16-bit kernels' % (pre, dims[1:]))
         saved = torch.empty(nsv, dtype=torch.uint8, device=x.device)
-        ws = workspace(getattr(L, pre + '_ws_bytes')(*dims), x.device, pre)
+        ws = _net_ws(ctx, x.device)
         y = torch.empty_like(x)
-        dt = _DT['bf16']
-        flop = 2.0 * (663809 if kind == 'unet' else 647120) * x.numel()
         e0 = _prof_begin()
         kept = ctypes.c_uint(0)  # deep_linear_gen: the form the forward took (the backward follows it, not the switches of its own moment)
         extra = (ctypes.byref(kept),) if kind != 'unet' else ()
-        check(getattr(L, pre + '_fwd')(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), *dims, I(dt), _ptr(ws), Z(ws.numel()),
+        check(getattr(L, pre + '_fwd')(_ptr(packed), _ptr(x), _ptr(y), _ptr(saved), *dims, _DT['bf16'], _ptr(ws), ws.numel(),
                                        _stream(), *extra), pre + '_fwd')
-        ctx.kept = kept.value
-        if e0 is not None:
-            _prof_end(e0, ('unet' if kind == 'unet' else 'deep_linear') + '_lp_fwd', flop)
+        ctx.kept, ctx.kind = kept.value, kind
+        _prof_end(e0, ('unet' if kind == 'unet' else 'deep_linear') + '_lp_fwd', 2.0 * (663809 if kind == 'unet' else 647120) * x.numel())
         ctx.save_for_backward(x, y, saved)
-        ctx.packed, ctx.packed_gen, ctx.kind = packed, _param_generation(packed), kind
-        ctx.shapes = [tuple(p.shape) for p in params]
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, saved = ctx.saved_tensors
-        if _param_generation(ctx.packed) != ctx.packed_gen:
-            raise _lib.NcError('16-bit generator: the parameters were updated between this forward and its backward')
         dy = dy.contiguous()
-        N, _, S0, S1, S2 = x.shape
-        L = lib()
-        kind = ctx.kind
-        pre = 'nc_unet_deconv_lp' if kind == 'unet' else 'nc_deep_linear_lp'
-        dims = (I(N), I(S0), I(S1), I(S2))
+        kind, dims, dt = ctx.kind, ctx.net[2], _DT['bf16']
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        dpar = _grad_target(ctx, 2)
-        ws = workspace(getattr(L, pre + '_ws_bytes')(*dims), x.device, pre)
-        dt = _DT['bf16']
+        dpar, ws = _net_backward(ctx, x.device, '16-bit generator: the parameters were updated between this forward and its backward',
+                                 always_dpar=True)
+        L = lib()
         e0 = _prof_begin()
         if kind == 'unet':
-            check(L.nc_unet_deconv_lp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(y), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *dims,
-                                          I(dt), _ptr(ws), Z(ws.numel()), _stream()), pre + '_bwd')
+            check(L.nc_unet_deconv_lp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(y), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *dims, dt,
+                                          _ptr(ws), ws.numel(), _stream()), 'nc_unet_deconv_lp_bwd')
         else:
-            check(L.nc_deep_linear_lp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *dims, I(dt),
-                                          _ptr(ws), Z(ws.numel()), _stream(), ctypes.c_uint(ctx.kept)), pre + '_bwd')
-        if e0 is not None:
-            mac = (2 * 663809 - 1728) if kind == 'unet' else 2 * 647120
-            _prof_end(e0, ('unet' if kind == 'unet' else 'deep_linear') + '_lp_bwd', 2.0 * mac * x.numel())
-        return (dx, None) + tuple(_param_grads(ctx, dpar, ctx.shapes, 2))
+            check(L.nc_deep_linear_lp_bwd(_ptr(ctx.packed), _ptr(x), _ptr(saved), _ptr(dy), _ptr(dx), _ptr(dpar), *dims, dt, _ptr(ws),
+                                          ws.numel(), _stream(), ctx.kept), 'nc_deep_linear_lp_bwd')
+        mac = (2 * 663809 - 1728) if kind == 'unet' else 2 * 647120
+        _prof_end(e0, ('unet' if kind == 'unet' else 'deep_linear') + '_lp_bwd', 2.0 * mac * x.numel())
+        return _net_grads(ctx, dx, dpar)
 
 
 def unet_deconv_lp(x, params):
@@ -1619,8 +1484,8 @@ class _SpectralNorm(torch.autograd.Function):
         w = torch.empty_like(w_orig)
         sigma = torch.empty(1, dtype=torch.float32, device=w_orig.device)
         scratch = torch.empty(K, dtype=torch.float32, device=w_orig.device)
-        check(lib().nc_spectral_norm_fwd(_ptr(w_orig), _ptr(u), _ptr(v), _ptr(w), _ptr(sigma), _ptr(scratch), I(K), I(M),
-                                         I(1 if power_iteration else 0), F(1e-12), _stream()), 'nc_spectral_norm_fwd')
+        check(lib().nc_spectral_norm_fwd(_ptr(w_orig), _ptr(u), _ptr(v), _ptr(w), _ptr(sigma), _ptr(scratch), K, M,
+                                         1 if power_iteration else 0, 1e-12, _stream()), 'nc_spectral_norm_fwd')
         # u, v as they stand after this forward (later forwards update the buffers in place)
         ctx.save_for_backward(w, u.clone(), v.clone(), sigma)
         return w
@@ -1632,7 +1497,7 @@ class _SpectralNorm(torch.autograd.Function):
         K = w.shape[0]
         M = w.numel() // K
         dw = torch.empty_like(w)
-        check(lib().nc_spectral_norm_bwd(_ptr(g), _ptr(w), _ptr(u), _ptr(v), _ptr(sigma), _ptr(dw), I(K), I(M), _stream()),
+        check(lib().nc_spectral_norm_bwd(_ptr(g), _ptr(w), _ptr(u), _ptr(v), _ptr(sigma), _ptr(dw), K, M, _stream()),
               'nc_spectral_norm_bwd')
         return dw, None, None, None
 

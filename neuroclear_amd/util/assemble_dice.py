@@ -15,22 +15,21 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .._lib import I, P, check, lib
+from .._lib import P, check, lib
 from . import util
 
 
 def match_histograms(source, template):
     """skimage.exposure.match_histograms(source, template) on the device (float32 tensors of equal size)."""
-    from .._lib import L_, Z
     src = source.contiguous().float()
     tm = template.contiguous().float()
     if src.numel() != tm.numel() or not src.is_cuda or not tm.is_cuda:
         raise ValueError('match_histograms: two CUDA tensors of equal size expected')
     n = src.numel()
     out = torch.empty_like(src)
-    nb = lib().nc_match_histograms_ws_bytes(L_(n))
+    nb = lib().nc_match_histograms_ws_bytes(n)
     ws = torch.empty(nb, dtype=torch.uint8, device=src.device)
-    check(lib().nc_match_histograms(P(src.data_ptr()), P(tm.data_ptr()), P(out.data_ptr()), L_(n), P(ws.data_ptr()), Z(nb),
+    check(lib().nc_match_histograms(P(src.data_ptr()), P(tm.data_ptr()), P(out.data_ptr()), n, P(ws.data_ptr()), nb,
                                     P(torch.cuda.current_stream().cuda_stream)), 'nc_match_histograms')
     return out
 
@@ -110,8 +109,8 @@ class Assemble_Dice:
             if z0 < self.slab[0] or z0 + self.roi_size > self.slab[1]:
                 raise AssertionError('cube %d lies outside the planes [%d, %d) of this accumulator' % (index, self.slab[0], self.slab[1]))
             base -= self.slab[0] * P1 * P2 * 4
-        check(lib().nc_assemble_scatter_add(P(cube.data_ptr()), P(base), I(P0), I(P1), I(P2),
-                                            I(self.roi_size), I(self.overlap), I(self.border_cut), I(int(index)),
+        check(lib().nc_assemble_scatter_add(P(cube.data_ptr()), P(base), P0, P1, P2,
+                                            self.roi_size, self.overlap, self.border_cut, int(index),
                                             P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_scatter_add')
 
     def match_cube(self, fake, real):
@@ -137,8 +136,8 @@ class Assemble_Dice:
         u16 = self.imtype == 'uint16'
         out = torch.empty((z1 - z0, L1, L2), dtype=torch.int16 if u16 else torch.uint8, device=self.device)
         if z1 > z0:
-            check(lib().nc_assemble_finalize_slab(P(own_acc.data_ptr()), P(out.data_ptr()), I(1 if u16 else 0), I(P0), I(P1), I(P2), I(L0),
-                                                  I(L1), I(L2), I(self.roi_size), I(self.overlap), I(z0), I(z1 - z0), I(za),
+            check(lib().nc_assemble_finalize_slab(P(own_acc.data_ptr()), P(out.data_ptr()), 1 if u16 else 0, P0, P1, P2, L0,
+                                                  L1, L2, self.roi_size, self.overlap, z0, z1 - z0, za,
                                                   P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_finalize_slab')
         return out
 
@@ -157,8 +156,8 @@ class Assemble_Dice:
                 host = out.cpu().numpy()
                 self.visual_ret[name] = host.view(np.uint16) if u16 else host
                 continue
-            check(lib().nc_assemble_finalize(P(acc.data_ptr()), P(out.data_ptr()), I(1 if u16 else 0), I(P0), I(P1),
-                                             I(P2), I(L0), I(L1), I(L2), I(self.roi_size), I(self.overlap),
+            check(lib().nc_assemble_finalize(P(acc.data_ptr()), P(out.data_ptr()), 1 if u16 else 0, P0, P1,
+                                             P2, L0, L1, L2, self.roi_size, self.overlap,
                                              P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_finalize')
             host = out.cpu().numpy()
             self.visual_ret[name] = host.view(np.uint16) if u16 else host
@@ -169,16 +168,15 @@ class Assemble_Dice:
         L0, L1, L2 = self.image_size_original
         stream = P(torch.cuda.current_stream().cuda_stream)
         merged = torch.empty_like(acc)
-        check(lib().nc_assemble_merge(P(acc.data_ptr()), P(merged.data_ptr()), I(L0), I(L1), I(L2), I(self.roi_size),
-                                      I(self.overlap), stream), 'nc_assemble_merge')
+        check(lib().nc_assemble_merge(P(acc.data_ptr()), P(merged.data_ptr()), L0, L1, L2, self.roi_size,
+                                      self.overlap, stream), 'nc_assemble_merge')
         p_lo, p_hi = pct.percentile(merged, (self.p1, self.p99))
         if not p_hi > p_lo:
             raise ValueError('normalize_intensity: empty intensity range (%g, %g)' % (p_lo, p_hi))
         self.last_percentiles = (p_lo, p_hi)
-        from .._lib import F
-        check(lib().nc_assemble_rescale_finalize(P(merged.data_ptr()), P(out.data_ptr()), I(1 if u16 else 0), I(L0),
-                                                 I(L1), I(L2), I(self.roi_size), I(self.overlap),
-                                                 F(np.float32(p_lo)), F(np.float32(p_hi)), F(np.float32(p_hi - p_lo)),
+        check(lib().nc_assemble_rescale_finalize(P(merged.data_ptr()), P(out.data_ptr()), 1 if u16 else 0, L0,
+                                                 L1, L2, self.roi_size, self.overlap,
+                                                 np.float32(p_lo), np.float32(p_hi), np.float32(p_hi - p_lo),
                                                  stream), 'nc_assemble_rescale_finalize')
 
     def getDict(self):

@@ -3,12 +3,11 @@
 (1.21.2, conda_environment/neuroclear_env.yml:155): virtual index (n - 1) * q / 100 in float64, neighbours a <= b,
 t = fractional part, p = a + (b - a) * t, or b - (b - a) * (1 - t) when t >= 0.5, with (b - a) taken in float32 and the
 rest in float64 (numpy/lib/function_base.py `_lerp` of that version on 0-d float32 / float64 operands)."""
-import ctypes
 
 import numpy as np
 import torch
 
-from .._lib import I, L_, P, check, lib
+from .._lib import P, check, lib
 
 
 def _key_to_float(key):
@@ -25,7 +24,7 @@ def select_kth(x, k):
     stream = P(torch.cuda.current_stream().cuda_stream)
     prefix, rank = 0, int(k)
     for p_, bits in ((0, 12), (1, 12), (2, 8)):
-        check(lib().nc_radix_hist(P(x.data_ptr()), L_(n), I(p_), ctypes.c_uint(prefix), P(hist.data_ptr()), stream),
+        check(lib().nc_radix_hist(P(x.data_ptr()), n, p_, prefix, P(hist.data_ptr()), stream),
               'nc_radix_hist')
         h = hist.cpu().numpy().astype(np.int64)
         c = np.cumsum(h)

@@ -852,19 +852,25 @@ def test_patchgan_spectral_norm(golden_dir, tag):
 
 
 @pytest.mark.parametrize('pattern', ['every_third', 'first_only'])
-@pytest.mark.parametrize('which', ['unet_deconv', 'deep_linear_gen', 'patchgan'])
+@pytest.mark.parametrize('which', ['unet_deconv', 'deep_linear_gen', 'patchgan', 'kernelgan', 'patchgan_gp', 'athena_pair'])
 def test_partly_frozen_parameters_are_not_updated(which, pattern):
     """Some (not all) parameters of a network with requires_grad off: the whole-network backward must not leave gradients for them
     in the optimizer's flat buffer (FlatAdam.step is one launch over the whole buffer), the others get exactly the gradient of the
     unfrozen run, and a step moves only those.  (base_model.py:221-232 set_requires_grad freezes whole networks; a user freezing an
     encoder is the partial case.)  'first_only' freezes the FIRST parameter alone (model.0.weight of the PatchGAN): the case an off-by-one
-    in the autograd node's input index misses (_PatchGAN.backward looked at needs_input_grad[3:])."""
+    in the autograd node's input index misses (_PatchGAN.backward looked at needs_input_grad[3:]).  Every whole-network
+    Function routes its parameter gradients through the same helpers of ops.py; the cases cover those the networks above do not reach:
+    the KernelGAN discriminator (12^2: 6^2 positions behind the valid 7^2 layer), the WGAN-GP penalty, and Athena's pair -- the pass over
+    the fake planes with the discriminator frozen as a whole, as that pass demands, then the partly frozen pass that joins the real ones."""
     from neuroclear_amd.models.axial_to_lateral_gan_apollo_model import FlatAdam
 
     def build():
-        if which == 'patchgan':
+        if which in ('patchgan', 'patchgan_gp', 'athena_pair'):
             net = load(networks.define_D(1, 64, 'basic', 3, 'instance', 'kaiming', 0.02, False, [0], dimension=2), S.patchgan_spec(2), 5)
             x = torch.from_numpy(rnd(3, (4, 1, 36, 36))).to(DEV)
+        elif which == 'kernelgan':
+            net = load(networks.define_D(1, 64, 'kernelGAN', 3, 'instance', 'normal', 0.02, False, [0], dimension=2), S.kernelgan_spec(2), 5)
+            x = torch.from_numpy(rnd(3, (4, 1, 12, 12))).to(DEV)
         elif which == 'unet_deconv':
             net = load(networks.define_G(1, 1, 64, 'unet_deconv', 'instance', False, 'kaiming', 0.02, [0]), S.unet_deconv_spec(), 5)
             x = torch.from_numpy(rnd(3, (1, 1, 16, 16, 16))).to(DEV)
@@ -873,9 +879,24 @@ def test_partly_frozen_parameters_are_not_updated(which, pattern):
             x = torch.from_numpy(rnd(3, (1, 1, 16, 16, 16))).to(DEV)
         return net, FlatAdam(net.parameters(), lr=1e-3, betas=(0.5, 0.999)), x
 
+    def loss(net, x):
+        ps = list(net.parameters())
+        if which == 'patchgan_gp':
+            return ops.patchgan_gp(x, ps, *net._cfg, 1.0, 10.0)[0]
+        if which != 'athena_pair':
+            return (net(x) ** 2).mean()
+        wants = [p.requires_grad for p in ps]
+        for p in ps:
+            p.requires_grad_(False)
+        share = ops.PatchGANShare()
+        net.forward_fake_half(torch.from_numpy(rnd(4, tuple(x.shape))).to(DEV), share, None, None)
+        for p, w in zip(ps, wants):
+            p.requires_grad_(w)
+        return (net.forward_join_real(x, share) ** 2).mean()
+
     net, opt, x = build()
     opt.zero_grad()
-    (net(x) ** 2).mean().backward()
+    loss(net, x).backward()
     opt._collect()
     full = opt.grad.clone()
     net2, opt2, _ = build()
@@ -885,7 +906,7 @@ def test_partly_frozen_parameters_are_not_updated(which, pattern):
         ps[i].requires_grad_(False)
     before = opt2.flat.clone()
     opt2.zero_grad()
-    (net2(x) ** 2).mean().backward()
+    loss(net2, x).backward()
     opt2.step()
     off = 0
     for i, p in enumerate(ps):
