@@ -584,6 +584,11 @@ int nc_instnorm_act_bwd_dbias_h2_debug(const float* dy, const float* w1, const f
 size_t nc_convT_k2s2_split_h2_ws_bytes(int N, int C, int D, int H, int W, int K);
 int nc_convT_k2s2_fwd_split_h2_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C,
                                      int D, int H, int W, int K, unsigned* out_cell, void* ws, size_t ws_bytes, void* stream);
+/* Test export of the THREE-term (S3) output of the fp32 matrix-core kernel (csrc/convt.hip convT_fwd_s3; tests/test_gpu_convt.py): y nullable;
+ * ys = channels [ys_c0, ys_c0 + K) of a ys_ctot-channel S3 tensor of the output volume (nc_s3_bytes), everything % 8.  A shape the kernel does
+ * not cover (C != 128, K % 32 != 0, nc_set_force_direct(1)) is refused with NC_ERR_SHAPE. */
+int nc_convT_k2s2_fwd_s3_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C, int D,
+                               int H, int W, int K, void* stream);
 
 /* ---- Learned-PSF generators (--netG_B linearkernel / linearkernel_double / linearkernel_LK31): LinearKernel and LinearKernel_double at
  *      models/networks.py:840-871, one bias-free Conv3d(1, 1, k, stride 1, padding (k - 1) / 2) -- applied twice with one weight in the

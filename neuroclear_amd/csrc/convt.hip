@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void k_convT_fwd(const float* __restrict__ x, 
 #pragma unroll
   for (int j = 0; j < KT; ++j)
 #pragma unroll
-    for (int t = 0; t < 8; ++t) acc[j][t] = bias ? bias[k0 + j] : 0.f;
+    for (int t = 0; t < 8; ++t) acc[j][t] = 0.f;
   const float* xn = x + (long)n * C * S + p;
   for (int c = 0; c < C; ++c) {
     const float xv = xn[(long)c * S];
@@ -40,12 +40,15 @@ __global__ __launch_bounds__(256) void k_convT_fwd(const float* __restrict__ x, 
 #pragma unroll
   for (int j = 0; j < KT; ++j) {
     float* yk = y + ((long)n * K + k0 + j) * S2;
+    // the bias joins the finished sum (as in k_convT_fwd_mfma): one rounding at the output's magnitude.  As the accumulators' initial value it
+    // put every one of the C roundings at the bias's magnitude -- 4 x the error of the fp32 operator for a bias of order 1 (tests/test_gpu_convt.py)
+    const float bj = bias ? bias[k0 + j] : 0.f;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         float2* dst = reinterpret_cast<float2*>(yk + ((long)(2 * iz + a) * H2 + (2 * iy + b)) * W2 + 2 * ix);
-        *dst = make_float2(acc[j][(a * 2 + b) * 2], acc[j][(a * 2 + b) * 2 + 1]);
+        *dst = make_float2(acc[j][(a * 2 + b) * 2] + bj, acc[j][(a * 2 + b) * 2 + 1] + bj);
       }
   }
 }
@@ -167,9 +170,13 @@ __global__ __launch_bounds__(256) void k_convT_dgrad(const float* __restrict__ d
       }
 #pragma unroll
     for (int j = 0; j < CT; ++j) {
+      // the 8 taps of an output channel are summed first and join the running sum as one term: K additions into acc instead of one chain of
+      // 8 K (1024 at K = 128, where the chain was 4.6 x the fp32 operator's largest error: tests/test_gpu_convt.py)
       const float* wc = w + ((long)(c0 + j) * K + k) * 8;
+      float sk = g[0] * wc[0];
 #pragma unroll
-      for (int t = 0; t < 8; ++t) acc[j] = fmaf(g[t], wc[t], acc[j]);
+      for (int t = 1; t < 8; ++t) sk = fmaf(g[t], wc[t], sk);
+      acc[j] += sk;
     }
   }
   if (valid) {

@@ -91,4 +91,15 @@ int nc_convT_k2s2_fwd_split_h2_debug(const float* x, const float* w, const float
   return convT_fwd_split_h2(x, w, bias, y, ys, ys_ctot, ys_c0, N, C, D, H, W, K, out_cell, ws, ws_bytes, s);
 }
 
+// the three-term (S3) output of the fp32 matrix-core kernel (convt.hip convT_fwd_s3; tests/test_gpu_convt.py): pointers and coverage
+// (convT_fwd_s3_supported) are checked by the internal function, the slice [ys_c0, ys_c0 + K) of the ys_ctot channels here
+int nc_convT_k2s2_fwd_s3_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C, int D,
+                               int H, int W, int K, void* stream) {
+  if (N < 1 || C < 1 || D < 1 || H < 1 || W < 1 || K < 1 || ys_ctot < 8 || ys_ctot % 8 || ys_c0 % 8 || ys_c0 < 0 || (long)ys_c0 + K > ys_ctot) {
+    set_error("convT_k2s2_fwd_s3_debug: shape not covered");
+    return NC_ERR_SHAPE;
+  }
+  return convT_fwd_s3(x, w, bias, y, ys, ys_ctot, ys_c0, N, C, D, H, W, K, stream);
+}
+
 }  // extern "C"
