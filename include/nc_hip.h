@@ -589,6 +589,11 @@ int nc_convT_k2s2_fwd_split_h2_debug(const float* x, const float* w, const float
  * not cover (C != 128, K % 32 != 0, nc_set_force_direct(1)) is refused with NC_ERR_SHAPE. */
 int nc_convT_k2s2_fwd_s3_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C, int D,
                                int H, int W, int K, void* stream);
+/* Test export of the one-pass inference tail of Unet_deconv (csrc/norm_act.hip k_in_act_tail; tests/test_gpu_norm.py), which otherwise runs only
+ * inside nc_unet_deconv_fwd: y[v] = sigmoid(w2 * (b1 + sum_c w1[c] * relu((x[c][v] - mean[c]) * rstd[c])) + b2) for one sample of C <= 256
+ * channels and S voxels (more channels: NC_ERR_SHAPE); w2, b1, b2 point at one float each. */
+int nc_instnorm_relu_tail_sigmoid_debug(const float* x, const float* mean, const float* rstd, const float* w1, const float* b1, const float* w2,
+                                        const float* b2, float* y, int C, long S, void* stream);
 
 /* ---- Learned-PSF generators (--netG_B linearkernel / linearkernel_double / linearkernel_LK31): LinearKernel and LinearKernel_double at
  *      models/networks.py:840-871, one bias-free Conv3d(1, 1, k, stride 1, padding (k - 1) / 2) -- applied twice with one weight in the

@@ -102,4 +102,12 @@ int nc_convT_k2s2_fwd_s3_debug(const float* x, const float* w, const float* bias
   return convT_fwd_s3(x, w, bias, y, ys, ys_ctot, ys_c0, N, C, D, H, W, K, stream);
 }
 
+// the one-pass inference tail of Unet_deconv (norm_act.hip k_in_act_tail; tests/test_gpu_norm.py): the channel limit is the internal function's
+int nc_instnorm_relu_tail_sigmoid_debug(const float* x, const float* mean, const float* rstd, const float* w1, const float* b1, const float* w2,
+                                        const float* b2, float* y, int C, long S, void* stream) {
+  if (!x || !mean || !rstd || !w1 || !b1 || !w2 || !b2 || !y) { set_error("instnorm_relu_tail_sigmoid_debug: null pointer"); return NC_ERR_ARG; }
+  if (C < 1 || S < 1) { set_error("instnorm_relu_tail_sigmoid_debug: bad shape"); return NC_ERR_SHAPE; }
+  return instnorm_relu_tail_sigmoid(x, mean, rstd, w1, b1, w2, b2, y, C, S, (hipStream_t)stream);
+}
+
 }  // extern "C"
