@@ -76,6 +76,18 @@ int nc_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias /* or
 int nc_conv_bwd(const float* x, const float* dy, const float* w, float* dx, float* dw, float* dbias, int N, int C, int D, int H, int W,
                 int K, int kd, int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, void* stream);
 
+/* Conv2d(k 3, s 1, p 1) of the 2-D generators (networks.py:413-476 with dimension == 2): nc_conv_fwd / nc_conv_dgrad run such a layer on the
+ * image-tiled fp32 matrix-core kernel of csrc/conv2d_k3.hip where it covers the shape -- reduction side (C forward, K backward) even and >= 16,
+ * output side a multiple of 64, enough tiles to fill the chip -- and on the gather GEMM otherwise.  nc_set_conv2d_k3(0) puts every such layer
+ * back on the gather GEMM (process-wide, default 1, no environment variable; nc_set_force_direct(1) overrides it).  nc_conv2d_k3_active: does
+ * the call with these dimensions take the kernel right now (what: 0 forward, 1 data gradient)?  nc_conv2d_k3_set_cfg(i) pins tile configuration
+ * i of nc_conv2d_k3_num_cfgs() (tests: every configuration gives the same bits), -1 returns to the launcher's choice.                        */
+int nc_set_conv2d_k3(int on);                 /* returns the previous setting */
+int nc_get_conv2d_k3(void);
+int nc_conv2d_k3_active(int what, int N, int C, int H, int W, int K);
+int nc_conv2d_k3_set_cfg(int cfg);            /* returns the previous pin */
+int nc_conv2d_k3_num_cfgs(void);
+
 /* ---- The same convolution on the 16-bit matrix cores (BASELINE.json configs[3]: "fp16 MFMA path with fp32
  *      InstanceNorm accumulate").  Tensors and master weights stay fp32 at this boundary; inside, operands are rounded
  *      (round-to-nearest-even) to `dtype` (NC_DT_BF16: v_mfma_f32_32x32x16_bf16, NC_DT_F16: ..._f16), products are
@@ -112,6 +124,19 @@ int nc_convT_k2s2_dgrad(const float* dy, const float* w, float* dx, int N, int C
                         void* ws, size_t ws_bytes, void* stream);
 int nc_convT_k2s2_wgrad(const float* x, const float* dy, float* dw, float* dbias, int N, int C, int D, int H, int W,
                         int K, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- ConvTranspose2d(k=2, s=2): the same layer of a generator built with dimension=2 (networks.py:382-390, 500, 503):
+ *      x[N,C,H,W], w[C,K,2,2], bias[K] or NULL, y[N,K,2H,2W]; y[n,k,2u+a,2v+b] = bias[k] + sum_c x[n,c,u,v] w[c,k,a,b].  fp32; the forward runs
+ *      on the fp32 matrix cores for K % 32 == 0, C % 16 == 0, C >= 128 (the U-Nets' 512->256, 256->128, 128->64), on the VALU otherwise and under
+ *      nc_set_force_direct(1).  dgrad / wgrad take the gather GEMM where it applies and `ws` covers nc_convT2d_ws_bytes, VALU kernels otherwise;
+ *      dbias (nullable) needs the workspace.  Results are run-to-run bit-identical.                                              */
+size_t nc_convT2d_ws_bytes(int N, int C, int H, int W, int K);
+int nc_convT2d_k2s2_fwd(const float* x, const float* w, const float* bias, float* y, int N, int C, int H, int W, int K,  /* networks.py:500,503 */
+                        void* stream);
+int nc_convT2d_k2s2_dgrad(const float* dy, const float* w, float* dx, int N, int C, int H, int W, int K,  /* backward of networks.py:500,503 */
+                          void* ws, size_t ws_bytes, void* stream);
+int nc_convT2d_k2s2_wgrad(const float* x, const float* dy, float* dw, float* dbias, int N, int C, int H, int W,  /* backward of networks.py:500,503 */
+                          int K, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- InstanceNorm{2,3}d(affine=False, track_running_stats=False) + ReLU / LeakyReLU(slope)
  *      (networks.py:33-34 with :422-423 (slope 0) and :1042-1046 (slope 0.2)).  One instance = one (n, c) plane of S

@@ -97,6 +97,7 @@ static int fwd_path(const ConvDims& d) {
   if (g_split && s3_fwd_supported(d)) return 9;
   if (g_split && p2d_fwd_supported(d)) return 10;
   if (g_split && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) in pseudo-channel form on the two-term kernels (conv_s3x.hip)
+  if (conv2d_k3_on() && conv2d_k3_fwd_supported(d)) return 12;  // Conv2d 3 x 3 of the 2-D generators, image-tiled (conv2d_k3.hip)
   return (c1k3_fwd_supported(d) || mfma_fwd_supported(d)) ? 1 : flat_1x1_supported(d) ? 3 : k1_fwd_supported(d) ? 5 : pg1_on(d) ? 8 : sconv_on(d, 0) ? 7 : gemm_fwd_supported(d) ? 2 : 0;
 }
 static int dgrad_path(const ConvDims& d) {
@@ -104,6 +105,7 @@ static int dgrad_path(const ConvDims& d) {
   if (g_split && s3_dgrad_supported(d)) return 9;
   if (g_split && p2d_dgrad_supported(d)) return 10;
   if (g_split && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7): two-term pseudo-channel form + fold (conv_s3x.hip)
+  if (conv2d_k3_on() && conv2d_k3_dgrad_supported(d)) return 12;
   return mfma_dgrad_supported(d) ? 1 : flat_1x1_supported(d) ? 3 : to1_mfma_supported(d) ? 6 : to1_dgrad_supported(d) ? 0
                                                                                               : pg1_on(d)             ? 8
                                                                                               : sconv_on(d, 1)        ? 7
@@ -184,6 +186,16 @@ int nc_conv2d_split_active(int what, int N, int C, int H, int W, int K, int k, i
   return what == 0 ? (p2d_fwd_supported(d) ? 1 : 0) : what == 1 ? (p2d_dgrad_supported(d) ? 1 : 0) : what == 2 ? (p2d_wgrad_supported(d) ? 1 : 0) : 0;
 }
 
+int nc_set_conv2d_k3(int on) { const int prev = conv2d_k3_on() ? 1 : 0; conv2d_k3_set(on); return prev; }
+int nc_get_conv2d_k3(void) { return conv2d_k3_on() ? 1 : 0; }
+int nc_conv2d_k3_set_cfg(int cfg) { return conv2d_k3_set_cfg(cfg); }
+int nc_conv2d_k3_num_cfgs(void) { return conv2d_k3_num_cfgs(); }
+int nc_conv2d_k3_active(int what, int N, int C, int H, int W, int K) {
+  ConvDims d;
+  if (!make_dims(d, N, C, 1, H, W, K, 1, 3, 3, 1, 1)) return 0;
+  return what == 0 ? (fwd_path(d) == 12 ? 1 : 0) : what == 1 ? (dgrad_path(d) == 12 ? 1 : 0) : 0;
+}
+
 int nc_conv_fwd_path(int C, int K, int kd, int kh, int kw, int stride, int pad) {
   ConvDims d;
   const int e = (kd == 1 && kh == 1 && kw == 1) ? 256 : 32;  // pointwise: a plane large enough for the flat kernel
@@ -229,6 +241,7 @@ size_t nc_conv_ws_bytes(int N, int C, int D, int H, int W, int K, int kd, int kh
     const size_t sc = pg1_ws_bytes(d);
     if (sc > b) b = sc;
   }
+  if (conv2d_k3_ws_bytes(d) > b) b = conv2d_k3_ws_bytes(d);  // its packed weights (whether or not the switch is on: the size does not depend on it)
   if (g_split) {
     size_t sc = p2d_ws_bytes(d);
     if (sc > b) b = sc;
@@ -272,6 +285,7 @@ int nc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int
   if (path == 9) return conv_fwd_s3(x, nullptr, w, bias, y, d, ws, ws_bytes, s);
   if (path == 10) return conv_fwd_p2d(x, w, bias, y, d, ws, ws_bytes, s);
   if (path == 11 && ws && ws_bytes >= c1k7_h2_ws_bytes(d)) return conv_c1k7_h2(x, w, bias, y, d, ws, ws_bytes, s);
+  if (path == 12) return conv_fwd_k3(x, w, bias, y, d, ws, ws_bytes, s);
   if (!g_force_direct && c1k3_fwd_supported(d)) return conv_fwd_c1k3(x, w, bias, y, d, s);  // 1 -> K channels, 3^3: its own fp32 MFMA kernel
   if (!g_force_direct && mfma_fwd_supported(d)) return conv_fwd_mfma(x, w, bias, y, d, ws, ws_bytes, s);
   if (!g_force_direct && flat_1x1_supported(d)) return conv_fwd_1x1(x, w, bias, y, d, ws, ws_bytes, s);
@@ -292,6 +306,7 @@ int nc_conv_dgrad(const float* dy, const float* w, float* dx, int N, int C, int 
   if (path == 9) return conv_dgrad_s3(dy, nullptr, w, dx, d, ws, ws_bytes, s);
   if (path == 10) return conv_dgrad_p2d(dy, w, dx, d, ws, ws_bytes, s);
   if (path == 11 && ws && ws_bytes >= c1k7_h2_dgrad_ws_bytes(d)) return conv_c1k7_h2_dgrad(dy, w, dx, d, ws, ws_bytes, s);
+  if (path == 12) return conv_dgrad_k3(dy, w, dx, d, ws, ws_bytes, s);
   if (!g_force_direct && mfma_dgrad_supported(d)) return conv_dgrad_mfma(dy, w, dx, d, ws, ws_bytes, s);
   if (!g_force_direct && flat_1x1_supported(d)) return conv_dgrad_1x1(dy, w, dx, d, ws, ws_bytes, s);
   if (!g_force_direct && to1_mfma_supported(d)) return conv_dgrad_to1_mfma(dy, w, dx, d, ws, ws_bytes, s);

@@ -142,6 +142,16 @@ int conv_wgrad_p2d(const float* x, const float* dy, float* dw, const ConvDims& d
 int conv_fwd_sconv(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 int conv_dgrad_sconv(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 void sconv_set_cfg(int cfg);
+// conv2d_k3.hip: Conv2d(k 3, s 1, p 1) forward / data gradient on a 2-D spatial tile with a one-pixel halo (the 2-D generators' 3 x 3 layers)
+bool conv2d_k3_on();  // nc_set_conv2d_k3
+void conv2d_k3_set(int on);
+int conv2d_k3_set_cfg(int cfg);  // returns the previous pin
+int conv2d_k3_num_cfgs();
+bool conv2d_k3_fwd_supported(const ConvDims& d);
+bool conv2d_k3_dgrad_supported(const ConvDims& d);
+size_t conv2d_k3_ws_bytes(const ConvDims& d);
+int conv_fwd_k3(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
+int conv_dgrad_k3(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 void sconv_set_tune(int on);
 bool sconv_wgrad_supported(const ConvDims& d);
 size_t sconv_wgrad_ws_bytes(const ConvDims& d);

@@ -1,12 +1,14 @@
 """Host-side mirror of the reference's network zoo for the hot path (reference: models/networks.py).
 
 Same factory names, argument meaning, state-dict keys and error behaviour as the reference for the networks that
-BASELINE.json's north_star names -- `unet_deconv` (:478-538), `deep_linear_gen` (:893-917), `basic` / `n_layers`
-PatchGAN (:1009-1067) -- plus, as the first widening row, `unet_vanilla` (:540-608) and the `pixel`
+BASELINE.json's north_star names -- `unet_deconv` (:478-538, dimension 3 or 2), `deep_linear_gen` (:893-917), `basic` / `n_layers`
+PatchGAN (:1009-1067) -- plus, as the first widening row, `unet_vanilla` (:540-608, dimension 3 or 2) and the `pixel`
 discriminator (:1147-1179), which are built from the same kernels; `get_norm_layer` (:20-44: instance -- the hot path -- and batch),
 `GANLoss` (:252-319: lsgan -- the hot path -- vanilla, wgangp), `init_net` (:122-137), `get_scheduler` (:50-86), and the learned-PSF
 generators `linearkernel`, `linearkernel_double`, `linearkernel_LK31` (:840-871, :183-188), and the KernelGAN patch discriminator
-`kernelGAN` (:1113-1145, :243-244).  Every forward/backward runs HIP kernels from libnc_hip.so through neuroclear_amd.ops; there is no
+`kernelGAN` (:1113-1145, :243-244).  The two U-Nets built with dimension=2 (the reference's TestModel passes opt.image_dimension,
+test_model.py:41-45) run layer by layer in fp32 under every --precision: Conv2d / MaxPool2d / norm kernels the discriminators already use, and
+ConvTranspose2d(k 2, s 2) on csrc/convt2d.hip; the whole-network and 16-bit shortcuts stay 3-D only.  Every forward/backward runs HIP kernels from libnc_hip.so through neuroclear_amd.ops; there is no
 torch.nn.functional compute and no CPU fallback.  Networks outside the scope table (resnet, VGG, linearkernel_NC,
 fixed_kernel, ...) raise NotImplementedError exactly like an unknown name does in the reference (:196, :246).
 """
@@ -169,17 +171,22 @@ class Conv(nn.Module):
 
 
 class ConvTranspose(nn.Module):
-    """nn.ConvTranspose3d(C, K, kernel 2, stride 2): weight (C,K,2,2,2), bias (K,)."""
+    """nn.ConvTranspose3d / nn.ConvTranspose2d(C, K, kernel 2, stride 2) (networks.py:382-390): weight (C,K,2,2,2) or (C,K,2,2), bias (K,)."""
 
     def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, dimension=3):
         super().__init__()
-        if kernel_size != 2 or stride != 2 or dimension != 3:
-            raise NotImplementedError('only ConvTranspose3d(k=2, s=2) is on the hot path (networks.py:500,503)')
-        self.weight = nn.Parameter(torch.empty((in_channels, out_channels, 2, 2, 2)))
+        if dimension not in (2, 3):
+            raise Exception('Invalid image dimension.')
+        if kernel_size != 2 or stride != 2:
+            raise NotImplementedError('only ConvTranspose%dd(k=2, s=2) is on the hot path (networks.py:500,503)' % dimension)
+        self.dimension = dimension
+        self.weight = nn.Parameter(torch.empty((in_channels, out_channels) + (2,) * dimension))
         self.bias = nn.Parameter(torch.zeros(out_channels))
         init.kaiming_uniform_(self.weight, a=5 ** 0.5)
 
     def forward(self, x):
+        if x.dim() != self.dimension + 2:
+            raise ValueError('ConvTranspose%dd: expected a %d-D input, got %s' % (self.dimension, self.dimension + 2, tuple(x.shape)))
         return ops.conv_transpose_k2s2(x, self.weight, self.bias)
 
 
@@ -335,12 +342,13 @@ class triple_conv(nn.Module):
 class Unet_deconv(nn.Module):
     """networks.py:478-538.  Training (grad enabled) runs layer by layer through neuroclear_amd.ops; inference
     (torch.no_grad, as BaseModel.test does at base_model.py:101-109) takes the whole-network C entry point
-    nc_unet_deconv_fwd with the parameters packed in state-dict order."""
+    nc_unet_deconv_fwd with the parameters packed in state-dict order.  dimension=2 (test_model.py:41-45 with --image_dimension 2): the same
+    modules on NCHW tensors, always layer by layer and in fp32 -- the whole-network and 16-bit shortcuts are 3-D only."""
 
     def __init__(self, input_nc, output_nc, norm_layer=None, dimension=3):
         super().__init__()
-        if dimension != 3:
-            raise NotImplementedError('Unet_deconv: the hot path is the 3-D generator (apollo_model.py:66)')
+        conv(dimension)  # any dimension but 2 or 3 raises what conv() raises
+        self.dimension = dimension
         start_nc = input_nc * 64
         self.input_nc, self.output_nc = input_nc, output_nc
         self.double_conv1 = double_conv(input_nc, start_nc, 3, 1, 1, norm_layer, dimension)
@@ -352,7 +360,7 @@ class Unet_deconv(nn.Module):
         self.ex_conv1_1 = last_conv(start_nc * 2, start_nc, 3, 1, 1, norm_layer, dimension)
         self.one_by_one = Conv(start_nc, output_nc, 1, 1, 0, dimension=dimension)
         self.one_by_one_2 = Conv(output_nc, output_nc, 1, 1, 0, dimension=dimension)
-        self._fusable = _is_instance_norm(norm_layer) and input_nc == 1 and output_nc == 1
+        self._fusable = dimension == 3 and _is_instance_norm(norm_layer) and input_nc == 1 and output_nc == 1
 
     def _packed_params(self):
         """The 28 tensors in state-dict order as one flat blob: a zero-copy view of FlatAdam's buffer when the
@@ -375,8 +383,11 @@ class Unet_deconv(nn.Module):
         return y
 
     def forward(self, inputs):
+        if inputs.dim() != self.dimension + 2:
+            raise ValueError('Unet_deconv(dimension=%d): expected a %d-D input, got %s' % (self.dimension, self.dimension + 2, tuple(inputs.shape)))
         if any(s % 4 for s in inputs.shape[2:]):
-            raise ValueError('Unet_deconv: every edge must be a multiple of 4, got %s' % (tuple(inputs.shape[2:]),))
+            raise ValueError('Unet_deconv: every edge must be a multiple of 4, got %s%s' % (
+                tuple(inputs.shape[2:]), '' if self.dimension == 3 else ' (MaxPool2d floors, torch.cat at networks.py:526,531 would fail)'))
         if self._fusable and not torch.is_grad_enabled() and inputs.is_cuda:
             return self._forward_fused(inputs)
         if self._fusable and inputs.is_cuda and ops.conv_precision == 'fp32' and _FUSED_GEN:
@@ -398,12 +409,12 @@ class Unet_deconv(nn.Module):
 class Unet_vanilla(nn.Module):
     """networks.py:540-608: the four-level U-Net behind --netG unet_vanilla (double_conv on every level, 512-channel
     bottom, one 1x1 head + sigmoid).  Layer by layer through neuroclear_amd.ops in both modes (the whole-network C
-    entry point covers unet_deconv only)."""
+    entry point covers unet_deconv only), with dimension=3 or 2."""
 
     def __init__(self, input_nc, output_nc, norm_layer=None, dimension=3):
         super().__init__()
-        if dimension != 3:
-            raise NotImplementedError('Unet_vanilla: 3-D only (ConvTranspose3d k2 s2 is the upsampling kernel)')
+        conv(dimension)  # any dimension but 2 or 3 raises what conv() raises
+        self.dimension = dimension
         c = input_nc * 64
         dc = functools.partial(double_conv, kernel_size=3, stride=1, padding=1, norm_layer=norm_layer,
                                dimension=dimension)
@@ -418,9 +429,11 @@ class Unet_vanilla(nn.Module):
         self.one_by_one = Conv(c, output_nc, 1, 1, 0, dimension=dimension)
 
     def forward(self, inputs):
+        if inputs.dim() != self.dimension + 2:
+            raise ValueError('Unet_vanilla(dimension=%d): expected a %d-D input, got %s' % (self.dimension, self.dimension + 2, tuple(inputs.shape)))
         if any(s % 8 for s in inputs.shape[2:]):
-            raise ValueError('Unet_vanilla: every edge must be a multiple of 8, got %s (MaxPool3d floors, torch.cat '
-                             'at networks.py:594,598,602 would fail)' % (tuple(inputs.shape[2:]),))
+            raise ValueError('Unet_vanilla: every edge must be a multiple of 8, got %s (MaxPool%dd floors, torch.cat '
+                             'at networks.py:594,598,602 would fail)' % (tuple(inputs.shape[2:]), self.dimension))
         conv1 = self.double_conv1(inputs)
         conv2 = self.double_conv2(ops.maxpool2(conv1))
         conv3 = self.double_conv3(ops.maxpool2(conv2))

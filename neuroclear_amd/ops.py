@@ -465,8 +465,50 @@ class _ConvT(torch.autograd.Function):
         return dx, dw, db
 
 
+class _ConvT2d(torch.autograd.Function):
+    """nn.ConvTranspose2d(C, K, 2, 2) on nc_convT2d_k2s2_*: fp32 under every conv precision."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        _chk(x, w, b)
+        _f32(x, w, b)
+        if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[2:]) != (2, 2) or w.shape[0] != x.shape[1]:
+            raise _lib.NcError('convT2d_k2s2: only ConvTranspose2d(kernel 2, stride 2) with x [N,C,H,W] and w [C,K,2,2] is on the hot path')
+        N, C, H, W = x.shape
+        K = w.shape[1]
+        y = torch.empty((N, K, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+        check(lib().nc_convT2d_k2s2_fwd(_ptr(x), _ptr(w), _ptr(b), _ptr(y), N, C, H, W, K, _stream()), 'nc_convT2d_k2s2_fwd')
+        ctx.save_for_backward(x, w)
+        ctx.has_b = b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        N, C, H, W = x.shape
+        K = w.shape[1]
+        dx = dw = db = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
+            ws = workspace(lib().nc_convT2d_ws_bytes(N, C, H, W, K), x.device, 'ws_convT')
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            check(lib().nc_convT2d_k2s2_dgrad(_ptr(dy), _ptr(w), _ptr(dx), N, C, H, W, K, _ptr(ws), ws.numel(), _stream()),
+                  'nc_convT2d_k2s2_dgrad')
+        if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
+            dw = torch.empty_like(w)
+            db = torch.empty(K, dtype=torch.float32, device=x.device) if ctx.has_b else None
+            check(lib().nc_convT2d_k2s2_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), N, C, H, W, K, _ptr(ws), ws.numel(), _stream()),
+                  'nc_convT2d_k2s2_wgrad')
+        return dx, dw, db
+
+
 def conv_transpose_k2s2(x, w, b=None):
-    """nn.ConvTranspose3d(C, K, 2, 2) (models/networks.py:500,503)."""
+    """nn.ConvTranspose3d(C, K, 2, 2) / nn.ConvTranspose2d(C, K, 2, 2) (models/networks.py:382-390, 500, 503): a 5-D input takes the 3-D
+    kernels, a 4-D input the 2-D ones (csrc/convt2d.hip)."""
+    if x.dim() == 4:
+        return _ConvT2d.apply(x, w, b)
     return _ConvT.apply(x, w, b)
 
 
