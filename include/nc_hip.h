@@ -368,6 +368,19 @@ int nc_get_unet_lean(void);
  * and with NC_CONVT_H2=0 the forward packs of blocks 7 and 9 (a measured cell). */
 void nc_set_unet_wprep(int on);
 int nc_get_unet_wprep(void);
+/* The folded InstanceNorm backward of the two-term training step (default on; NC_IN_BWD_FOLD=0 at load time; process-wide, sampled once per
+ * call; nc_set_in_bwd_fold returns the previous setting).  Per two-term block of nc_unet_deconv_bwd: the sums pass keeps the loads of four
+ * iterations in flight (same element sequence and order of additions per thread), the apply pass takes the tensor's bound itself, the range
+ * guard's words are zeroed with the cells, and the bias sums and the guard's decision are one launch -- four launches instead of six.  Blocks 1
+ * and 3 (their output feeds a max-pool and a skip connection): nc_unet_deconv_train_fwd's pool kernel also writes one byte per pooled element,
+ * the winner's index, into `saved` (nc_unet_deconv_saved_floats counts it; `kept` bit 26), and the norm backward forms skip + pool gradient per
+ * element instead of reading the tensor nc_maxpool2_bwd_add would write.  Every stored value and every order of summation is unchanged: outputs
+ * and gradients are bit for bit the same.  Launches of before: the switch off at either call, a range guard that may switch kernels inside the
+ * call (nc_set_h2_guard(2); mode 1 in the per-layer entry points), three terms, the split kernels off, NC_S3_TRAIN_FUSE=0.
+ * nc_in_bwd_launches(which, reset): kernel launches so far of the two-term norm backward (which = 0) or of nc_maxpool2_bwd_add (1), for tests. */
+int nc_set_in_bwd_fold(int on);
+int nc_get_in_bwd_fold(void);
+int nc_in_bwd_launches(int which, int reset);
 /* Test exports.  nc_unet_wprep_layout: where block `block`'s (1 .. 9) prepared pack of `form` (0 forward, 1 data gradient) lies in `saved`
  * (byte offsets; cell_off: its weight cell; bound_off: the transposed convolution's bound of blocks 7 / 9, else 0).  nc_s3x_pack_h2_debug: the
  * PER-LAYER preparation of w[K][C][27] (cell_a / cell_b: device words, the two scale groups of a forward input) into wp / wcell.
@@ -606,6 +619,13 @@ int nc_maxpool2_h2_debug(const void* in, void* out, int N, int C, int ctot, int 
 int nc_h2_to_s3_if_debug(const void* xh, void* xs, int N, int C, long S, const unsigned* cells, const unsigned* guard, void* stream);
 int nc_instnorm_act_bwd_dbias_h2_debug(const float* dy, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
                                        float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, unsigned* guard, void* stream);
+/* nc_instnorm_act_bwd_dbias_h2_pool_debug: the same inside a whole-network scope (guard mode 1 only counts); gp / arg != NULL: the POOL form --
+ * dy is the skip gradient (sample stride dy_stride floats), gp the dense pooled gradient and arg the winner bytes [N][C][D/2 H/2 W/2] (even
+ * sizes).  nc_maxpool2_fwd_arg_debug: MaxPool3d(2) that also writes the winner bytes. */
+int nc_instnorm_act_bwd_dbias_h2_pool_debug(const float* dy, long dy_stride, const float* gp, const unsigned char* arg, const float* x, const float* mean,
+                                            const float* rstd, float slope, void* dxs, float* dbias, int N, int C, int D, int H, int W, void* ws,
+                                            size_t ws_bytes, unsigned* guard, void* stream);
+int nc_maxpool2_fwd_arg_debug(const float* x, float* y, unsigned char* arg, int NC, int D, int H, int W, void* stream);
 size_t nc_convT_k2s2_split_h2_ws_bytes(int N, int C, int D, int H, int W, int K);
 int nc_convT_k2s2_fwd_split_h2_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C,
                                      int D, int H, int W, int K, unsigned* out_cell, void* ws, size_t ws_bytes, void* stream);

@@ -220,6 +220,10 @@ struct SwitchScope { SwitchScope(); ~SwitchScope(); };
 struct ForceTwoTerm { ForceTwoTerm(); ~ForceTwoTerm(); int prev_terms, prev_depth; };
 int frozen_terms();  // -1: no scope open on this thread
 int frozen_guard();
+int frozen_fold();   // nc_set_in_bwd_fold as this call sees it
+int in_bwd_fold_raw();
+bool in_bwd_fold_on();
+void count_in_bwd_launches(int n, int which = 0);  // nc_in_bwd_launches (norm_act.hip)
 bool h2_guard_can_flip();  // mode 2, or mode 1 outside a whole-network call
 int operand_into(const ConvDims& d, const float* x, long xstride, void* xs, int N, int C, long S, int ctot, int c0, hipStream_t s);
 int act_operand(const ConvDims& d, const float* x, const float* mean, const float* rstd, float slope, float* y, long ystride, void* ys, int N, int C,
@@ -329,6 +333,34 @@ __device__ __forceinline__ bool guard_skip(const unsigned* guard, int want) {  /
 #else
 __device__ bool guard_skip(const unsigned* guard, int want);
 #endif
+#if defined(__HIPCC__)
+// The guard's decision (k_h2_guard_decide's comment in h2.hip has the arguments), for ONE thread: shared by that kernel and by the launch of the
+// norm backward that takes the decision beside its bias sums (norm_act.hip k_in_dbias_final_decide)
+__device__ __forceinline__ void h2_guard_decide_one(unsigned* ga, unsigned* gb, unsigned* prior, unsigned* flag, int can_flip,
+                                                    unsigned long long* stats, unsigned long long total_a) {
+  unsigned f = 0;
+  unsigned long long worst = 0;
+  int n = 0;
+  for (unsigned* g : {ga, gb}) {
+    if (!g) continue;
+    ++n;
+    const unsigned long long lo = g[kGuardLow], all = (g == ga && total_a) ? total_a - g[kGuardAll] : g[kGuardAll];
+    if (all && lo * kGuardShare > all) f = 1;
+    const unsigned long long ppm = all ? lo * 1000000ull / all : 0;
+    worst = ppm > worst ? ppm : worst;
+  }
+  unsigned F = f && can_flip ? 1u : 0u;
+  if (prior && prior[kGuardFlag]) F = 1u;
+  *flag = F;
+  if (prior) prior[kGuardFlag] = F;
+  if (stats && n) {
+    __hip_atomic_fetch_add(stats + 0, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (f) __hip_atomic_fetch_add(stats + (can_flip ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_fetch_max(stats + 3, worst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+#endif
+unsigned long long* h2_guard_stats_dev();  // the device pointer of the host-visible counters (allocated on first use, off the launch path)
 bool h2_guard_on();
 int h2_guard_mode();  // 0 off; 1 (default): in-call fallback in the per-layer entry points, whole-network calls count only; 2: in-call fallback everywhere
 void h2_guard_set(int on);
@@ -350,6 +382,13 @@ int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, in
 bool conv_bwd_pre_supported(int N, int C, int D, int H, int W, int K, int ks, bool want_dx, size_t ws_bytes);
 int conv_bwd_pre(const float* x, const void* xs, const float* w, float* dx, float* dw, int N, int C, int D, int H, int W, int K, int ks,
                  void* ws, size_t ws_bytes, void* stream, bool dy_guarded = false, const S3xPrepared* prep = nullptr);  // prep: of the data gradient
+// norm_act.hip: the H2 norm backward of a block whose output feeds a MaxPool3d(2) and a skip connection, without the pool's backward tensor
+// (nc_set_in_bwd_fold), and the pool forward that leaves the winner bytes it reads
+bool instnorm_bwd_h2_pool_supported(int N, int C, int D, int H, int W, unsigned* guard);
+int instnorm_act_bwd_dbias_h2_pool(const float* skip, long skip_stride, const float* gp, const unsigned char* arg, const float* x, const float* mean,
+                                   const float* rstd, float slope, void* dxs, float* dbias, int N, int C, int D, int H, int W, void* ws,
+                                   size_t ws_bytes, void* stream, unsigned* guard);
+int maxpool2_fwd_arg(const float* x, float* y, unsigned char* arg, int NC, int D, int H, int W, hipStream_t s);
 // norm_act.hip: InstanceNorm + activation backward with dx written in S3 form only
 bool instnorm_bwd_s3_supported(int N, int C, long S);
 int instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,

@@ -64,6 +64,11 @@ const UBlock kUB[10] = {{1, 64, 0},    {64, 64, 0},    {64, 128, 1},  {128, 128,
 // measured, and those two forward packs stay with the per-layer launches.
 std::atomic<int> g_unet_wprep{getenv("NC_UNET_WPREP") ? (atoi(getenv("NC_UNET_WPREP")) != 0) : 1};
 constexpr unsigned kKeptWPrep = 1u << 15;
+// THE WINNER BYTES of the two max-pools (nc_set_in_bwd_fold, default on; norm_act.hip PoolGrad): the forward's pool kernel also writes one byte per
+// pooled element, the index of its window's winner, into `saved` (UPlan::parg); `kept` bit 26 records that they exist.  The backward of blocks 1
+// and 3 then forms the gradient at the block's output -- skip half of the concat gradient + the pool's backward -- inside its InstanceNorm
+// backward, and nc_maxpool2_bwd_add with its 64- / 128-channel tensor is not launched.
+constexpr unsigned kKeptPoolArg = 1u << 26;
 // segment 2 (i - 1) + form of block i (form 0: forward, 1: data gradient); all 18 have their place in the region whichever of them a call prepares
 void wprep_segs(WPrepSeg (&sg)[18]) {
   for (int i = 1; i < 10; ++i) {
@@ -81,6 +86,7 @@ struct UPlan {
   size_t a1, cat1, p1, a2, cat2, p2, b1, b2, b3, e2a, e2b, e1, t1, raw[10], mean[10], rstd[10], saved;
   size_t xs3[10];      // S3 copy of block i's input (i >= 1), see `kept`
   size_t wprep;        // the prepared weights (w_prep.hip wprep_run's region), see kKeptWPrep
+  size_t parg[2];      // the winner bytes of pool 1 (behind block 1) and pool 2 (behind block 3), see kKeptPoolArg
   // backward scratch (floats)
   size_t G1, G2, G3, H1, H2, H3, Q1, Q2, s1, s2, T, grads;
   size_t conv_ws, in_ws, convT_ws;  // bytes
@@ -113,6 +119,8 @@ bool u_plan(UPlan& p, int N, int S0, int S1, int S2) {
     p.wprep = off;
     off += up64((wprep_bytes(sg, 18) + 3) / 4);
   }
+  p.parg[0] = off; off += up64((n * 64 * Sh + 3) / 4);
+  p.parg[1] = off; off += up64((n * 128 * Sq + 3) / 4);
   p.saved = off;
   off = 0;
   p.G1 = take(n * 64 * S); p.G2 = take(n * 64 * S); p.G3 = take(n * 128 * S);
@@ -346,12 +354,24 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   };
   NC_TRY(block(0, x, V + p.a1, (size_t)64 * S, 1, 64));
   NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128));
-  for (int n = 0; n < N; ++n)
-    NC_TRY(nc_maxpool2_fwd(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, 64, d0[0], d0[1], d0[2], stream));
+  const bool pool_arg = in_bwd_fold_on();  // (the pools also leave their winner bytes, see kKeptPoolArg)
+  if (pool_arg) kept_mask |= kKeptPoolArg;
+  for (int n = 0; n < N; ++n) {
+    if (pool_arg)
+      NC_TRY(maxpool2_fwd_arg(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, (unsigned char*)(V + p.parg[0]) + (size_t)n * 64 * Sh, 64,
+                              d0[0], d0[1], d0[2], hs));
+    else
+      NC_TRY(nc_maxpool2_fwd(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, 64, d0[0], d0[1], d0[2], stream));
+  }
   NC_TRY(block(2, V + p.p1, V + p.a2, (size_t)128 * Sh, 3, 128));
   NC_TRY(block(3, V + p.a2, V + p.cat2, (size_t)256 * Sh, 7, 256));
-  for (int n = 0; n < N; ++n)
-    NC_TRY(nc_maxpool2_fwd(V + p.cat2 + (size_t)n * 256 * Sh, V + p.p2 + (size_t)n * 128 * Sq, 128, d1[0], d1[1], d1[2], stream));
+  for (int n = 0; n < N; ++n) {
+    if (pool_arg)
+      NC_TRY(maxpool2_fwd_arg(V + p.cat2 + (size_t)n * 256 * Sh, V + p.p2 + (size_t)n * 128 * Sq, (unsigned char*)(V + p.parg[1]) + (size_t)n * 128 * Sq,
+                              128, d1[0], d1[1], d1[2], hs));
+    else
+      NC_TRY(nc_maxpool2_fwd(V + p.cat2 + (size_t)n * 256 * Sh, V + p.p2 + (size_t)n * 128 * Sq, 128, d1[0], d1[1], d1[2], stream));
+  }
   NC_TRY(block(4, V + p.p2, V + p.b1, (size_t)256 * Sq, 5, 256));
   NC_TRY(block(5, V + p.b1, V + p.b2, (size_t)256 * Sq, 6, 256));
   NC_TRY(block(6, V + p.b2, V + p.b3, (size_t)256 * Sq, -1, 0));
@@ -448,7 +468,9 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   }
   // backward of block i: g = gradient at the block's (post-ReLU) output, dense [N][K][S]; `in` = the block's input.
   // draw <- InstanceNorm/ReLU backward (+ the conv's bias gradient); dW <- wgrad; gin (nullable) <- dgrad
-  auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin, bool r1 = false) -> int {
+  // pool (block_bwd, blocks 1 and 3 under pool_folds): g is the skip half of the concat gradient (sample stride 2 K Sl), pool the dense pooled
+  // gradient; the winner bytes are in `saved`
+  auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin, bool r1 = false, const float* pool = nullptr) -> int {
     const UBlock& b = kUB[i];
     const int* d = p.d[b.lvl];
     const long Sl = p.S[b.lvl];
@@ -476,16 +498,31 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
     // conversion phase of the split-operand backward would put it): no fp32 tensor, no conversion pass
     if (fuse_bwd && i >= 1 && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, gin != nullptr, p.conv_ws) &&
         instnorm_bwd_s3_supported(N, b.K, Sl)) {
-      if (now_h2)  // (with the range guard's words of the dY operand: the norm backward counts, decides and -- flagged -- rewrites it as S3)
+      if (now_h2 && pool)
+        NC_TRY(instnorm_act_bwd_dbias_h2_pool(g, (long)2 * b.K * Sl, pool, (const unsigned char*)(V + p.parg[i == 1 ? 0 : 1]), V + p.raw[i], V + p.mean[i],
+                                              V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, d[0], d[1], d[2], iws, p.in_ws, stream,
+                                              conv_bwd_guard_words(cws, N, b.K, Sl)));
+      else if (now_h2)  // (with the range guard's words of the dY operand: the norm backward counts, decides and -- flagged -- rewrites it as S3)
         NC_TRY(instnorm_act_bwd_dbias_h2(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream,
                                          conv_bwd_guard_words(cws, N, b.K, Sl)));
       else
         NC_TRY(instnorm_act_bwd_dbias_s3(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream));
       return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, now_h2 && h2_guard_can_flip(), pd);
     }
+    if (pool) { set_error("unet_deconv_bwd: block %d left the path its pooled gradient was planned for", i); return NC_ERR_ARG; }
     NC_TRY(nc_instnorm_act_bwd_dbias(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, draw, DP + o.b[i], N, b.K, Sl, iws,
                                      p.in_ws, stream));
     return conv_bwd_keep(in, xs, draw, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream);
+  };
+  // Does block i (1 or 3) take the pool's backward into its InstanceNorm backward?  block_bwd's own conditions for the two-term path with its dY
+  // written by the norm backward, the winner bytes, the switch, and a range guard that cannot switch kernels inside this call.
+  auto pool_folds = [&](int i) -> bool {
+    const UBlock& b = kUB[i];
+    const int* d = p.d[b.lvl];
+    ConvDims cdk;
+    return (kept_mask & kKeptPoolArg) && fuse_bwd && make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk) &&
+           conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, true, p.conv_ws) &&
+           instnorm_bwd_h2_pool_supported(N, b.K, d[0], d[1], d[2], conv_bwd_guard_words(cws, N, b.K, p.S[b.lvl]));
   };
   // gradient of the second half of a concat buffer as a dense tensor
   auto upper_half = [&](const float* dcat, int Ctot, long Sl, const float** out) -> int {
@@ -529,17 +566,25 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   NC_TRY(block_bwd(5, G + p.Q1, V + p.b1, G + p.Q2, G + p.Q1));
   NC_TRY(block_bwd(4, G + p.Q1, V + p.p2, G + p.Q2, G + p.Q1));
   // conv2 = cat2[:, :128] feeds the pool AND the skip: gradient = pool backward + the first half of dcat2
-  for (int n = 0; n < N; ++n)
-    NC_TRY(nc_maxpool2_bwd_add(G + p.Q1 + (size_t)n * 128 * Sq, V + p.cat2 + (size_t)n * 256 * Sh, G + p.H3 + (size_t)n * 256 * Sh,
-                               G + p.H1 + (size_t)n * 128 * Sh, 128, d1[0], d1[1], d1[2], stream));
-  // double_conv2 (p1 -> a2 -> conv2)
-  NC_TRY(block_bwd(3, G + p.H1, V + p.a2, G + p.H2, G + p.H1));
+  if (pool_folds(3)) {  // (the gradient is formed inside block 3's norm backward: no 128-channel tensor)
+    NC_TRY(block_bwd(3, G + p.H3, V + p.a2, G + p.H2, G + p.H1, false, G + p.Q1));
+  } else {
+    for (int n = 0; n < N; ++n)
+      NC_TRY(nc_maxpool2_bwd_add(G + p.Q1 + (size_t)n * 128 * Sq, V + p.cat2 + (size_t)n * 256 * Sh, G + p.H3 + (size_t)n * 256 * Sh,
+                                 G + p.H1 + (size_t)n * 128 * Sh, 128, d1[0], d1[1], d1[2], stream));
+    // double_conv2 (p1 -> a2 -> conv2)
+    NC_TRY(block_bwd(3, G + p.H1, V + p.a2, G + p.H2, G + p.H1));
+  }
   NC_TRY(block_bwd(2, G + p.H1, V + p.p1, G + p.H2, G + p.H1));
-  for (int n = 0; n < N; ++n)
-    NC_TRY(nc_maxpool2_bwd_add(G + p.H1 + (size_t)n * 64 * Sh, V + p.cat1 + (size_t)n * 128 * S, G + p.G3 + (size_t)n * 128 * S,
-                               G + p.G1 + (size_t)n * 64 * S, 64, d0[0], d0[1], d0[2], stream));
-  // double_conv1 (x -> a1 -> conv1)
-  NC_TRY(block_bwd(1, G + p.G1, V + p.a1, G + p.G2, G + p.G1));
+  if (pool_folds(1)) {
+    NC_TRY(block_bwd(1, G + p.G3, V + p.a1, G + p.G2, G + p.G1, false, G + p.H1));
+  } else {
+    for (int n = 0; n < N; ++n)
+      NC_TRY(nc_maxpool2_bwd_add(G + p.H1 + (size_t)n * 64 * Sh, V + p.cat1 + (size_t)n * 128 * S, G + p.G3 + (size_t)n * 128 * S,
+                                 G + p.G1 + (size_t)n * 64 * S, 64, d0[0], d0[1], d0[2], stream));
+    // double_conv1 (x -> a1 -> conv1)
+    NC_TRY(block_bwd(1, G + p.G1, V + p.a1, G + p.G2, G + p.G1));
+  }
   return block_bwd(0, G + p.G1, x, G + p.G2, dx);
 }
 

@@ -126,26 +126,7 @@ __global__ void __launch_bounds__(256) k_split2h(const float* __restrict__ x, ui
 __global__ void k_h2_guard_decide(unsigned* ga, unsigned* gb, unsigned* prior, unsigned* flag, int can_flip, unsigned long long* stats,
                                   unsigned long long total_a) {
   if (threadIdx.x || blockIdx.x) return;
-  unsigned f = 0;
-  unsigned long long worst = 0;
-  int n = 0;
-  for (unsigned* g : {ga, gb}) {
-    if (!g) continue;
-    ++n;
-    const unsigned long long lo = g[kGuardLow], all = (g == ga && total_a) ? total_a - g[kGuardAll] : g[kGuardAll];
-    if (all && lo * kGuardShare > all) f = 1;
-    const unsigned long long ppm = all ? lo * 1000000ull / all : 0;
-    worst = ppm > worst ? ppm : worst;
-  }
-  unsigned F = f && can_flip ? 1u : 0u;
-  if (prior && prior[kGuardFlag]) F = 1u;
-  *flag = F;
-  if (prior) prior[kGuardFlag] = F;
-  if (stats && n) {
-    __hip_atomic_fetch_add(stats + 0, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (f) __hip_atomic_fetch_add(stats + (can_flip ? 1 : 2), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_fetch_max(stats + 3, worst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  h2_guard_decide_one(ga, gb, prior, flag, can_flip, stats, total_a);
 }
 
 // An H2 tensor back to fp32 values and on to the S3 form (exact: a0 + a1 has at most 23 significant bits and 2^-k is a power of two), into a
@@ -369,6 +350,7 @@ int h2_guard_read(unsigned long long* out4, int reset) {
   }
   return NC_OK;
 }
+unsigned long long* h2_guard_stats_dev() { return guard_stats_dev(); }
 int h2_guard_zero(unsigned* g, hipStream_t s, int nwords) {
   hipLaunchKernelGGL(k_set_cells, dim3(1), dim3(64), 0, s, g, nwords, 0u);
   return check_launch("h2_guard_zero");

@@ -72,6 +72,24 @@ int nc_instnorm_act_bwd_dbias_h2_debug(const float* dy, const float* w1, const f
   return instnorm_act_bwd_dbias_h2(dy, x, mean, rstd, slope, dxs, dbias, N, C, S, ws, ws_bytes, stream, guard);
 }
 
+// The same inside a whole-network scope (guard mode 1 counts a flagged tensor and switches nothing, as in nc_unet_deconv_bwd), and with gp / arg
+// != NULL the POOL form: dy is the skip gradient with sample stride dy_stride.  nc_maxpool2_fwd_arg_debug: the pool forward that leaves the
+// winner bytes.
+int nc_instnorm_act_bwd_dbias_h2_pool_debug(const float* dy, long dy_stride, const float* gp, const unsigned char* arg, const float* x, const float* mean,
+                                            const float* rstd, float slope, void* dxs, float* dbias, int N, int C, int D, int H, int W, void* ws,
+                                            size_t ws_bytes, unsigned* guard, void* stream) {
+  NetworkScope net_scope;
+  if (D < 1 || H < 1 || W < 1) { set_error("instnorm_act_bwd_dbias_h2_pool_debug: bad shape"); return NC_ERR_SHAPE; }
+  if (!gp && !arg) {
+    if (dy_stride != (long)C * D * H * W) { set_error("instnorm_act_bwd_dbias_h2_pool_debug: the plain form takes a dense gradient"); return NC_ERR_ARG; }
+    return instnorm_act_bwd_dbias_h2(dy, x, mean, rstd, slope, dxs, dbias, N, C, (long)D * H * W, ws, ws_bytes, stream, guard);
+  }
+  return instnorm_act_bwd_dbias_h2_pool(dy, dy_stride, gp, arg, x, mean, rstd, slope, dxs, dbias, N, C, D, H, W, ws, ws_bytes, stream, guard);
+}
+int nc_maxpool2_fwd_arg_debug(const float* x, float* y, unsigned char* arg, int NC, int D, int H, int W, void* stream) {
+  return maxpool2_fwd_arg(x, y, arg, NC, D, H, W, (hipStream_t)stream);
+}
+
 static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t nc_convT_k2s2_split_h2_ws_bytes(int N, int C, int D, int H, int W, int K) {
   if (!convT_s3x_supported(N, C, D, H, W, K)) return 0;

@@ -2,6 +2,7 @@
 // elementwise / reduction part of the hot path (reference models/networks.py:33-34,:422-423,:1042-1046,:491,:510).
 // All of these are pure streams: 16-byte loads where the instance length allows it, fp64 accumulation for every
 // statistic (1.26 M elements per instance at 108^3 -- fp32 sums would not hold the stated tolerance).
+#include <atomic>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -189,6 +190,22 @@ __global__ __launch_bounds__(256) void k_in_dbias_final(const double* __restrict
   __shared__ double out2[2];
   block_reduce2(s, zero, out2);
   if (threadIdx.x == 0) dbias[c] = (float)out2[0];
+}
+// k_in_dbias_final and, in workgroup 0, the range guard's decision about the tensor the apply pass wrote (k_h2_guard_decide's, counted only:
+// h2_guard_decide_one with can_flip = 0) -- one launch for the two; neither waits for the other
+__global__ __launch_bounds__(256) void k_in_dbias_final_decide(const double* __restrict__ rowpart, int N, int C, int nb, float* __restrict__ dbias,
+                                                               unsigned* guard, unsigned long long* stats, unsigned long long total) {
+  const int c = blockIdx.x;
+  double s = 0.0, zero = 0.0;
+  const int tot = N * nb;
+  for (int i = threadIdx.x; i < tot; i += 256) {
+    const int n = i / nb, b = i - n * nb;
+    s += rowpart[((long)n * C + c) * nb + b];
+  }
+  __shared__ double out2[2];
+  block_reduce2(s, zero, out2);
+  if (threadIdx.x == 0) dbias[c] = (float)out2[0];
+  if (blockIdx.x == 0 && threadIdx.x == 0) h2_guard_decide_one(guard, nullptr, nullptr, guard + kGuardFlag, 0, stats, total);
 }
 
 // ---- short instances (S <= kRowsMaxS: the 2-D PatchGAN layers, 12^2 .. 27^2 positions x tens of thousands of
@@ -488,30 +505,80 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_s3(const float* __restrict
 //   |dx| = r |g - mean(g) - xhat mean(g xhat)| <= r max|g| (2 + max|xhat|)      (|mean(g xhat)| <= rms(g) rms(xhat) <= max|g|)
 // bounds the tensor from above within a small factor -- fp16's exponent range has room for that (s3_common.hpp).
 // R1 (one sample: inst = channel): the K-channel gradient does not exist as a tensor
-template <bool R1 = false>
+// POOL (k_in_bwd_sums_h2, k_in_bwd_apply_h2): the block's output feeds a MaxPool3d(2) AND a skip connection, and the gradient at it is formed per
+// element instead of read from a tensor the pool's backward wrote: skip[i] + (the pooled gradient where i is its window's winner, else 0) -- the one
+// fp32 add k_maxpool2_bwd<true> stores.  The winner is a byte per pooled element left by the forward (k_maxpool2_fwd<true>, pool_winner's index).
+struct PoolGrad {
+  const float* gp;           // dense pooled gradient [N][C][Sp]
+  const unsigned char* arg;  // winner index 0..7 per pooled element, same layout
+  long skip_stride;          // floats between the samples of the skip gradient (`dy`)
+  long Sp;                   // Do * Ho * Wo
+  int C, H, W, Ho, Wo;
+};
+// voxel i of a D x H x W volume (i < 2^31) -> its pooled element and its place 0..7 inside the window
+__device__ __forceinline__ void pool_site(unsigned i, const PoolGrad& q, unsigned& w, unsigned& pos) {
+  const unsigned x = i % (unsigned)q.W, t = i / (unsigned)q.W, y = t % (unsigned)q.H, z = t / (unsigned)q.H;
+  w = ((z >> 1) * (unsigned)q.Ho + (y >> 1)) * (unsigned)q.Wo + (x >> 1);
+  pos = ((z & 1u) * 2u + (y & 1u)) * 2u + (x & 1u);
+}
+__device__ __forceinline__ float pool_grad_value(float skip, unsigned arg, unsigned pos, float gp) {
+  float g = skip + (arg == pos ? gp : 0.f);
+  asm("" : "+v"(g));  // (a rounded value of its own, as the tensor element it replaces was)
+  return g;
+}
+
+// U: the loads of U iterations are issued before the first of them is used (U = 1: one iteration at a time).  A thread's element sequence
+// i = b + tid + 256 k and the order of its additions do not depend on U: the sums have the same bits.  The loop with U = 1 keeps 32 waves x
+// 2 dwords in flight per CU, about a third of what the memory system needs to stream at full rate (k_in_stats gets there with 16-byte loads,
+// which would change which thread adds what).
+template <bool R1 = false, bool POOL = false, int U = 1>
 __global__ __launch_bounds__(256) void k_in_bwd_sums_h2(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, float slope, long S, int splits,
                                                         double* __restrict__ part, unsigned* __restrict__ gmax, unsigned* __restrict__ xmax,
-                                                        const float* __restrict__ w1 = nullptr) {
+                                                        const float* __restrict__ w1, PoolGrad pq) {
   const int inst = blockIdx.y, sp = blockIdx.x;
   long b, e;
   chunk_range(S, splits, sp, b, e);
   const float m = mean[inst], r = rstd[inst];
   const float* px = x + (long)inst * S;
-  const float* pg = R1 ? dy : dy + (long)inst * S;
+  const float* pg = R1 ? dy : POOL ? dy + (long)(inst / pq.C) * pq.skip_stride + (long)(inst % pq.C) * S : dy + (long)inst * S;
+  const float* pp = POOL ? pq.gp + (long)inst * pq.Sp : nullptr;
+  const unsigned char* pa = POOL ? pq.arg + (long)inst * pq.Sp : nullptr;
   const float w = R1 ? w1[inst] : 0.f;
   double s1 = 0.0, s2 = 0.0;
   unsigned gm = 0, xm = 0;
-  for (long i = b + threadIdx.x; i < e; i += 256) {
-    const float xh = (px[i] - m) * r;
-    const float gy = R1 ? r1_product(w, pg[i]) : pg[i];
+  auto load_g = [&](long i) -> float {
+    if constexpr (POOL) {
+      unsigned wi, pos;
+      pool_site((unsigned)i, pq, wi, pos);
+      return pool_grad_value(pg[i], pa[wi], pos, pp[wi]);
+    } else {
+      return pg[i];
+    }
+  };
+  auto add = [&](float xv, float gl) {
+    const float xh = (xv - m) * r;
+    const float gy = R1 ? r1_product(w, gl) : gl;
     const float g = xh > 0.f ? gy : gy * slope;
     s1 += (double)g;
     s2 = fma((double)g, (double)xh, s2);
     const unsigned gb = __float_as_uint(g) & 0x7fffffffu, xb = __float_as_uint(xh) & 0x7fffffffu;
     if (gb < 0x7f800000u && gb > gm) gm = gb;
     if (xb < 0x7f800000u && xb > xm) xm = xb;
+  };
+  long i = b + threadIdx.x;
+  if constexpr (U > 1) {
+    for (; i + (long)(U - 1) * 256 < e; i += (long)U * 256) {
+      float xv[U], gv[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) xv[k] = px[i + k * 256];
+#pragma unroll
+      for (int k = 0; k < U; ++k) gv[k] = load_g(i + k * 256);
+#pragma unroll
+      for (int k = 0; k < U; ++k) add(xv[k], gv[k]);
+    }
   }
+  for (; i < e; i += 256) add(px[i], load_g(i));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned q1 = (unsigned)__shfl_xor((int)gm, o), q2 = (unsigned)__shfl_xor((int)xm, o);
@@ -524,10 +591,9 @@ __global__ __launch_bounds__(256) void k_in_bwd_sums_h2(const float* __restrict_
   block_reduce2(s1, s2, part + ((long)inst * splits + sp) * 2);
 }
 
-__global__ __launch_bounds__(256) void k_in_bwd_bound(const float* __restrict__ rstd, const unsigned* __restrict__ gmax,
-                                                      const unsigned* __restrict__ xmax, int NC, unsigned* __restrict__ cell,
-                                                      unsigned* __restrict__ cell2, unsigned* __restrict__ guard) {
-  if (guard && threadIdx.x < 8) guard[threadIdx.x] = 0u;  // (the range guard's words of the tensor the apply pass is about to write)
+// this thread's share of the tensor's bound (see above), reduced over its wave: max over instances of rstd max|g| (2 + max|xhat|), as float bits
+__device__ __forceinline__ unsigned in_bwd_bound_wave(const float* __restrict__ rstd, const unsigned* __restrict__ gmax,
+                                                      const unsigned* __restrict__ xmax, int NC) {
   unsigned m = 0;
   for (int i = threadIdx.x; i < NC; i += 256) {
     const float bnd = rstd[i] * __uint_as_float(gmax[i]) * (2.f + __uint_as_float(xmax[i]));
@@ -539,25 +605,40 @@ __global__ __launch_bounds__(256) void k_in_bwd_bound(const float* __restrict__ 
     const unsigned q = (unsigned)__shfl_xor((int)m, o);
     m = q > m ? q : m;
   }
+  return m;
+}
+
+__global__ __launch_bounds__(256) void k_in_bwd_bound(const float* __restrict__ rstd, const unsigned* __restrict__ gmax,
+                                                      const unsigned* __restrict__ xmax, int NC, unsigned* __restrict__ cell,
+                                                      unsigned* __restrict__ cell2, unsigned* __restrict__ guard) {
+  if (guard && threadIdx.x < 8) guard[threadIdx.x] = 0u;  // (the range guard's words of the tensor the apply pass is about to write)
+  const unsigned m = in_bwd_bound_wave(rstd, gmax, xmax, NC);
   if ((threadIdx.x & 63) == 0 && m) {
     atomicMax(cell, m);
     atomicMax(cell2, m);
   }
 }
 
-__global__ void k_zero_u32(unsigned* p, int n) {
+// q (nullable): nq <= 256 more words somewhere else (the folded norm backward: the range guard's words)
+__global__ void k_zero_u32(unsigned* p, int n, unsigned* q, int nq) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
+  if (q && blockIdx.x == 0 && (int)threadIdx.x < nq) q[threadIdx.x] = 0u;
 }
 
-template <bool R1 = false>
+// FOLD: no k_in_bwd_bound launch in front -- every workgroup takes the tensor's bound itself from rstd / gmax / xmax (a maximum over at most a few
+// hundred words that sit in L2: the same bits in every workgroup, whatever the order), and workgroup (0, 0) stores it in the two cells for the
+// convolution kernels behind this pass.  Nothing waits for another workgroup.
+template <bool R1 = false, bool POOL = false, bool FOLD = false>
 __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict__ dy, const float* __restrict__ x,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          float slope, long S, int splits, const double* __restrict__ part,
                                                          uint4* __restrict__ dxs, int cblocks, double* __restrict__ rowpart,
-                                                         const unsigned* __restrict__ cell, unsigned* __restrict__ guard,
-                                                         const float* __restrict__ w1 = nullptr) {
+                                                         const unsigned* cell, unsigned* __restrict__ guard,
+                                                         const float* __restrict__ w1, PoolGrad pq, const unsigned* gmax, const unsigned* xmax,
+                                                         int NC, unsigned* cells_out) {
   __shared__ float sm[2][8];
   __shared__ double red[8][4];
+  __shared__ unsigned bmax[4];
   const long ncb = blockIdx.y;
   if (threadIdx.x < 8) {
     const long inst = ncb * 8 + threadIdx.x;
@@ -569,15 +650,30 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict
     sm[0][threadIdx.x] = (float)(s1 / (double)S);
     sm[1][threadIdx.x] = (float)(s2 / (double)S);
   }
+  if constexpr (FOLD) {
+    const unsigned bw = in_bwd_bound_wave(rstd, gmax, xmax, NC);
+    if ((threadIdx.x & 63) == 0) bmax[threadIdx.x >> 6] = bw;
+  }
   __syncthreads();
-  const unsigned cbits = *cell;
+  unsigned cbits_;
+  if constexpr (FOLD) {
+    const unsigned b01 = bmax[0] > bmax[1] ? bmax[0] : bmax[1], b23 = bmax[2] > bmax[3] ? bmax[2] : bmax[3];
+    cbits_ = b01 > b23 ? b01 : b23;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { cells_out[0] = cbits_; cells_out[1] = cbits_; }
+  } else {
+    cbits_ = *cell;
+  }
+  const unsigned cbits = cbits_;
   const float sc = h2_scale(cbits);
   unsigned n_zero = 0, n_low = 0;  // (wave-uniform: every lane counts the same chunks)
   float m[8], r[8], m1[8], m2[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) { m[j] = mean[ncb * 8 + j]; r[j] = rstd[ncb * 8 + j]; m1[j] = sm[0][j]; m2[j] = sm[1][j]; }
   const float* px = x + ncb * 8 * S;
-  const float* pg = R1 ? dy : dy + ncb * 8 * S;
+  // (POOL: the 8 channels of a block lie in one sample, C % 8 == 0)
+  const float* pg = R1 ? dy : POOL ? dy + (ncb * 8 / pq.C) * pq.skip_stride + (ncb * 8 % pq.C) * S : dy + ncb * 8 * S;
+  const float* pp = POOL ? pq.gp + ncb * 8 * pq.Sp : nullptr;
+  const unsigned char* pa = POOL ? pq.arg + ncb * 8 * pq.Sp : nullptr;
   float wj[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) wj[j] = R1 ? w1[ncb * 8 + j] : 0.f;
@@ -588,9 +684,18 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict
     unsigned short e[8][3];
     unsigned mx = 0;
     const float sv = R1 ? pg[v] : 0.f;
+    unsigned wi = 0, pos = 0;
+    if constexpr (POOL) pool_site((unsigned)v, pq, wi, pos);
+    float gl[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float t = in_bwd_value(px[j * S + v], R1 ? r1_product(wj[j], sv) : pg[j * S + v], m[j], r[j], m1[j], m2[j], slope);
+      if constexpr (R1) gl[j] = r1_product(wj[j], sv);
+      else if constexpr (POOL) gl[j] = pool_grad_value(pg[j * S + v], pa[j * pq.Sp + wi], pos, pp[j * pq.Sp + wi]);
+      else gl[j] = pg[j * S + v];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float t = in_bwd_value(px[j * S + v], gl[j], m[j], r[j], m1[j], m2[j], slope);
       rs[j] += (double)t;
       asm("" : "+v"(t));
       const unsigned b = __float_as_uint(t) & 0x7fffffffu;
@@ -677,21 +782,35 @@ __global__ void k_sigmoid_bwd(const float* __restrict__ dy, const float* __restr
 
 // MaxPool(2), floor mode.  H2 = 1 turns it into a 2-D pool is NOT needed: the reference only pools 3-D volumes
 // in Unet_deconv; D may still be 1 for a 2-D U-Net (pool window 1x2x2).
-__global__ void k_maxpool2_fwd(const float* __restrict__ x, float* __restrict__ y, int NC, int D, int H, int W, int Do,
-                               int Ho, int Wo, int wd) {
+// The window's winner, one definition for the forward (which may record it) and the backward (which recomputes it): the first element in
+// (a, b, c) order that is greater than every one before it, a NaN taking over from anything.  Returns its index (a * 2 + b) * 2 + c.
+__device__ __forceinline__ int pool_winner(const float* __restrict__ p, int od, int oh, int ow, int H, int W, int wd, float& best) {
+  best = -INFINITY;
+  int arg = 0;
+  for (int a = 0; a < wd; ++a)
+    for (int b = 0; b < 2; ++b)
+      for (int c = 0; c < 2; ++c) {
+        const float v = p[((long)(od * wd + a) * H + (oh * 2 + b)) * W + ow * 2 + c];
+        if (v > best || v != v) {
+          best = v;
+          arg = (a * 2 + b) * 2 + c;
+        }
+      }
+  return arg;
+}
+
+// ARG: also one byte per pooled element, the winner's index (read by the POOL form of the norm backward instead of the activation)
+template <bool ARG>
+__global__ void k_maxpool2_fwd(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ arg, int NC, int D, int H, int W,
+                               int Do, int Ho, int Wo, int wd) {
   const long total = (long)NC * Do * Ho * Wo;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int ow = (int)(i % Wo), oh = (int)((i / Wo) % Ho), od = (int)((i / ((long)Wo * Ho)) % Do);
     const long nc = i / ((long)Wo * Ho * Do);
-    const float* p = x + nc * D * H * W;
-    float best = -INFINITY;
-    for (int a = 0; a < wd; ++a)
-      for (int b = 0; b < 2; ++b)
-        for (int c = 0; c < 2; ++c) {
-          const float v = p[((long)(od * wd + a) * H + (oh * 2 + b)) * W + ow * 2 + c];
-          if (v > best || v != v) best = v;
-        }
+    float best;
+    const int a = pool_winner(x + nc * D * H * W, od, oh, ow, H, W, wd, best);
     y[i] = best;
+    if (ARG) arg[i] = (unsigned char)a;
   }
 }
 
@@ -704,19 +823,9 @@ __global__ void k_maxpool2_bwd(const float* __restrict__ dy, const float* __rest
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int ow = (int)(i % Wo), oh = (int)((i / Wo) % Ho), od = (int)((i / ((long)Wo * Ho)) % Do);
     const long nc = i / ((long)Wo * Ho * Do);
-    const float* p = x + nc * D * H * W;
     float* q = dx + nc * D * H * W;
-    float best = -INFINITY;
-    int arg = 0;
-    for (int a = 0; a < wd; ++a)
-      for (int b = 0; b < 2; ++b)
-        for (int c = 0; c < 2; ++c) {
-          const float v = p[((long)(od * wd + a) * H + (oh * 2 + b)) * W + ow * 2 + c];
-          if (v > best || v != v) {
-            best = v;
-            arg = (a * 2 + b) * 2 + c;
-          }
-        }
+    float best;
+    const int arg = pool_winner(x + nc * D * H * W, od, oh, ow, H, W, wd, best);
     const float g = dy[i];
     for (int a = 0; a < wd; ++a)
       for (int b = 0; b < 2; ++b)
@@ -1041,8 +1150,13 @@ int instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean
 // dxs: an H2 tensor [N][C/8][2][S] with its cell at byte offset h2_cells_offset(N * C * S) (cells[0] = cells[1] = the bound) and two
 // arrays of N * C words of scratch behind the cells -- all inside the N * C * S * 6 bytes an S3 tensor of the same shape takes.
 // w1 != NULL (the rank-one form, N == 1): dy is ONE channel and the gradient at the norm's output is w1[c] * dy[v]
+// pool != NULL (the POOL form, see PoolGrad): dy is the skip gradient, the gradient at the norm's output is formed from it and the pooled one.
+// Folded (nc_set_in_bwd_fold, default on; not when the range guard may switch kernels inside this call -- then every launch is the parent's):
+// the sums pass keeps the loads of four iterations in flight, the bound is taken by the apply pass itself, the guard's words are zeroed with the
+// cells, and the bias sums and the guard's decision are one launch -- four launches per tensor instead of six.
 static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
-                           float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard) {
+                           float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard,
+                           const PoolGrad* pool = nullptr) {
   if (!dy || !x || !mean || !rstd || !dxs || !dbias) { set_error("instnorm_act_bwd_dbias_h2: null pointer"); return NC_ERR_ARG; }
   if (!instnorm_bwd_s3_supported(N, C, S)) { set_error("instnorm_act_bwd_dbias_h2: bad shape"); return NC_ERR_SHAPE; }
   const int NC = N * C;
@@ -1053,37 +1167,57 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
   unsigned* cells = (unsigned*)((char*)dxs + h2_cells_offset((size_t)NC * S));
   unsigned* gmax = cells + 64;
   unsigned* xmax = gmax + NC;
-  hipLaunchKernelGGL(k_zero_u32, dim3((unsigned)cdiv(64 + 2 * NC, 256)), dim3(256), 0, s, cells, 64 + 2 * NC);
-  const int splits = pick_splits(NC, S);
-  if (w1)
-    hipLaunchKernelGGL(k_in_bwd_sums_h2<true>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax, w1);
-  else
-    hipLaunchKernelGGL(k_in_bwd_sums_h2<false>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax,
-                       (const float*)nullptr);
-  hipLaunchKernelGGL(k_in_bwd_bound, dim3(1), dim3(256), 0, s, rstd, gmax, xmax, NC, cells, cells + 1, guard);
-  long bx = cdiv(S, 1024);
-  if (bx > 1024) bx = 1024;
-  double* rowpart = (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S));
   // Range guard (common.hpp): the cell is a bound from the tensor's own per-instance maxima, i.e. data-derived like a measured one -- a block
   // of channels or a region far below the rest loses bits the same way.  guard (nullable): the words conv_bwd_s3 reads (conv_bwd_guard_words);
   // the apply pass counts its low chunks, the decision is taken on the device, and a flagged tensor is written AGAIN by the S3 twin of the
   // apply pass (same values, three exact bf16 terms, over the H2 form: the buffer has the S3 capacity) for the three-term kernels
   unsigned* g = guard && h2_guard_on() ? guard : nullptr;
-  if (w1)
-    hipLaunchKernelGGL(k_in_bwd_apply_h2<true>, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                       (const double*)ws, (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g, w1);
-  else
-    hipLaunchKernelGGL(k_in_bwd_apply_h2<false>, dim3((unsigned)bx, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                       (const double*)ws, (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g, (const float*)nullptr);
+  // Inside a whole-network call mode 1 (default) COUNTS a flagged tensor (nc_h2_guard_stats [2]) and leaves the switch to the caller (the
+  // Python models go to the three-term form when they see it, models/base_model.py): the in-call fallback costs the training step ~65
+  // near-empty launches, 0.5 ms of 35, for an event InstanceNorm networks do not produce.  Mode 2: in-call fallback here too.
+  const bool flip = g && h2_guard_can_flip();
+  const bool fold = in_bwd_fold_on() && !flip;
+  if (pool && (!fold || w1)) { set_error("instnorm_act_bwd_dbias_h2: the pooled form needs the folded path"); return NC_ERR_ARG; }
+  const PoolGrad none{};
+  hipLaunchKernelGGL(k_zero_u32, dim3((unsigned)cdiv(64 + 2 * NC, 256)), dim3(256), 0, s, cells, 64 + 2 * NC, fold ? guard : (unsigned*)nullptr, 8);
+  const int splits = pick_splits(NC, S);
+  const dim3 gs(splits, NC);
+  constexpr int U = 4;
+#define NC_SUMS(R1_, POOL_, U_, pq_) \
+  hipLaunchKernelGGL((k_in_bwd_sums_h2<R1_, POOL_, U_>), gs, dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax, w1, pq_)
+  if (pool) NC_SUMS(false, true, U, *pool);
+  else if (fold && w1) NC_SUMS(true, false, U, none);
+  else if (fold) NC_SUMS(false, false, U, none);
+  else if (w1) NC_SUMS(true, false, 1, none);
+  else NC_SUMS(false, false, 1, none);
+#undef NC_SUMS
+  if (!fold) hipLaunchKernelGGL(k_in_bwd_bound, dim3(1), dim3(256), 0, s, rstd, gmax, xmax, NC, cells, cells + 1, guard);
+  long bx = cdiv(S, 1024);
+  if (bx > 1024) bx = 1024;
+  double* rowpart = (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S));
+  const dim3 ga((unsigned)bx, (unsigned)(NC / 8));
+#define NC_APPLY(R1_, POOL_, FOLD_, pq_)                                                                                                     \
+  hipLaunchKernelGGL((k_in_bwd_apply_h2<R1_, POOL_, FOLD_>), ga, dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (const double*)ws, \
+                     (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g, w1, pq_, (const unsigned*)gmax, (const unsigned*)xmax, NC, cells)
+  if (pool) NC_APPLY(false, true, true, *pool);
+  else if (fold && w1) NC_APPLY(true, false, true, none);
+  else if (fold) NC_APPLY(false, false, true, none);
+  else if (w1) NC_APPLY(true, false, false, none);
+  else NC_APPLY(false, false, false, none);
+#undef NC_APPLY
+  // chunks: one per wave and loop iteration = (NC / 8) * sum over blocks of ceil(iterations): every 64-voxel group of every 8-channel block
+  const unsigned long long total = (unsigned long long)(NC / 8) * (unsigned long long)cdiv(S, 64);
+  if (fold) {
+    if (g) hipLaunchKernelGGL(k_in_dbias_final_decide, dim3(C), dim3(256), 0, s, (const double*)rowpart, N, C, (int)bx, dbias, g, h2_guard_stats_dev(), total);
+    else hipLaunchKernelGGL(k_in_dbias_final, dim3(C), dim3(256), 0, s, (const double*)rowpart, N, C, (int)bx, dbias);
+    count_in_bwd_launches(4);
+    return check_launch("instnorm_act_bwd_dbias_h2");
+  }
   hipLaunchKernelGGL(k_in_dbias_final, dim3(C), dim3(256), 0, s, (const double*)rowpart, N, C, (int)bx, dbias);
+  count_in_bwd_launches(5);
   if (g) {
-    // chunks: one per wave and loop iteration = (NC / 8) * sum over blocks of ceil(iterations): every 64-voxel group of every 8-channel block
-    const unsigned long long total = (unsigned long long)(NC / 8) * (unsigned long long)cdiv(S, 64);
-    // Inside a whole-network call mode 1 (default) COUNTS a flagged tensor (nc_h2_guard_stats [2]) and leaves the switch to the caller (the
-    // Python models go to the three-term form when they see it, models/base_model.py): the in-call fallback costs the training step ~65
-    // near-empty launches, 0.5 ms of 35, for an event InstanceNorm networks do not produce.  Mode 2: in-call fallback here too.
-    const bool flip = h2_guard_can_flip();
     if (int e = h2_guard_decide(g, nullptr, nullptr, g + kGuardFlag, flip, s, total)) return e;
+    count_in_bwd_launches(1);
     if (!flip) return check_launch("instnorm_act_bwd_dbias_h2");
     long bx3 = bx < 128 ? bx : 128;  // (usually leaves at once; no row partials: the bias gradient is the H2 pass's)
     if (w1)  // (the rewrite takes the gradient from the same source)
@@ -1092,9 +1226,42 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
     else
       hipLaunchKernelGGL(k_in_bwd_apply_s3<false>, dim3((unsigned)bx3, (unsigned)(NC / 8)), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
                          (const double*)ws, (uint4*)dxs, C / 8, (double*)nullptr, (const unsigned*)g, (const float*)nullptr);
+    count_in_bwd_launches(1);
   }
   return check_launch("instnorm_act_bwd_dbias_h2");
 }
+// The POOL form (PoolGrad): skip = the skip half of the concat gradient, sample stride skip_stride floats; gp / arg: the dense pooled gradient
+// and the forward's winner bytes [N][C][D/2 * H/2 * W/2].  false: take nc_maxpool2_bwd_add and the plain form.
+bool instnorm_bwd_h2_pool_supported(int N, int C, int D, int H, int W, unsigned* guard) {
+  const long S = (long)D * H * W;
+  return D >= 2 && H >= 2 && W >= 2 && !((D | H | W) & 1) && S < 0x7fffffffL && instnorm_bwd_s3_supported(N, C, S) && in_bwd_fold_on() &&
+         !(guard && h2_guard_on() && h2_guard_can_flip());
+}
+int instnorm_act_bwd_dbias_h2_pool(const float* skip, long skip_stride, const float* gp, const unsigned char* arg, const float* x, const float* mean,
+                                   const float* rstd, float slope, void* dxs, float* dbias, int N, int C, int D, int H, int W, void* ws,
+                                   size_t ws_bytes, void* stream, unsigned* guard) {
+  if (!gp || !arg) { set_error("instnorm_act_bwd_dbias_h2_pool: null pointer"); return NC_ERR_ARG; }
+  if (!instnorm_bwd_h2_pool_supported(N, C, D, H, W, guard) || skip_stride < (long)C * D * H * W) {
+    set_error("instnorm_act_bwd_dbias_h2_pool: shape or switches not covered");
+    return NC_ERR_SHAPE;
+  }
+  const PoolGrad pq{gp, arg, skip_stride, (long)(D / 2) * (H / 2) * (W / 2), C, H, W, H / 2, W / 2};
+  return in_bwd_dbias_h2(skip, nullptr, x, mean, rstd, slope, dxs, dbias, N, C, (long)D * H * W, ws, ws_bytes, stream, guard, &pq);
+}
+// MaxPool3d(2) forward of NC even-sized volumes that also leaves the winner bytes
+int maxpool2_fwd_arg(const float* x, float* y, unsigned char* arg, int NC, int D, int H, int W, hipStream_t s) {
+  if (!x || !y || !arg) { set_error("maxpool2_fwd_arg: null pointer"); return NC_ERR_ARG; }
+  if (NC < 1 || D < 2 || H < 2 || W < 2 || ((D | H | W) & 1)) { set_error("maxpool2_fwd_arg: bad shape"); return NC_ERR_SHAPE; }
+  const long total = (long)NC * (D / 2) * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(k_maxpool2_fwd<true>, dim3(flat_grid(total)), dim3(256), 0, s, x, y, arg, NC, D, H, W, D / 2, H / 2, W / 2, 2);
+  return check_launch("maxpool2_fwd_arg");
+}
+// nc_set_in_bwd_fold: process-wide; inside a call the value sampled when the call began (SwitchScope)
+static std::atomic<int> g_in_bwd_fold{getenv("NC_IN_BWD_FOLD") ? (atoi(getenv("NC_IN_BWD_FOLD")) != 0) : 1};
+int in_bwd_fold_raw() { return g_in_bwd_fold.load(std::memory_order_relaxed); }
+bool in_bwd_fold_on() { const int f = frozen_fold(); return (f >= 0 ? f : in_bwd_fold_raw()) != 0; }
+static std::atomic<int> g_in_bwd_launches[2];  // [0] the two-term norm backward, [1] nc_maxpool2_bwd_add
+void count_in_bwd_launches(int n, int which) { g_in_bwd_launches[which].fetch_add(n, std::memory_order_relaxed); }
 int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
                               float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard) {
   return in_bwd_dbias_h2(dy, nullptr, x, mean, rstd, slope, dxs, dbias, N, C, S, ws, ws_bytes, stream, guard);
@@ -1116,6 +1283,13 @@ extern "C" {
 int nc_instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs, float* dbias,
                                  int N, int C, long S, void* ws, size_t ws_bytes, void* stream) {
   return instnorm_act_bwd_dbias_s3(dy, x, mean, rstd, slope, dxs, dbias, N, C, S, ws, ws_bytes, stream);
+}
+
+int nc_set_in_bwd_fold(int on) { return g_in_bwd_fold.exchange(on != 0, std::memory_order_relaxed); }
+int nc_get_in_bwd_fold(void) { return in_bwd_fold_raw(); }
+int nc_in_bwd_launches(int which, int reset) {
+  std::atomic<int>& c = g_in_bwd_launches[which == 1 ? 1 : 0];
+  return reset ? c.exchange(0, std::memory_order_relaxed) : c.load(std::memory_order_relaxed);
 }
 
 int nc_leaky_relu_fwd(const float* x, float slope, float* y, long n, void* stream) {
@@ -1145,7 +1319,8 @@ int nc_maxpool2_fwd(const float* x, float* y, int NC, int D, int H, int W, void*
   const int Do = D / wd, Ho = H / 2, Wo = W / 2;
   if (NC < 1 || Do < 1 || Ho < 1 || Wo < 1) { set_error("maxpool2_fwd: bad shape"); return NC_ERR_SHAPE; }
   const long total = (long)NC * Do * Ho * Wo;
-  hipLaunchKernelGGL(k_maxpool2_fwd, dim3(flat_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, NC, D, H, W, Do, Ho, Wo, wd);
+  hipLaunchKernelGGL(k_maxpool2_fwd<false>, dim3(flat_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, (unsigned char*)nullptr, NC, D, H, W,
+                     Do, Ho, Wo, wd);
   return check_launch("maxpool2_fwd");
 }
 
@@ -1178,6 +1353,7 @@ int nc_maxpool2_bwd_add(const float* dy, const float* x, const float* skip, floa
   const long total = (long)NC * Do * Ho * Wo;
   hipLaunchKernelGGL(k_maxpool2_bwd<true>, dim3(flat_grid(total)), dim3(256), 0, (hipStream_t)stream, dy, x, skip, dx, NC, D, H, W,
                      Do, Ho, Wo, wd);
+  count_in_bwd_launches(1, 1);
   return check_launch("maxpool2_bwd_add");
 }
 
