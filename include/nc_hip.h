@@ -381,6 +381,15 @@ int nc_get_unet_wprep(void);
 int nc_set_in_bwd_fold(int on);
 int nc_get_in_bwd_fold(void);
 int nc_in_bwd_launches(int which, int reset);
+/* The streaming passes of the training step nearer to the memory system's rate (default on; process-wide, sampled once per call;
+ * nc_set_stream_passes returns the previous setting).  On: the folded rank-one form of the two-term norm backward (the last block) issues the
+ * nine loads of an apply iteration before it uses the first and keeps eight iterations in flight in its sums pass; the fp32 norm backward on
+ * long instances keeps eight iterations in flight in its sums pass (nc_instnorm_act_bwd, _dbias, _c8, _dbias_s3), and its apply pass
+ * (nc_instnorm_act_bwd, _dbias) four, the first of them issued before the partial sums are added up; the batched weight preparation takes its
+ * cells row by row without a division per element and writes whole 16-byte fragments, both terms from one read of the eight weights.  Off: the
+ * kernels as they were.  Every stored value and every order of summation is the same either way: outputs and gradients are bit for bit equal. */
+int nc_set_stream_passes(int on);
+int nc_get_stream_passes(void);
 /* Test exports.  nc_unet_wprep_layout: where block `block`'s (1 .. 9) prepared pack of `form` (0 forward, 1 data gradient) lies in `saved`
  * (byte offsets; cell_off: its weight cell; bound_off: the transposed convolution's bound of blocks 7 / 9, else 0).  nc_s3x_pack_h2_debug: the
  * PER-LAYER preparation of w[K][C][27] (cell_a / cell_b: device words, the two scale groups of a forward input) into wp / wcell.

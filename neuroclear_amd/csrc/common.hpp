@@ -223,6 +223,9 @@ int frozen_guard();
 int frozen_fold();   // nc_set_in_bwd_fold as this call sees it
 int in_bwd_fold_raw();
 bool in_bwd_fold_on();
+int frozen_stream();  // nc_set_stream_passes as this call sees it
+int stream_passes_raw();
+bool stream_passes_on();
 void count_in_bwd_launches(int n, int which = 0);  // nc_in_bwd_launches (norm_act.hip)
 bool h2_guard_can_flip();  // mode 2, or mode 1 outside a whole-network call
 int operand_into(const ConvDims& d, const float* x, long xstride, void* xs, int N, int C, long S, int ctot, int c0, hipStream_t s);

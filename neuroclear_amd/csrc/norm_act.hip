@@ -114,6 +114,9 @@ __global__ __launch_bounds__(256) void k_in_act_fwd(const float* __restrict__ x,
 }
 
 // pass 1 of the backward: s1 = sum(g), s2 = sum(g * xhat), g = dy * act'(xhat)
+// U (nc_set_stream_passes: 8, off: 1): the loads of U iterations are issued before the first of them is used, as in k_in_bwd_sums_h2 below.  A
+// thread's element sequence i = b + tid + 256 k and the order of its additions do not depend on U: the sums have the same bits.
+template <int U = 1>
 __global__ __launch_bounds__(256) void k_in_bwd_sums(const float* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      float slope, long S, int splits, double* __restrict__ part) {
@@ -124,12 +127,25 @@ __global__ __launch_bounds__(256) void k_in_bwd_sums(const float* __restrict__ d
   const float* px = x + (long)inst * S;
   const float* pg = dy + (long)inst * S;
   double s1 = 0.0, s2 = 0.0;
-  for (long i = b + threadIdx.x; i < e; i += 256) {
-    const float xh = (px[i] - m) * r;
-    const float g = xh > 0.f ? pg[i] : pg[i] * slope;
+  auto add = [&](float xv, float gy) {
+    const float xh = (xv - m) * r;
+    const float g = xh > 0.f ? gy : gy * slope;
     s1 += (double)g;
     s2 = fma((double)g, (double)xh, s2);
+  };
+  long i = b + threadIdx.x;
+  if constexpr (U > 1) {
+    for (; i + (long)(U - 1) * 256 < e; i += (long)U * 256) {
+      float xv[U], gv[U];
+#pragma unroll
+      for (int k = 0; k < U; ++k) xv[k] = px[i + k * 256];
+#pragma unroll
+      for (int k = 0; k < U; ++k) gv[k] = pg[i + k * 256];
+#pragma unroll
+      for (int k = 0; k < U; ++k) add(xv[k], gv[k]);
+    }
   }
+  for (; i < e; i += 256) add(px[i], pg[i]);
   block_reduce2(s1, s2, part + ((long)inst * splits + sp) * 2);
 }
 
@@ -144,24 +160,71 @@ __device__ __forceinline__ float in_bwd_value(float xv, float gy, float m, float
   return r * ((g - m1) - p);
 }
 
+// U: as in k_in_bwd_sums -- the same i = blockIdx.x * 256 + tid + k * gridDim.x * 256 per thread, the same order of the fp64 additions, plain tail.
+// A workgroup of this grid lives for about five iterations, so what it does before the first load counts: the loads of the first round are
+// issued BEFORE the partial sums are added up (they do not depend on them), and the partials are loaded eight at a time: the means are ready
+// when the data arrives.
+template <int U = 1>
 __global__ __launch_bounds__(256) void k_in_bwd_apply(const float* __restrict__ dy, const float* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       float slope, long S, int splits,
                                                       const double* __restrict__ part, float* __restrict__ dx,
                                                       double* __restrict__ rowpart) {
   const int inst = blockIdx.y;
+  const float* px = x + (long)inst * S;
+  const float* pg = dy + (long)inst * S;
+  float* o = dx + (long)inst * S;
+  const long st = (long)gridDim.x * 256;
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  float xv[U], gv[U];
+  bool round = U > 1 && i + (U - 1) * st < S;
+  if constexpr (U > 1) {
+    if (round) {
+#pragma unroll
+      for (int k = 0; k < U; ++k) xv[k] = px[i + k * st];
+#pragma unroll
+      for (int k = 0; k < U; ++k) gv[k] = pg[i + k * st];
+    }
+  }
   double s1 = 0.0, s2 = 0.0;
-  for (int k = 0; k < splits; ++k) {
+  int k0 = 0;
+  if constexpr (U > 1) {  // (eight partials per round of loads instead of one load waited for per partial; added in the same order)
+    for (; k0 + 8 <= splits; k0 += 8) {
+      double a[8], b[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { a[j] = part[((long)inst * splits + k0 + j) * 2]; b[j] = part[((long)inst * splits + k0 + j) * 2 + 1]; }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { s1 += a[j]; s2 += b[j]; }
+    }
+  }
+  for (int k = k0; k < splits; ++k) {
     s1 += part[((long)inst * splits + k) * 2];
     s2 += part[((long)inst * splits + k) * 2 + 1];
   }
   const float m1 = (float)(s1 / (double)S), m2 = (float)(s2 / (double)S);
   const float m = mean[inst], r = rstd[inst];
-  const float* px = x + (long)inst * S;
-  const float* pg = dy + (long)inst * S;
-  float* o = dx + (long)inst * S;
   double rs = 0.0;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < S; i += (long)gridDim.x * 256) {
+  if constexpr (U > 1) {
+    // (a SECOND round needs more than 2 U iterations per thread, i.e. the grid capped at 1024 workgroups and S >= 8 x 262 144 voxels: the step's
+    // 108^3 has 4.8 iterations, one round and the tail; tests/test_gpu_stream_passes.py runs the refill at 2.2 M voxels)
+    while (round) {
+#pragma unroll
+      for (int k = 0; k < U; ++k) {
+        const float v = in_bwd_value(xv[k], gv[k], m, r, m1, m2, slope);
+        o[i + k * st] = v;
+        rs += (double)v;
+      }
+      i += U * st;
+      round = i + (U - 1) * st < S;
+      if (round) {
+#pragma unroll
+        for (int k = 0; k < U; ++k) xv[k] = px[i + k * st];
+#pragma unroll
+        for (int k = 0; k < U; ++k) gv[k] = pg[i + k * st];
+      }
+    }
+  }
+  for (; i < S; i += st) {
     const float v = in_bwd_value(px[i], pg[i], m, r, m1, m2, slope);
     o[i] = v;
     rs += (double)v;
@@ -628,7 +691,10 @@ __global__ void k_zero_u32(unsigned* p, int n, unsigned* q, int nq) {
 // FOLD: no k_in_bwd_bound launch in front -- every workgroup takes the tensor's bound itself from rstd / gmax / xmax (a maximum over at most a few
 // hundred words that sit in L2: the same bits in every workgroup, whatever the order), and workgroup (0, 0) stores it in the two cells for the
 // convolution kernels behind this pass.  Nothing waits for another workgroup.
-template <bool R1 = false, bool POOL = false, bool FOLD = false>
+// STAGE (nc_set_stream_passes, the folded rank-one form): every load of an iteration -- the eight raw channels and the one-channel gradient -- is
+// issued before the first of them is used.  Left to itself the compiler schedules that instance's loop as nine loads each waited for in turn (the
+// unfolded instance of the same source and the plain forms get all of them in flight).  Same values, same additions in the same order.
+template <bool R1 = false, bool POOL = false, bool FOLD = false, bool STAGE = false>
 __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict__ dy, const float* __restrict__ x,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          float slope, long S, int splits, const double* __restrict__ part,
@@ -686,16 +752,29 @@ __global__ __launch_bounds__(256) void k_in_bwd_apply_h2(const float* __restrict
     const float sv = R1 ? pg[v] : 0.f;
     unsigned wi = 0, pos = 0;
     if constexpr (POOL) pool_site((unsigned)v, pq, wi, pos);
-    float gl[8];
+    float gl[8], xv[8];
+    if constexpr (STAGE) {
+      static_assert(!STAGE || (R1 && !POOL), "the staged loop is the rank-one form's");
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if constexpr (R1) gl[j] = r1_product(wj[j], sv);
-      else if constexpr (POOL) gl[j] = pool_grad_value(pg[j * S + v], pa[j * pq.Sp + wi], pos, pp[j * pq.Sp + wi]);
-      else gl[j] = pg[j * S + v];
+      for (int j = 0; j < 8; ++j) xv[j] = px[j * S + v];
+      // One statement that needs all nine: no load can sink below it, one wait for the nine.  What the backend makes of it is a property of the
+      // compiler at hand (ROCm 7.2: nine global_load_dword, one s_waitcnt vmcnt(0), 71 VGPRs, no scratch): read this instance's
+      // disassembly again after a compiler upgrade.
+      float s0 = sv;
+      asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]), "+v"(xv[7]), "+v"(s0));
+#pragma unroll
+      for (int j = 0; j < 8; ++j) gl[j] = r1_product(wj[j], s0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if constexpr (R1) gl[j] = r1_product(wj[j], sv);
+        else if constexpr (POOL) gl[j] = pool_grad_value(pg[j * S + v], pa[j * pq.Sp + wi], pos, pp[j * pq.Sp + wi]);
+        else gl[j] = pg[j * S + v];
+      }
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      float t = in_bwd_value(px[j * S + v], gl[j], m[j], r[j], m1[j], m2[j], slope);
+      float t = in_bwd_value(STAGE ? xv[j] : px[j * S + v], gl[j], m[j], r[j], m1[j], m2[j], slope);
       rs[j] += (double)t;
       asm("" : "+v"(t));
       const unsigned b = __float_as_uint(t) & 0x7fffffffu;
@@ -835,6 +914,20 @@ __global__ void k_maxpool2_bwd(const float* __restrict__ dy, const float* __rest
           q[o] = SKIP ? skip[nc * D * H * W + o] + v : v;
         }
   }
+}
+
+// the plain sums / apply pass with the prefetch of nc_set_stream_passes (off: one iteration at a time, the kernels as they were)
+static void launch_in_bwd_sums(const float* dy, const float* x, const float* mean, const float* rstd, float slope, long S, int splits, int NC,
+                               double* part, hipStream_t s) {
+  if (stream_passes_on()) hipLaunchKernelGGL(k_in_bwd_sums<8>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part);
+  else hipLaunchKernelGGL(k_in_bwd_sums<1>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part);
+}
+static void launch_in_bwd_apply(const float* dy, const float* x, const float* mean, const float* rstd, float slope, long S, int splits, int NC,
+                                long bx, const double* part, float* dx, double* rowpart, hipStream_t s) {
+  if (stream_passes_on())
+    hipLaunchKernelGGL(k_in_bwd_apply<4>, dim3((unsigned)bx, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part, dx, rowpart);
+  else
+    hipLaunchKernelGGL(k_in_bwd_apply<1>, dim3((unsigned)bx, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part, dx, rowpart);
 }
 
 static unsigned flat_grid(long n, int per_block = 256) {
@@ -1028,6 +1121,7 @@ int nc_instnorm_fwd(const float* x, float eps, float slope, float* mean, float* 
 
 int nc_instnorm_act_bwd(const float* dy, const float* x, const float* mean, const float* rstd, float slope, float* dx,
                         int NC, long S, void* ws, size_t ws_bytes, void* stream) {
+  SwitchScope switches_;  // (both passes see one value of nc_set_stream_passes)
   if (!dy || !x || !mean || !rstd || !dx) { set_error("instnorm_act_bwd: null pointer"); return NC_ERR_ARG; }
   if (NC >= 1 && S >= 1 && rows_path(S)) {
     launch_bwd_rows(dy, x, mean, rstd, slope, NC, S, dx, nullptr, (hipStream_t)stream);
@@ -1045,11 +1139,10 @@ int nc_instnorm_act_bwd(const float* dy, const float* x, const float* mean, cons
   if (!ws || ws_bytes < nc_instnorm_ws_bytes(NC, S)) { set_error("instnorm_act_bwd: workspace too small"); return NC_ERR_WS; }
   hipStream_t s = (hipStream_t)stream;
   const int splits = pick_splits(NC, S);
-  hipLaunchKernelGGL(k_in_bwd_sums, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws);
+  launch_in_bwd_sums(dy, x, mean, rstd, slope, S, splits, NC, (double*)ws, s);
   long bx = cdiv(S, 1024);
   if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(k_in_bwd_apply, dim3((unsigned)bx, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                     (const double*)ws, dx, (double*)nullptr);
+  launch_in_bwd_apply(dy, x, mean, rstd, slope, S, splits, NC, bx, (const double*)ws, dx, nullptr, s);
   return check_launch("instnorm_act_bwd");
 }
 
@@ -1061,6 +1154,7 @@ size_t nc_instnorm_bwd_dbias_ws_bytes(int NC, long S) {
 
 int nc_instnorm_act_bwd_dbias(const float* dy, const float* x, const float* mean, const float* rstd, float slope, float* dx,
                               float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream) {
+  SwitchScope switches_;  // (both passes see one value of nc_set_stream_passes)
   if (!dy || !x || !mean || !rstd || !dx || !dbias) { set_error("instnorm_act_bwd_dbias: null pointer"); return NC_ERR_ARG; }
   const long NCl = (long)N * C;
   if (N < 1 || C < 1 || S < 1 || NCl > 0x7fffffffL) { set_error("instnorm_act_bwd_dbias: bad shape"); return NC_ERR_SHAPE; }
@@ -1076,11 +1170,10 @@ int nc_instnorm_act_bwd_dbias(const float* dy, const float* x, const float* mean
   if (!ws || ws_bytes < nc_instnorm_bwd_dbias_ws_bytes(NC, S)) { set_error("instnorm_act_bwd_dbias: workspace too small"); return NC_ERR_WS; }
   const int splits = pick_splits(NC, S);
   double* rowpart = (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S));
-  hipLaunchKernelGGL(k_in_bwd_sums, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws);
+  launch_in_bwd_sums(dy, x, mean, rstd, slope, S, splits, NC, (double*)ws, s);
   long bx = cdiv(S, 1024);
   if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(k_in_bwd_apply, dim3((unsigned)bx, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits,
-                     (const double*)ws, dx, rowpart);
+  launch_in_bwd_apply(dy, x, mean, rstd, slope, S, splits, NC, bx, (const double*)ws, dx, rowpart, s);
   hipLaunchKernelGGL(k_in_dbias_final, dim3(C), dim3(256), 0, s, (const double*)rowpart, N, C, (int)bx, dbias);
   return check_launch("instnorm_act_bwd_dbias");
 }
@@ -1102,6 +1195,7 @@ int nc_instnorm_act_fwd_c8(const float* x, const float* mean, const float* rstd,
 
 int nc_instnorm_act_bwd_c8(const float* dy, const float* x, const float* mean, const float* rstd, float slope, float* dx,
                            void* dxh, float* dbias, int N, int C, long S, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  SwitchScope switches_;  // (both passes see one value of nc_set_stream_passes)
   if (!dy || !x || !mean || !rstd || !dx || !dxh) { set_error("instnorm_act_bwd_c8: null pointer"); return NC_ERR_ARG; }
   const long NCl = (long)N * C;
   if (N < 1 || C < 8 || C % 8 || S < 1 || NCl > 65535) { set_error("instnorm_act_bwd_c8: bad shape"); return NC_ERR_SHAPE; }
@@ -1110,7 +1204,7 @@ int nc_instnorm_act_bwd_c8(const float* dy, const float* x, const float* mean, c
   if (!ws || ws_bytes < nc_instnorm_bwd_dbias_ws_bytes(NC, S)) { set_error("instnorm_act_bwd_c8: workspace too small"); return NC_ERR_WS; }
   hipStream_t s = (hipStream_t)stream;
   const int splits = pick_splits(NC, S);
-  hipLaunchKernelGGL(k_in_bwd_sums, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws);
+  launch_in_bwd_sums(dy, x, mean, rstd, slope, S, splits, NC, (double*)ws, s);
   long bx = cdiv(S, 1024);  // the same block count as nc_instnorm_bwd_dbias_ws_bytes sizes the partials for
   if (bx > 1024) bx = 1024;
   double* rowpart = dbias ? (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S)) : nullptr;
@@ -1132,13 +1226,14 @@ namespace nc {
 bool instnorm_bwd_s3_supported(int N, int C, long S) { return N >= 1 && C >= 8 && C % 8 == 0 && S >= 1 && !rows_path(S) && (long)N * C <= 65535; }
 int instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
                               float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream) {
+  SwitchScope switches_;  // (both passes see one value of nc_set_stream_passes)
   if (!dy || !x || !mean || !rstd || !dxs || !dbias) { set_error("instnorm_act_bwd_dbias_s3: null pointer"); return NC_ERR_ARG; }
   if (!instnorm_bwd_s3_supported(N, C, S)) { set_error("instnorm_act_bwd_dbias_s3: bad shape"); return NC_ERR_SHAPE; }
   const int NC = N * C;
   if (!ws || ws_bytes < nc_instnorm_bwd_dbias_ws_bytes(NC, S)) { set_error("instnorm_act_bwd_dbias_s3: workspace too small"); return NC_ERR_WS; }
   hipStream_t s = (hipStream_t)stream;
   const int splits = pick_splits(NC, S);
-  hipLaunchKernelGGL(k_in_bwd_sums, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws);
+  launch_in_bwd_sums(dy, x, mean, rstd, slope, S, splits, NC, (double*)ws, s);
   long bx = cdiv(S, 1024);
   if (bx > 1024) bx = 1024;
   double* rowpart = (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S));
@@ -1157,6 +1252,7 @@ int instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* mean
 static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
                            float* dbias, int N, int C, long S, void* ws, size_t ws_bytes, void* stream, unsigned* guard,
                            const PoolGrad* pool = nullptr) {
+  SwitchScope switches_;  // (both passes see one value of nc_set_stream_passes)
   if (!dy || !x || !mean || !rstd || !dxs || !dbias) { set_error("instnorm_act_bwd_dbias_h2: null pointer"); return NC_ERR_ARG; }
   if (!instnorm_bwd_s3_supported(N, C, S)) { set_error("instnorm_act_bwd_dbias_h2: bad shape"); return NC_ERR_SHAPE; }
   const int NC = N * C;
@@ -1182,10 +1278,15 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
   hipLaunchKernelGGL(k_zero_u32, dim3((unsigned)cdiv(64 + 2 * NC, 256)), dim3(256), 0, s, cells, 64 + 2 * NC, fold ? guard : (unsigned*)nullptr, 8);
   const int splits = pick_splits(NC, S);
   const dim3 gs(splits, NC);
-  constexpr int U = 4;
+  // Prefetch depth of the folded sums pass: 4; with nc_set_stream_passes the rank-one form, whose one-channel gradient sits in L2, takes 8
+  // (103.6 -> 100.6 us at 64 x 108^3).  The POOL and the plain form gained nothing from 8 (both grids together 117.7 -> 119.5 and 33.2 -> 34.3 us,
+  // DESIGN.md 4.1): the switch does not change them.
+  constexpr int U = 4, U_R1 = 8;
+  const bool sp = stream_passes_on();
 #define NC_SUMS(R1_, POOL_, U_, pq_) \
   hipLaunchKernelGGL((k_in_bwd_sums_h2<R1_, POOL_, U_>), gs, dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax, w1, pq_)
   if (pool) NC_SUMS(false, true, U, *pool);
+  else if (fold && w1 && sp) NC_SUMS(true, false, U_R1, none);
   else if (fold && w1) NC_SUMS(true, false, U, none);
   else if (fold) NC_SUMS(false, false, U, none);
   else if (w1) NC_SUMS(true, false, 1, none);
@@ -1196,15 +1297,18 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
   if (bx > 1024) bx = 1024;
   double* rowpart = (double*)((char*)ws + nc_instnorm_ws_bytes(NC, S));
   const dim3 ga((unsigned)bx, (unsigned)(NC / 8));
-#define NC_APPLY(R1_, POOL_, FOLD_, pq_)                                                                                                     \
-  hipLaunchKernelGGL((k_in_bwd_apply_h2<R1_, POOL_, FOLD_>), ga, dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (const double*)ws, \
+#define NC_APPLY(R1_, POOL_, FOLD_, pq_) NC_APPLY_(R1_, POOL_, FOLD_, false, pq_)
+#define NC_APPLY_(R1_, POOL_, FOLD_, STAGE_, pq_)                                                                                            \
+  hipLaunchKernelGGL((k_in_bwd_apply_h2<R1_, POOL_, FOLD_, STAGE_>), ga, dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (const double*)ws, \
                      (uint4*)dxs, C / 8, rowpart, (const unsigned*)cells, g, w1, pq_, (const unsigned*)gmax, (const unsigned*)xmax, NC, cells)
   if (pool) NC_APPLY(false, true, true, *pool);
+  else if (fold && w1 && sp) NC_APPLY_(true, false, true, true, none);
   else if (fold && w1) NC_APPLY(true, false, true, none);
   else if (fold) NC_APPLY(false, false, true, none);
   else if (w1) NC_APPLY(true, false, false, none);
   else NC_APPLY(false, false, false, none);
 #undef NC_APPLY
+#undef NC_APPLY_
   // chunks: one per wave and loop iteration = (NC / 8) * sum over blocks of ceil(iterations): every 64-voxel group of every 8-channel block
   const unsigned long long total = (unsigned long long)(NC / 8) * (unsigned long long)cdiv(S, 64);
   if (fold) {
@@ -1260,6 +1364,10 @@ int maxpool2_fwd_arg(const float* x, float* y, unsigned char* arg, int NC, int D
 static std::atomic<int> g_in_bwd_fold{getenv("NC_IN_BWD_FOLD") ? (atoi(getenv("NC_IN_BWD_FOLD")) != 0) : 1};
 int in_bwd_fold_raw() { return g_in_bwd_fold.load(std::memory_order_relaxed); }
 bool in_bwd_fold_on() { const int f = frozen_fold(); return (f >= 0 ? f : in_bwd_fold_raw()) != 0; }
+// nc_set_stream_passes: the same
+static std::atomic<int> g_stream_passes{1};
+int stream_passes_raw() { return g_stream_passes.load(std::memory_order_relaxed); }
+bool stream_passes_on() { const int f = frozen_stream(); return (f >= 0 ? f : stream_passes_raw()) != 0; }
 static std::atomic<int> g_in_bwd_launches[2];  // [0] the two-term norm backward, [1] nc_maxpool2_bwd_add
 void count_in_bwd_launches(int n, int which) { g_in_bwd_launches[which].fetch_add(n, std::memory_order_relaxed); }
 int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
@@ -1287,6 +1395,8 @@ int nc_instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* m
 
 int nc_set_in_bwd_fold(int on) { return g_in_bwd_fold.exchange(on != 0, std::memory_order_relaxed); }
 int nc_get_in_bwd_fold(void) { return in_bwd_fold_raw(); }
+int nc_set_stream_passes(int on) { return g_stream_passes.exchange(on != 0, std::memory_order_relaxed); }
+int nc_get_stream_passes(void) { return stream_passes_raw(); }
 int nc_in_bwd_launches(int which, int reset) {
   std::atomic<int>& c = g_in_bwd_launches[which == 1 ? 1 : 0];
   return reset ? c.exchange(0, std::memory_order_relaxed) : c.load(std::memory_order_relaxed);

@@ -8,6 +8,8 @@
 //   2. k_wprep_bounds: the output bounds of the transposed convolutions (inputs of the concat blocks' forward packs)
 //   3. k_wprep_absmax: every segment's weight cell (blockIdx.y = segment), integer atomicMax
 //   4. k_wprep_pack: every segment's packed weights; the segment of a concat block also leaves the bound in the H2 tensor's second cell
+// With nc_set_stream_passes (default) launches 3 and 4 are k_wprep_absmax_rows (rows of an output channel, no division per element) and
+// k_wprep_pack_frag (one thread per 16-byte unit of a fragment, both terms from one read of the eight weights): the same cells, the same packs.
 #include "common.hpp"
 #include "w_prep.hpp"
 
@@ -26,7 +28,7 @@ struct WPrepDevSeg {
 };
 struct WPrepDevTable {
   WPrepDevSeg seg[kWPrepMaxSegs];
-  unsigned blk0[kWPrepMaxSegs + 1];  // first block of each segment in k_wprep_pack's grid
+  unsigned blk0[kWPrepMaxSegs + 1];  // first block of each segment in the pack's grid: blocks of 256 elements (k_wprep_pack) or of 256 16-byte units (k_wprep_pack_frag)
   int nseg;
 };
 struct WPrepDevBounds {
@@ -49,6 +51,14 @@ __global__ void __launch_bounds__(256) k_wprep_absmax(const WPrepDevTable t, uns
   const unsigned ca = g.a_bits, cb = g.b_cell >= 0 ? cells[g.b_cell] : ca;
   absmax_w_block(g.w, g.nw, 27, g.Cin, g.split_c, ca, cb, cells + blockIdx.y, blockIdx.x, gridDim.x, wm);
 }
+// nc_set_stream_passes: the same cells, walked by rows (w_prep.hpp)
+__global__ void __launch_bounds__(256) k_wprep_absmax_rows(const WPrepDevTable t, unsigned* __restrict__ cells) {
+  __shared__ unsigned wm[4];
+  const WPrepDevSeg& g = t.seg[blockIdx.y];
+  if (!g.w) return;
+  const unsigned ca = g.a_bits, cb = g.b_cell >= 0 ? cells[g.b_cell] : ca;
+  absmax_w_rows_block(g.w, g.nw, 27, g.Cin, g.split_c, ca, cb, cells + blockIdx.y, (int)blockIdx.x, (int)gridDim.x, wm);
+}
 
 __global__ void __launch_bounds__(256) k_wprep_pack(const WPrepDevTable t, const unsigned* __restrict__ cells) {
   int k = 0;
@@ -59,6 +69,18 @@ __global__ void __launch_bounds__(256) k_wprep_pack(const WPrepDevTable t, const
   if (i == 0 && g.ext_cell) *g.ext_cell = cb;
   if (i >= g.total) return;
   g.wp[i] = pack_w_s3x_elem<2>(g.w, i, g.Cin / 8, 3, g.NS, g.so, g.si, g.flip, cells[k], g.split_c, ca, cb);
+}
+// nc_set_stream_passes: the same packs, one thread per 16-byte unit of a fragment -- the eight weights are read and split once and written for
+// both terms (k_wprep_pack: sixteen threads, sixteen scattered reads and splits, sixteen 2-byte stores).  blk0 counts blocks of 256 UNITS here.
+__global__ void __launch_bounds__(256) k_wprep_pack_frag(const WPrepDevTable t, const unsigned* __restrict__ cells) {
+  int k = 0;
+  while (k + 1 < t.nseg && blockIdx.x >= t.blk0[k + 1]) ++k;
+  const WPrepDevSeg& g = t.seg[k];
+  const unsigned ca = g.a_bits, cb = g.b_cell >= 0 ? cells[g.b_cell] : ca;
+  const long u = (long)(blockIdx.x - t.blk0[k]) * 256 + threadIdx.x;
+  if (u == 0 && g.ext_cell) *g.ext_cell = cb;
+  if (u >= g.total / 16) return;  // (total: a multiple of the 2048 elements of a fragment pair)
+  pack_w_s3x_frag2(g.w, u, g.Cin / 8, 3, g.NS, g.so, g.si, g.flip, cells[k], g.split_c, ca, cb, (uint4*)g.wp);
 }
 
 }  // namespace
@@ -77,6 +99,8 @@ int wprep_run(const WPrepSeg* segs, int n, const WPrepBound* bounds, int nb, voi
   char* packs = (char*)region + kWPrepCellBytes;
   WPrepDevTable t{};
   WPrepDevBounds tb{};
+  const bool frag = stream_passes_on();  // (k_wprep_absmax_rows + k_wprep_pack_frag; off: the kernels as they were)
+  if (frag && ((uintptr_t)packs & 15) != 0) { set_error("wprep_run: the region must be 16-byte aligned"); return NC_ERR_ARG; }  // (the convolutions read the packs as uint4)
   t.nseg = n;
   size_t off = 0;
   unsigned blk = 0;
@@ -100,7 +124,7 @@ int wprep_run(const WPrepSeg* segs, int n, const WPrepBound* bounds, int nb, voi
     g.so = h.flip ? 27 : (long)h.Cin * 27; g.si = h.flip ? (long)h.Kout * 27 : 27;
     g.split_c = h.flip ? h.Cin : h.Cin / 2;
     g.b_cell = h.b_cell; g.a_bits = h.a_bits;
-    blk += (unsigned)cdiv(g.total, 256);
+    blk += (unsigned)cdiv(frag ? g.total / 16 : g.total, 256);
     if (out) { out[k].wp = packs + off; out[k].wcell = cells + k; }
     off += bytes;
   }
@@ -114,8 +138,12 @@ int wprep_run(const WPrepSeg* segs, int n, const WPrepBound* bounds, int nb, voi
   tb.n = nb;
   if (int e = h2_zero_cells(cells, kWPrepBoundCell0 + kWPrepMaxBounds, s)) return e;
   if (nb) hipLaunchKernelGGL(k_wprep_bounds, dim3((unsigned)cdiv((long)kmax * 8, 64), (unsigned)nb), dim3(256), 0, s, tb, cells);
-  if (n) hipLaunchKernelGGL(k_wprep_absmax, dim3(256, (unsigned)n), dim3(256), 0, s, t, cells);
-  if (blk) hipLaunchKernelGGL(k_wprep_pack, dim3(blk), dim3(256), 0, s, t, (const unsigned*)cells);
+  // (256 blocks per segment, as before: every block ends in one atomicMax and the cells share a cache line -- with 1024 blocks per segment the
+  // pass took twice as long)
+  if (n && frag) hipLaunchKernelGGL(k_wprep_absmax_rows, dim3(256, (unsigned)n), dim3(256), 0, s, t, cells);
+  else if (n) hipLaunchKernelGGL(k_wprep_absmax, dim3(256, (unsigned)n), dim3(256), 0, s, t, cells);
+  if (blk && frag) hipLaunchKernelGGL(k_wprep_pack_frag, dim3(blk), dim3(256), 0, s, t, (const unsigned*)cells);
+  else if (blk) hipLaunchKernelGGL(k_wprep_pack, dim3(blk), dim3(256), 0, s, t, (const unsigned*)cells);
   return check_launch("wprep_run");
 }
 
