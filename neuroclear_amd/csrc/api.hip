@@ -1,6 +1,5 @@
 // C-ABI glue: error reporting, convolution dispatch (MFMA implicit GEMM vs direct), and the whole-network forward of
 // Unet_deconv used by diced inference (reference models/networks.py:512-538 via models/test_model.py:60-62).
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -14,7 +13,6 @@
 namespace nc {
 
 static thread_local char g_err[512] = "";
-int g_force_direct = 0;
 
 void set_error(const char* fmt, ...) {
   va_list ap;
@@ -78,48 +76,42 @@ ProfScope::~ProfScope() {
 
 // NC_SCONV=0 switches the image-staged kernels of the PatchGAN layers off (A/B runs against the gather GEMM)
 static bool sconv_on(const ConvDims& d, int dgrad) {
-  static const bool on = !(getenv("NC_SCONV") && atoi(getenv("NC_SCONV")) == 0);
-  return on && (dgrad ? sconv_dgrad_supported(d) : sconv_fwd_supported(d));
+  return sw::raw(sw::SCONV) && (dgrad ? sconv_dgrad_supported(d) : sconv_fwd_supported(d));
 }
 // NC_PG1=0: the PatchGAN's first layer back on the generic kernels (A/B runs)
 static bool pg1_on(const ConvDims& d) {
-  static const bool on = !(getenv("NC_PG1") && atoi(getenv("NC_PG1")) == 0);
-  return on && pg1_supported(d);
+  return sw::raw(sw::PG1) && pg1_supported(d);
 }
 // Split-operand kernels (conv_split.hip): the fp32 3^3 / 5^3 convolutions they cover run as six bf16 MFMA products of an exact
 // three-term operand split (same operands, fp32 accumulation, error against fp64 not above the fp32 MFMA kernel's:
 // tests/test_gpu_split.py).  On by default; nc_set_conv_split(0) or NC_CONV_SPLIT=0 put those layers back on the fp32 MFMA kernels.
-static std::atomic<int> g_split{getenv("NC_CONV_SPLIT") ? atoi(getenv("NC_CONV_SPLIT")) : 1};  // process-wide; read once per call
 // NC_S3_FUSE=0 (nc_set_s3_fusion(0)): nc_unet_deconv_fwd converts every convolution input to S3 in a separate pass (A/B, tests)
-static std::atomic<int> g_s3_fuse{getenv("NC_S3_FUSE") ? atoi(getenv("NC_S3_FUSE")) : 1};
 static int fwd_path(const ConvDims& d) {
-  if (g_force_direct) return 0;
-  if (g_split && s3_fwd_supported(d)) return 9;
-  if (g_split && p2d_fwd_supported(d)) return 10;
-  if (g_split && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) in pseudo-channel form on the two-term kernels (conv_s3x.hip)
-  if (conv2d_k3_on() && conv2d_k3_fwd_supported(d)) return 12;  // Conv2d 3 x 3 of the 2-D generators, image-tiled (conv2d_k3.hip)
+  if (sw::raw(sw::FORCE_DIRECT)) return 0;
+  if (sw::raw(sw::CONV_SPLIT) && s3_fwd_supported(d)) return 9;
+  if (sw::raw(sw::CONV_SPLIT) && p2d_fwd_supported(d)) return 10;
+  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) in pseudo-channel form on the two-term kernels (conv_s3x.hip)
+  if (sw::raw(sw::CONV2D_K3) && conv2d_k3_fwd_supported(d)) return 12;  // Conv2d 3 x 3 of the 2-D generators, image-tiled (conv2d_k3.hip)
   return (c1k3_fwd_supported(d) || mfma_fwd_supported(d)) ? 1 : flat_1x1_supported(d) ? 3 : k1_fwd_supported(d) ? 5 : pg1_on(d) ? 8 : sconv_on(d, 0) ? 7 : gemm_fwd_supported(d) ? 2 : 0;
 }
 static int dgrad_path(const ConvDims& d) {
-  if (g_force_direct) return 0;
-  if (g_split && s3_dgrad_supported(d)) return 9;
-  if (g_split && p2d_dgrad_supported(d)) return 10;
-  if (g_split && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7): two-term pseudo-channel form + fold (conv_s3x.hip)
-  if (conv2d_k3_on() && conv2d_k3_dgrad_supported(d)) return 12;
+  if (sw::raw(sw::FORCE_DIRECT)) return 0;
+  if (sw::raw(sw::CONV_SPLIT) && s3_dgrad_supported(d)) return 9;
+  if (sw::raw(sw::CONV_SPLIT) && p2d_dgrad_supported(d)) return 10;
+  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7): two-term pseudo-channel form + fold (conv_s3x.hip)
+  if (sw::raw(sw::CONV2D_K3) && conv2d_k3_dgrad_supported(d)) return 12;
   return mfma_dgrad_supported(d) ? 1 : flat_1x1_supported(d) ? 3 : to1_mfma_supported(d) ? 6 : to1_dgrad_supported(d) ? 0
                                                                                               : pg1_on(d)             ? 8
                                                                                               : sconv_on(d, 1)        ? 7
                                                                                               : gemm_dgrad_supported(d) ? 2 : 0;
 }
 static bool sconv_wgrad_on(const ConvDims& d) {
-  static const bool on = !(getenv("NC_SCONV") && atoi(getenv("NC_SCONV")) == 0) &&
-                         !(getenv("NC_SCONV_WGRAD") && atoi(getenv("NC_SCONV_WGRAD")) == 0);
-  return on && sconv_wgrad_supported(d);
+  return sw::raw(sw::SCONV) && sw::raw(sw::SCONV_WGRAD) && sconv_wgrad_supported(d);
 }
 static int wgrad_path(const ConvDims& d) {
-  if (g_force_direct) return 0;
-  if (g_split && s3_wgrad_supported(d)) return 9;
-  if (g_split && p2d_wgrad_supported(d)) return 10;
+  if (sw::raw(sw::FORCE_DIRECT)) return 0;
+  if (sw::raw(sw::CONV_SPLIT) && s3_wgrad_supported(d)) return 9;
+  if (sw::raw(sw::CONV_SPLIT) && p2d_wgrad_supported(d)) return 10;
   return mfma_wgrad_supported(d) ? 1 : wgrad_1x1_supported(d) ? 3 : c1_wgrad_supported(d) ? 4 : k1_wgrad_supported(d) ? 5
                                                                                             : pg1_on(d)              ? 8
                                                                                             : sconv_wgrad_on(d)      ? 7
@@ -159,22 +151,39 @@ int nc_prof_end2(int max, int* cls, double* flop, float* ms, double* abytes) {
 
 const char* nc_last_error(void) { return g_err; }
 int nc_version(void) { return 100; }
-void nc_set_force_direct(int on) { g_force_direct = on; }
-void nc_sconv_set_cfg(int cfg) { sconv_set_cfg(cfg); }
-void nc_sconv_set_tune(int on) { sconv_set_tune(on); }
-void nc_set_conv_split(int on) { g_split = on; }
-void nc_set_s3_fusion(int on) { g_s3_fuse = on; }
-int nc_get_conv_split(void) { return g_split; }
-void nc_set_split_terms(int terms) { s3x_set_terms(terms); }
-int nc_get_split_terms(void) { return s3x_get_terms(); }
-void nc_set_epi_stats(int on) { epi_stats_set(on); }
-int nc_get_epi_stats(void) { return epi_stats_mode(); }
-void nc_set_s3x_w64(int on) { s3x_w64_set(on); }
-int nc_get_s3x_w64(void) { return s3x_w64_get(); }
-void nc_set_p2d_terms(int mode) { p2d_set_terms(mode); }
-int nc_get_p2d_terms(void) { return p2d_get_terms(); }
-void nc_set_h2_guard(int on) { h2_guard_set(on); }
-int nc_get_h2_guard(void) { return h2_guard_mode(); }
+// the switches of the C ABI over the one table (switches.hpp): a setter clamps by its row; the two frozen getters answer as the call sees them
+void nc_set_force_direct(int on) { sw::set(sw::FORCE_DIRECT, on); }
+void nc_sconv_set_cfg(int cfg) { sw::set(sw::SCONV_CFG_PIN, cfg); }
+void nc_sconv_set_tune(int on) { sw::set(sw::SCONV_TUNE_MODE, on); }
+void nc_set_conv_split(int on) { sw::set(sw::CONV_SPLIT, on); }
+int nc_get_conv_split(void) { return sw::raw(sw::CONV_SPLIT); }
+void nc_set_s3_fusion(int on) { sw::set(sw::S3_FUSE, on); }
+void nc_set_split_terms(int terms) { sw::set(sw::SPLIT_TERMS, terms); }
+int nc_get_split_terms(void) { return sw::get(sw::SPLIT_TERMS); }
+void nc_set_epi_stats(int on) { sw::set(sw::EPI_STATS, on); }
+int nc_get_epi_stats(void) { return sw::raw(sw::EPI_STATS); }
+void nc_set_s3x_w64(int on) { sw::set(sw::S3X_W64, on); }
+int nc_get_s3x_w64(void) { return sw::raw(sw::S3X_W64); }
+void nc_set_p2d_terms(int mode) { sw::set(sw::P2D_TERMS, mode); }
+int nc_get_p2d_terms(void) { return sw::raw(sw::P2D_TERMS); }
+// (allocates the pinned counter block HERE, off the launch path: a first allocation inside h2_guard_decide could invalidate a stream capture)
+void nc_set_h2_guard(int on) { sw::set(sw::H2_GUARD, on); if (on) (void)h2_guard_stats_dev(); }
+int nc_get_h2_guard(void) { return sw::get(sw::H2_GUARD); }
+void nc_set_c8x_mode(int mode) { sw::set(sw::C8X, mode); }
+int nc_get_c8x_mode(void) { return sw::raw(sw::C8X); }
+void nc_set_unet_wprep(int on) { sw::set(sw::UNET_WPREP, on); }
+int nc_get_unet_wprep(void) { return sw::raw(sw::UNET_WPREP); }
+void nc_set_unet_lean(int on) { sw::set(sw::UNET_LEAN, on); }
+int nc_get_unet_lean(void) { return sw::raw(sw::UNET_LEAN); }
+void nc_set_dl_collapse(int on) { sw::set(sw::DL_COLLAPSE, on); }
+int nc_get_dl_collapse(void) { return sw::raw(sw::DL_COLLAPSE); }
+int nc_set_in_bwd_fold(int on) { return sw::set(sw::IN_BWD_FOLD, on); }
+int nc_get_in_bwd_fold(void) { return sw::raw(sw::IN_BWD_FOLD); }
+int nc_set_stream_passes(int on) { return sw::set(sw::STREAM_PASSES, on); }
+int nc_get_stream_passes(void) { return sw::raw(sw::STREAM_PASSES); }
+int nc_set_conv2d_k3(int on) { return sw::set(sw::CONV2D_K3, on); }
+int nc_get_conv2d_k3(void) { return sw::raw(sw::CONV2D_K3); }
+int nc_conv2d_k3_set_cfg(int cfg) { return sw::set(sw::CONV2D_K3_CFG, cfg); }
 int nc_h2_guard_stats(unsigned long long* out4, int reset) {
   if (!out4) { set_error("h2_guard_stats: null pointer"); return NC_ERR_ARG; }
   return h2_guard_read(out4, reset);
@@ -182,13 +191,10 @@ int nc_h2_guard_stats(unsigned long long* out4, int reset) {
 
 int nc_conv2d_split_active(int what, int N, int C, int H, int W, int K, int k, int stride, int pad) {
   ConvDims d;
-  if (!make_dims(d, N, C, 1, H, W, K, 1, k, k, stride, pad) || g_force_direct || !g_split) return 0;
+  if (!make_dims(d, N, C, 1, H, W, K, 1, k, k, stride, pad) || sw::raw(sw::FORCE_DIRECT) || !sw::raw(sw::CONV_SPLIT)) return 0;
   return what == 0 ? (p2d_fwd_supported(d) ? 1 : 0) : what == 1 ? (p2d_dgrad_supported(d) ? 1 : 0) : what == 2 ? (p2d_wgrad_supported(d) ? 1 : 0) : 0;
 }
 
-int nc_set_conv2d_k3(int on) { const int prev = conv2d_k3_on() ? 1 : 0; conv2d_k3_set(on); return prev; }
-int nc_get_conv2d_k3(void) { return conv2d_k3_on() ? 1 : 0; }
-int nc_conv2d_k3_set_cfg(int cfg) { return conv2d_k3_set_cfg(cfg); }
 int nc_conv2d_k3_num_cfgs(void) { return conv2d_k3_num_cfgs(); }
 int nc_conv2d_k3_active(int what, int N, int C, int H, int W, int K) {
   ConvDims d;
@@ -200,9 +206,9 @@ int nc_conv_fwd_path(int C, int K, int kd, int kh, int kw, int stride, int pad) 
   ConvDims d;
   const int e = (kd == 1 && kh == 1 && kw == 1) ? 256 : 32;  // pointwise: a plane large enough for the flat kernel
   if (!make_dims(d, 1, C, kd > 1 ? 32 : 1, e, e, K, kd, kh, kw, stride, pad)) return -1;
-  if (g_force_direct) return 0;
-  if (g_split && s3_fwd_supported(d)) return 9;
-  if (g_split && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) on the two-term kernels in pseudo-channel form (round 6)
+  if (sw::raw(sw::FORCE_DIRECT)) return 0;
+  if (sw::raw(sw::CONV_SPLIT) && s3_fwd_supported(d)) return 9;
+  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) on the two-term kernels in pseudo-channel form (round 6)
   return mfma_fwd_supported(d) ? 1 : flat_1x1_supported(d) ? 3 : pg1_on(d) ? 8 : gemm_fwd_supported(d) ? 2 : 0;  // (the K = 1
   // reduction kernel of the PatchGAN head and the image-staged kernels depend on the batch, which this query does not take:
   // reported as 2)
@@ -211,8 +217,8 @@ int nc_conv_wgrad_path(int C, int K, int kd, int kh, int kw, int stride, int pad
   ConvDims d;
   const int e = (kd == 1 && kh == 1 && kw == 1) ? 256 : 32;  // pointwise: a plane large enough for the flat kernel
   if (!make_dims(d, 1, C, kd > 1 ? 32 : 1, e, e, K, kd, kh, kw, stride, pad)) return -1;
-  if (g_force_direct) return 0;
-  if (g_split && s3_wgrad_supported(d)) return 9;
+  if (sw::raw(sw::FORCE_DIRECT)) return 0;
+  if (sw::raw(sw::CONV_SPLIT) && s3_wgrad_supported(d)) return 9;
   return mfma_wgrad_supported(d) ? 1 : wgrad_1x1_supported(d) ? 3 : c1_wgrad_supported(d) ? 4
                                                                          : gemm_wgrad_supported(d) ? 2 : 0;
 }
@@ -242,19 +248,19 @@ size_t nc_conv_ws_bytes(int N, int C, int D, int H, int W, int K, int kd, int kh
     if (sc > b) b = sc;
   }
   if (conv2d_k3_ws_bytes(d) > b) b = conv2d_k3_ws_bytes(d);  // its packed weights (whether or not the switch is on: the size does not depend on it)
-  if (g_split) {
+  if (sw::raw(sw::CONV_SPLIT)) {
     size_t sc = p2d_ws_bytes(d);
     if (sc > b) b = sc;
     sc = p2d_wgrad_ws_bytes(d);
     if (sc > b) b = sc;
   }
-  if (g_split && (s3_fwd_supported(d) || s3_dgrad_supported(d))) {
+  if (sw::raw(sw::CONV_SPLIT) && (s3_fwd_supported(d) || s3_dgrad_supported(d))) {
     const size_t sc = s3_ws_bytes(d);
     if (sc > b) b = sc;
   }
-  if (g_split && c1k7_h2_ws_bytes(d) > b) b = c1k7_h2_ws_bytes(d);
-  if (g_split && c1k7_h2_dgrad_ws_bytes(d) > b) b = c1k7_h2_dgrad_ws_bytes(d);
-  if (g_split && s3_wgrad_supported(d)) {
+  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_ws_bytes(d) > b) b = c1k7_h2_ws_bytes(d);
+  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_dgrad_ws_bytes(d) > b) b = c1k7_h2_dgrad_ws_bytes(d);
+  if (sw::raw(sw::CONV_SPLIT) && s3_wgrad_supported(d)) {
     size_t sc = s3_wgrad_ws_bytes(d);
     if (sc > b) b = sc;
     sc = s3_bwd_ws_bytes(d);
@@ -286,13 +292,13 @@ int nc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int
   if (path == 10) return conv_fwd_p2d(x, w, bias, y, d, ws, ws_bytes, s);
   if (path == 11 && ws && ws_bytes >= c1k7_h2_ws_bytes(d)) return conv_c1k7_h2(x, w, bias, y, d, ws, ws_bytes, s);
   if (path == 12) return conv_fwd_k3(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!g_force_direct && c1k3_fwd_supported(d)) return conv_fwd_c1k3(x, w, bias, y, d, s);  // 1 -> K channels, 3^3: its own fp32 MFMA kernel
-  if (!g_force_direct && mfma_fwd_supported(d)) return conv_fwd_mfma(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!g_force_direct && flat_1x1_supported(d)) return conv_fwd_1x1(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!g_force_direct && k1_fwd_supported(d)) return conv_fwd_k1(x, w, bias, y, d, s);
-  if (!g_force_direct && fwd_path(d) == 8) return conv_fwd_pg1(x, w, bias, y, d, 1.f, s);
-  if (!g_force_direct && sconv_on(d, 0)) return conv_fwd_sconv(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!g_force_direct && gemm_fwd_supported(d)) return conv_fwd_gemm(x, w, bias, y, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && c1k3_fwd_supported(d)) return conv_fwd_c1k3(x, w, bias, y, d, s);  // 1 -> K channels, 3^3: its own fp32 MFMA kernel
+  if (!sw::raw(sw::FORCE_DIRECT) && mfma_fwd_supported(d)) return conv_fwd_mfma(x, w, bias, y, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && flat_1x1_supported(d)) return conv_fwd_1x1(x, w, bias, y, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && k1_fwd_supported(d)) return conv_fwd_k1(x, w, bias, y, d, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && fwd_path(d) == 8) return conv_fwd_pg1(x, w, bias, y, d, 1.f, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && sconv_on(d, 0)) return conv_fwd_sconv(x, w, bias, y, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && gemm_fwd_supported(d)) return conv_fwd_gemm(x, w, bias, y, d, ws, ws_bytes, s);
   return conv_fwd_direct(x, w, bias, y, d, s);
 }
 
@@ -307,13 +313,13 @@ int nc_conv_dgrad(const float* dy, const float* w, float* dx, int N, int C, int 
   if (path == 10) return conv_dgrad_p2d(dy, w, dx, d, ws, ws_bytes, s);
   if (path == 11 && ws && ws_bytes >= c1k7_h2_dgrad_ws_bytes(d)) return conv_c1k7_h2_dgrad(dy, w, dx, d, ws, ws_bytes, s);
   if (path == 12) return conv_dgrad_k3(dy, w, dx, d, ws, ws_bytes, s);
-  if (!g_force_direct && mfma_dgrad_supported(d)) return conv_dgrad_mfma(dy, w, dx, d, ws, ws_bytes, s);
-  if (!g_force_direct && flat_1x1_supported(d)) return conv_dgrad_1x1(dy, w, dx, d, ws, ws_bytes, s);
-  if (!g_force_direct && to1_mfma_supported(d)) return conv_dgrad_to1_mfma(dy, w, dx, d, ws, ws_bytes, s);
-  if (!g_force_direct && to1_dgrad_supported(d)) return conv_dgrad_to1(dy, w, dx, d, s);
-  if (!g_force_direct && dgrad_path(d) == 8) return conv_dgrad_pg1(dy, nullptr, 1.f, w, dx, d, s);
-  if (!g_force_direct && sconv_on(d, 1)) return conv_dgrad_sconv(dy, w, dx, d, ws, ws_bytes, s);
-  if (!g_force_direct && gemm_dgrad_supported(d)) return conv_dgrad_gemm(dy, w, dx, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && mfma_dgrad_supported(d)) return conv_dgrad_mfma(dy, w, dx, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && flat_1x1_supported(d)) return conv_dgrad_1x1(dy, w, dx, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && to1_mfma_supported(d)) return conv_dgrad_to1_mfma(dy, w, dx, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && to1_dgrad_supported(d)) return conv_dgrad_to1(dy, w, dx, d, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && dgrad_path(d) == 8) return conv_dgrad_pg1(dy, nullptr, 1.f, w, dx, d, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && sconv_on(d, 1)) return conv_dgrad_sconv(dy, w, dx, d, ws, ws_bytes, s);
+  if (!sw::raw(sw::FORCE_DIRECT) && gemm_dgrad_supported(d)) return conv_dgrad_gemm(dy, w, dx, d, ws, ws_bytes, s);
   return conv_dgrad_direct(dy, w, dx, d, s);
 }
 
@@ -393,16 +399,16 @@ int nc_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias, int 
   ProfScope ps(2, path, d, 0, s);
   if (path == 9) e = conv_wgrad_s3(x, nullptr, dy, nullptr, dw, d, ws, ws_bytes, s);
   else if (path == 10) e = conv_wgrad_p2d(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!g_force_direct && mfma_wgrad_supported(d)) e = conv_wgrad_mfma(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!g_force_direct && wgrad_1x1_supported(d)) e = conv_wgrad_1x1(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!g_force_direct && c1_wgrad_supported(d)) e = conv_wgrad_c1(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!g_force_direct && k1_wgrad_supported(d)) e = conv_wgrad_k1(x, dy, dw, d, s);
-  else if (!g_force_direct && wgrad_path(d) == 8) {  // the bias gradient is a column of the same product
+  else if (!sw::raw(sw::FORCE_DIRECT) && mfma_wgrad_supported(d)) e = conv_wgrad_mfma(x, dy, dw, d, ws, ws_bytes, s);
+  else if (!sw::raw(sw::FORCE_DIRECT) && wgrad_1x1_supported(d)) e = conv_wgrad_1x1(x, dy, dw, d, ws, ws_bytes, s);
+  else if (!sw::raw(sw::FORCE_DIRECT) && c1_wgrad_supported(d)) e = conv_wgrad_c1(x, dy, dw, d, ws, ws_bytes, s);
+  else if (!sw::raw(sw::FORCE_DIRECT) && k1_wgrad_supported(d)) e = conv_wgrad_k1(x, dy, dw, d, s);
+  else if (!sw::raw(sw::FORCE_DIRECT) && wgrad_path(d) == 8) {  // the bias gradient is a column of the same product
     e = conv_wgrad_pg1(x, dy, nullptr, 1.f, dw, dbias, d, ws, ws_bytes, s);
     dbias = nullptr;
   }
-  else if (!g_force_direct && sconv_wgrad_on(d)) e = conv_wgrad_sconv(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!g_force_direct && gemm_wgrad_supported(d)) e = conv_wgrad_gemm(x, dy, dw, d, ws, ws_bytes, s);
+  else if (!sw::raw(sw::FORCE_DIRECT) && sconv_wgrad_on(d)) e = conv_wgrad_sconv(x, dy, dw, d, ws, ws_bytes, s);
+  else if (!sw::raw(sw::FORCE_DIRECT) && gemm_wgrad_supported(d)) e = conv_wgrad_gemm(x, dy, dw, d, ws, ws_bytes, s);
   else e = conv_wgrad_direct(x, dy, dw, d, s);
   }
   if (e) return e;
@@ -593,7 +599,7 @@ UnetWs unet_ws(int S0, int S1, int S2, int NB = 1) {
 // H2 mode of the whole-network forward: every 3^3 layer must be one the tap-stream kernel covers
 static bool unet_h2_ok(int S0, int S1, int S2, size_t conv_ws_bytes) {
   const int h0 = S0 / 2, h1 = S1 / 2, h2 = S2 / 2, q0 = S0 / 4, q1 = S1 / 4, q2 = S2 / 4;
-  return g_split && g_s3_fuse && s3x_get_terms() != 3 && s3x_supported(1, 64, S0, S1, S2, 64, 3) && s3x_supported(1, 128, S0, S1, S2, 64, 3) &&
+  return sw::raw(sw::CONV_SPLIT) && sw::raw(sw::S3_FUSE) && sw::get(sw::SPLIT_TERMS) != 3 && s3x_supported(1, 64, S0, S1, S2, 64, 3) && s3x_supported(1, 128, S0, S1, S2, 64, 3) &&
          s3x_supported(1, 64, h0, h1, h2, 128, 3) && s3x_supported(1, 128, h0, h1, h2, 128, 3) && s3x_supported(1, 256, h0, h1, h2, 128, 3) &&
          s3x_supported(1, 128, q0, q1, q2, 256, 3) && s3x_supported(1, 256, q0, q1, q2, 256, 3) &&
          conv_ws_bytes >= 256 + s3x_packed_bytes(256, 256, 3, 2) + 256;
@@ -609,7 +615,7 @@ int nc_unet_deconv_fwd_terms(int S0, int S1, int S2) {
 
 // samples per pass of the whole-network forward: the whole batch in the two-term mode (NC_INFER_BATCHED=0: one by one, A/B), else one
 static int unet_fwd_batch(int N, int S0, int S1, int S2) {
-  static const bool batched = !(getenv("NC_INFER_BATCHED") && atoi(getenv("NC_INFER_BATCHED")) == 0);
+  const bool batched = sw::raw(sw::INFER_BATCHED) != 0;
   if (N <= 1 || !batched || nc_unet_deconv_fwd_terms(S0, S1, S2) != 2) return 1;
   return N;
 }
@@ -646,7 +652,7 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
   // layer in front writes that form from its normalisation pass (k_act_split3) instead of a separate conversion pass.
   auto split_in = [&](int C, int K, int D, int H, int Wd) {
     ConvDims d;
-    return g_s3_fuse && make_dims(d, 1, C, D, H, Wd, K, 3, 3, 3, 1, 1) && fwd_path(d) == 9;
+    return sw::raw(sw::S3_FUSE) && make_dims(d, 1, C, D, H, Wd, K, 3, 3, 3, 1, 1) && fwd_path(d) == 9;
   };
   // conv (3^3, pad 1) + InstanceNorm + ReLU: in (fp32) or in3 (S3, when the convolution takes it) -> raw -> out (fp32, nullable)
   // and / or out3 (channels c0 .. of an S3 tensor with ctot channels, nullable)
@@ -670,7 +676,7 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
     };
     // Epilogue statistics (default; NC_EPI_STATS=0 / nc_set_epi_stats(0): off): the two-term convolution leaves the partial InstanceNorm sums of
     // its output itself (conv_s3x.hip, ST) and k_in_stats' pass over the raw output goes away: -1.8 % per 140^3 cube, mean / rstd equal to 4e-8
-    const bool epi = epi_stats_on();
+    const bool epi = sw::raw(sw::EPI_STATS) != 0;
     if (in3 && in_a) {
       ConvDims d;
       make_dims(d, bn, C, D, H, Wd, K, 3, 3, 3, 1, 1);
@@ -695,7 +701,7 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
       NC_TRY(conv_fwd_s3(nullptr, in3, P + o.w[id], P + o.b[id], W + u.raw, d, cws, u.conv_ws_bytes, hs));
     } else {
       ConvDims d1;
-      if (epi && C == 1 && !g_force_direct && make_dims(d1, 1, C, D, H, Wd, K, 3, 3, 3, 1, 1) && c1k3_stats_bytes(d1)) {
+      if (epi && C == 1 && !sw::raw(sw::FORCE_DIRECT) && make_dims(d1, 1, C, D, H, Wd, K, 3, 3, 3, 1, 1) && c1k3_stats_bytes(d1)) {
         // the first block: the one-channel kernel leaves its InstanceNorm sums too (conv_c1k3.hip ST) -- one sample per launch, then ONE
         // normalise + convert pass over the batch
         for (int n = 0; n < bn; ++n) {
@@ -764,7 +770,7 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
       // are measured and converted, the ratio of the two halves' powers of two goes into the consumer's weights
       const bool t10 = convT_s3x_supported(bn, 256, q0, q1, q2, 128) && u.conv_ws_bytes >= convT_s3x_ws_bytes(256, 128);
       const bool t11 = convT_s3x_supported(bn, 128, h0, h1, h2, 64) && u.conv_ws_bytes >= convT_s3x_ws_bytes(128, 64);
-      static const bool ct_h2 = !(getenv("NC_CONVT_H2") && atoi(getenv("NC_CONVT_H2")) == 0);  // 0: three-term input, fp32 output measured and converted (A/B)
+      const bool ct_h2 = sw::raw(sw::CONVT_H2) != 0;  // 0: three-term input, fp32 output measured and converted (A/B)
       const bool t10h = t10 && ct_h2, t11h = t11 && ct_h2;  // the two-term transposed convolution: H2 in (the block's output, bound sqrt(S)), H2 out
       NC_TRY(block(6, nullptr, W + u.s_b2, t10 ? nullptr : W + u.b1, t10 ? W + u.s_b1 : nullptr, 256, 0, 256, 256, q0, q1, q2, c2, nullptr, 0,
                    t10h ? c2 : nullptr));
@@ -800,7 +806,7 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
       // the last block's normalisation, the two pointwise layers and the sigmoid in one pass over its raw output (NC_INFER_TAIL=0: separately)
       static const bool tail = true;
       if (tail) {
-        const bool epi9 = epi_stats_on();
+        const bool epi9 = sw::raw(sw::EPI_STATS) != 0;
         {
           ConvDims d9;
           make_dims(d9, bn, 128, S0, S1, S2, 64, 3, 3, 3, 1, 1);
@@ -835,7 +841,7 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
     // block 5, s_cat2 after block 7) -- or, with the fusion switched off, in fp32 and a separate pass converts it (the same bits) --
     // and they write the S3 form of the upper half of the concatenation themselves when the next convolution takes it (in the
     // inference forward nothing else reads it, so no fp32 copy is written), fp32 otherwise.
-    const bool sp = g_split != 0, fuse = g_s3_fuse != 0;
+    const bool sp = sw::raw(sw::CONV_SPLIT) != 0, fuse = sw::raw(sw::S3_FUSE) != 0;
     const bool t10 = sp && convT_s3x_supported(1, 256, q0, q1, q2, 128) && u.conv_ws_bytes >= convT_s3x_ws_bytes(256, 128);
     const bool t11 = sp && convT_s3x_supported(1, 128, h0, h1, h2, 64) && u.conv_ws_bytes >= convT_s3x_ws_bytes(128, 64);
     const bool b6s3 = t10 && fuse, b8s3 = t11 && fuse;

@@ -196,8 +196,6 @@ int nc_conv_lp_uses_c8x(int what, int fp32_out, int N, int C, int D, int H, int 
   if (what == 1) return c8x_supported(N, K, D, H, W, C, ks, fp32_out != 0) ? 1 : 0;
   return 0;
 }
-void nc_set_c8x_mode(int mode) { c8x_set_mode(mode); }
-int nc_get_c8x_mode(void) { return c8x_get_mode(); }
 int nc_convT_k2s2_split_active(int N, int C, int D, int H, int W, int K) { return nc_get_conv_split() && convT_s3x_supported(N, C, D, H, W, K) ? 1 : 0; }
 size_t nc_convT_k2s2_split_ws_bytes(int N, int C, int D, int H, int W, int K) {
   if (!convT_s3x_supported(N, C, D, H, W, K)) return 0;

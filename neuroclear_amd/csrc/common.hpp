@@ -6,6 +6,7 @@
 #include <cstdio>
 
 #include "../../include/nc_hip.h"
+#include "switches.hpp"
 
 namespace nc {
 
@@ -128,8 +129,6 @@ bool sconv_fwd_supported(const ConvDims& d);
 bool sconv_dgrad_supported(const ConvDims& d);
 size_t sconv_ws_bytes(const ConvDims& d);
 // conv_p2d.hip: the PatchGAN's 4 x 4 stride-1 layer at Athena's batches on the split-operand arithmetic (forward, data gradient)
-void p2d_set_terms(int m);
-int p2d_get_terms();
 bool p2d_fwd_supported(const ConvDims& d);
 bool p2d_dgrad_supported(const ConvDims& d);
 size_t p2d_ws_bytes(const ConvDims& d);
@@ -141,18 +140,13 @@ size_t p2d_wgrad_ws_bytes(const ConvDims& d);
 int conv_wgrad_p2d(const float* x, const float* dy, float* dw, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 int conv_fwd_sconv(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 int conv_dgrad_sconv(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
-void sconv_set_cfg(int cfg);
 // conv2d_k3.hip: Conv2d(k 3, s 1, p 1) forward / data gradient on a 2-D spatial tile with a one-pixel halo (the 2-D generators' 3 x 3 layers)
-bool conv2d_k3_on();  // nc_set_conv2d_k3
-void conv2d_k3_set(int on);
-int conv2d_k3_set_cfg(int cfg);  // returns the previous pin
 int conv2d_k3_num_cfgs();
 bool conv2d_k3_fwd_supported(const ConvDims& d);
 bool conv2d_k3_dgrad_supported(const ConvDims& d);
 size_t conv2d_k3_ws_bytes(const ConvDims& d);
 int conv_fwd_k3(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 int conv_dgrad_k3(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
-void sconv_set_tune(int on);
 bool sconv_wgrad_supported(const ConvDims& d);
 size_t sconv_wgrad_ws_bytes(const ConvDims& d);
 int conv_wgrad_sconv(const float* x, const float* dy, float* dw, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
@@ -206,28 +200,8 @@ int split3_to(const float* x, void* xs, int N, int C, long S, hipStream_t s);
 int split3_into(const float* x, long xstride, void* xs, int N, int C, long S, int ctot, int c0, hipStream_t s, const unsigned* guard = nullptr);
 // (S3 or H2 by the consuming layer d: conv_split.hip)
 bool conv_layer_h2(const ConvDims& d);
-// the explicit S3 entry points (nc_conv_*_split, operands from nc_to_s3) are three-term by definition, whatever nc_set_split_terms says
-struct ForceThreeTerm { ForceThreeTerm(); ~ForceThreeTerm(); };
-// RAII mark of a whole-network call (gen_nets.hip, api.hip): inside one, guard mode 1 COUNTS a flagged measured tensor instead of launching the
-// three-term kernels beside the two-term ones (h2_guard_can_flip) -- ~65 near-empty launches per training step otherwise
-struct NetworkScope { NetworkScope(); ~NetworkScope(); };
-// RAII: the process-wide arithmetic switches (nc_set_split_terms, nc_set_h2_guard) as THIS call sees them -- sampled once when the outermost scope
-// of the thread opens, so that the phases of one call (conversion / data gradient / weight gradient of conv_bwd_s3, the layers of a whole-network
-// call) cannot be desynchronised by another thread moving a switch in between.  NetworkScope opens one; the per-layer entry points
-// with more than one phase open their own.
-struct SwitchScope { SwitchScope(); ~SwitchScope(); };
-// RAII: this thread sees nc_set_split_terms(2) while it lives (kernels that exist in the two-term form only and convert their fp32 operands themselves)
-struct ForceTwoTerm { ForceTwoTerm(); ~ForceTwoTerm(); int prev_terms, prev_depth; };
-int frozen_terms();  // -1: no scope open on this thread
-int frozen_guard();
-int frozen_fold();   // nc_set_in_bwd_fold as this call sees it
-int in_bwd_fold_raw();
-bool in_bwd_fold_on();
-int frozen_stream();  // nc_set_stream_passes as this call sees it
-int stream_passes_raw();
-bool stream_passes_on();
+// (SwitchScope, NetworkScope, ForceTwoTerm, ForceThreeTerm, h2_guard_can_flip: switches.hpp)
 void count_in_bwd_launches(int n, int which = 0);  // nc_in_bwd_launches (norm_act.hip)
-bool h2_guard_can_flip();  // mode 2, or mode 1 outside a whole-network call
 int operand_into(const ConvDims& d, const float* x, long xstride, void* xs, int N, int C, long S, int ctot, int c0, hipStream_t s);
 int act_operand(const ConvDims& d, const float* x, const float* mean, const float* rstd, float slope, float* y, long ystride, void* ys, int N, int C,
                 long S, int ctot, int c0, hipStream_t s);
@@ -238,11 +212,6 @@ int act_split3(const float* x, const float* mean, const float* rstd, float slope
 struct S3xPrepared { const void* wp; const unsigned* wcell; };
 int conv_fwd_s3(const float* x, const void* xs, const float* w, const float* b, float* y, const ConvDims& d, void* ws, size_t wsb,
                 hipStream_t s, void* xs_keep = nullptr, float* stats_part = nullptr, const S3xPrepared* prep = nullptr);
-bool epi_stats_on();  // nc_set_epi_stats / NC_EPI_STATS (conv_s3x.hip)
-void epi_stats_set(int on);
-int epi_stats_mode();
-void s3x_w64_set(int on);  // nc_set_s3x_w64 / NC_S3X_W64 (conv_s3x.hip, k_conv_s3w)
-int s3x_w64_get();
 int conv_dgrad_s3(const float* dy, const void* dys, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 size_t s3_bwd_ws_bytes(const ConvDims& d);
 int conv_bwd_s3(const float* x, const float* dy, const float* w, float* dx, float* dw, const ConvDims& d, void* ws, size_t wsb,
@@ -271,8 +240,6 @@ int wprep_run(const WPrepSeg* segs, int n, const WPrepBound* bounds, int nb, voi
 int s3x_pack_h2(const float* w, int Cin, int Kout, int KS, long so, long si, int flip, int split_c, const unsigned* cell_a, const unsigned* cell_b,
                 unsigned* wcell, void* wp_ws, hipStream_t s);
 // NT = 2 (two-term fp16 split, three products; s3_common.hpp) from the fp32 input: ws >= s3x_h2_ws_bytes
-void s3x_set_terms(int t);
-int s3x_get_terms();
 int conv_s3x_h2(const void* xs, const unsigned* cell_a, const unsigned* cell_b, int split_c, const float* w, const float* bias, float* y, int N,
                 int Cin, int D, int H, int W, int Kout, int KS, long so, long si, int flip, unsigned* wcell, void* wp_ws, hipStream_t s,
                 const unsigned* guard = nullptr, float* stats_part = nullptr, const S3xPrepared* prep = nullptr);
@@ -364,9 +331,6 @@ __device__ __forceinline__ void h2_guard_decide_one(unsigned* ga, unsigned* gb, 
 }
 #endif
 unsigned long long* h2_guard_stats_dev();  // the device pointer of the host-visible counters (allocated on first use, off the launch path)
-bool h2_guard_on();
-int h2_guard_mode();  // 0 off; 1 (default): in-call fallback in the per-layer entry points, whole-network calls count only; 2: in-call fallback everywhere
-void h2_guard_set(int on);
 int h2_guard_read(unsigned long long* out4, int reset);
 int h2_guard_zero(unsigned* g, hipStream_t s, int nwords = 8);
 int h2_guard_decide(unsigned* ga, unsigned* gb, unsigned* prior, unsigned* flag, bool can_flip, hipStream_t s, unsigned long long total_a = 0);
@@ -401,8 +365,6 @@ bool convT_fwd_s3_supported(int N, int C, int D, int H, int W, int K);
 // convt_s3.hip: the same forward on the bf16 matrix cores from an S3 input (three-term split, six products per fp32 product)
 // conv_c8x.hip: the tap-stream form of the 16-bit forward / data-gradient kernel (C8 in, C8 or fp32 out; packed weights in wp_ws)
 size_t c8x_packed_bytes(int Cin, int Kout, int KS);
-void c8x_set_mode(int m);
-int c8x_get_mode();
 bool c8x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS, bool fp32_out);
 int conv_c8x(const void* xh, const float* w, const float* bias, float* y, void* yh, int ctot, int c0, int N, int Cin, int D, int H, int W,
              int Kout, int KS, long so, long si, int flip, int diffuse, int dt, void* wp_ws, hipStream_t s);
@@ -450,7 +412,6 @@ int conv_dgrad_h_c8(const void* dyh, const float* w, void* dxh, int ctot, int c0
 // deep_linear_gen's collapsed tail (gen_nets.hip, "the collapsed tail"): the weight-space steps, shared with the 16-bit path.  tail: dl_tail_bytes()
 // of device scratch; compose fills E / Ef ([64][27] fp32: the 64 -> 1 kernel and its tap-flipped copy); q: [64][27], the caller's one-channel
 // weight gradient (x := dy, dY := act1); grads turns q into dW2 .. dW5
-bool dl_collapse_on();
 size_t dl_tail_bytes();
 const float* dl_tail_E(const char* tail);
 const float* dl_tail_Ef(const char* tail);
@@ -484,8 +445,6 @@ int conv_c1_wgrad_h(const float* x, const void* dyh, float* dw, int N, int D, in
 
 // the fwd/dgrad MFMA kernel prefetches packed weights one kernel row ahead: slack behind the packed stream
 static constexpr size_t kPackSlackBytes = 128 * 1024;
-
-extern int g_force_direct;
 
 // Live launch profiler (nc_prof_begin / nc_prof_end, api.hip): brackets one convolution launch with HIP events on its
 // stream when profiling is on.  cls = op (0 fwd, 1 dgrad, 2 wgrad) | path << 4 | kernel edge << 8 | (16-bit ? 1 << 16 : 0)

@@ -20,8 +20,6 @@
 //   * weights stream through a buffer descriptor, packed [co tile][channel pair][tap][h][32][2], as in conv_mfma_fwd.hip.
 // v_mfma_f32_32x32x2_f32 (exact fp32): the two k values of an MFMA are two input channels of one tap.
 #include <algorithm>
-#include <cstdlib>
-#include <atomic>
 #include <map>
 #include <mutex>
 
@@ -287,10 +285,7 @@ struct SCfg { int WM, WN, VB; };
 // whole rounds of 256 workgroups (M = 64..512, 10^4..10^5 columns)
 static const SCfg kSCfgs[] = {{4, 2, 2}, {8, 1, 1}, {5, 2, 1}, {6, 2, 1}, {3, 2, 2}, {4, 2, 1}, {6, 1, 1}, {5, 1, 1},
                               {2, 2, 2}, {4, 1, 2}, {3, 1, 2}, {2, 1, 2}, {2, 2, 3}, {2, 1, 3}};
-static int forced_cfg() {  // NC_SCONV_CFG=i: only configuration i (timing experiments, tools/sconv_layers.py)
-  static const int v = getenv("NC_SCONV_CFG") ? atoi(getenv("NC_SCONV_CFG")) : -1;
-  return v;
-}
+static int forced_cfg() { return sw::raw(sw::SCONV_CFG); }  // NC_SCONV_CFG=i: only configuration i (timing experiments, tools/sconv_layers.py)
 
 // the plan of ONE tile configuration (ok = false: not applicable to this problem)
 SPlan plan_one(const SCfg& g, int B, int C, int M, int Hu, int Wu, int si, int rspan, int Wp, int nclass) {
@@ -347,21 +342,16 @@ struct TuneKey {
 };
 std::map<TuneKey, int> g_tuned;
 std::mutex g_tune_mu;
-int g_cfg_override = -1;  // nc_sconv_set_cfg (tests)
-std::atomic<int> g_tune_mode{-1};  // nc_sconv_set_tune: 0 never time (heuristic plan), 1 time on first use, -1 = NC_SCONV_TUNE (default 1)
-bool tune_on() {
-  const int m = g_tune_mode.load();
-  if (m >= 0) return m != 0;
-  static const bool on = !(getenv("NC_SCONV_TUNE") && atoi(getenv("NC_SCONV_TUNE")) == 0);
-  return on;
-}
+// nc_sconv_set_tune: 0 never time (heuristic plan), 1 time on first use, negative (default) = NC_SCONV_TUNE (default 1)
+bool tune_on() { return (sw::raw(sw::SCONV_TUNE_MODE) >= 0 ? sw::raw(sw::SCONV_TUNE_MODE) : sw::raw(sw::SCONV_TUNE)) != 0; }
 
 template <class L>
 int run_tuned(int dir, int B, int C, int M, int Hu, int Wu, int si, int rspan, int Wp, int nclass, hipStream_t s, L&& launch) {
   const int ncfg = (int)(sizeof(kSCfgs) / sizeof(kSCfgs[0]));
-  if (g_cfg_override >= 0 && g_cfg_override < ncfg) {
-    const SPlan pl = plan_one(kSCfgs[g_cfg_override], B, C, M, Hu, Wu, si, rspan, Wp, nclass);
-    if (!pl.ok) { set_error("sconv: configuration %d does not apply", g_cfg_override); return NC_ERR_SHAPE; }
+  const int pin = sw::raw(sw::SCONV_CFG_PIN);  // nc_sconv_set_cfg (tests)
+  if (pin >= 0 && pin < ncfg) {
+    const SPlan pl = plan_one(kSCfgs[pin], B, C, M, Hu, Wu, si, rspan, Wp, nclass);
+    if (!pl.ok) { set_error("sconv: configuration %d does not apply", pin); return NC_ERR_SHAPE; }
     return launch(pl);
   }
   if (forced_cfg() >= 0 || !tune_on()) {
@@ -813,8 +803,5 @@ int conv_dgrad_sconv(const float* dy, const float* w, float* dx, const ConvDims&
     return launch_sconv<2, 2, -1>(pl, p, max_ncol, 4, s);
   });
 }
-
-void sconv_set_cfg(int cfg) { g_cfg_override = cfg; }
-void sconv_set_tune(int on) { g_tune_mode = on; }
 
 }  // namespace nc

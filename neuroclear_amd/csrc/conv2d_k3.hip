@@ -13,7 +13,6 @@
 // Coverage: D == 1, kd == 1, kh == kw == 3, stride 1, padding 1; reduction side (C forward, K backward) even and >= 16; output side a multiple of
 // 64; any H, W, N; and enough tiles to fill the chip (k3_min_workgroups) -- smaller problems, the one-channel first layer and the weight gradient
 // stay on the gather GEMM (conv_gemm.hip).
-#include <atomic>
 
 #include "common.hpp"
 
@@ -221,9 +220,6 @@ K3Plan k3_plan_one(int ci, int B, int C, int M, int H, int W) {
   return pl;
 }
 
-std::atomic<int> g_k3_on{1};         // nc_set_conv2d_k3
-std::atomic<int> g_k3_cfg{-1};       // nc_conv2d_k3_set_cfg (tests): -1 = the heuristic
-
 // Below this many workgroups of the smallest tile (128 pixels x 64 channels) the problem does not give every one of the 256 CUs a workgroup, and
 // a workgroup walks its whole reduction alone where the gather GEMM splits it.  Every shape at or above the rule is measured faster than the
 // gather GEMM (profiles/unet2d_k3.txt); shapes below it were not measured on this kernel and stay where they were.
@@ -231,7 +227,7 @@ long k3_min_workgroups() { return 256; }
 
 // the heuristic: the 256-pixel tile (twice the operand reuse) once it still gives every CU two workgroups, else the 128-pixel tile
 K3Plan k3_plan(int B, int C, int M, int H, int W) {
-  const int forced = g_k3_cfg.load();
+  const int forced = sw::raw(sw::CONV2D_K3_CFG);
   if (forced >= 0 && forced < kK3NumCfgs) return k3_plan_one(forced, B, C, M, H, W);
   const K3Plan big = k3_plan_one(0, B, C, M, H, W);
   if (big.ok && big.wgs >= 512) return big;
@@ -264,7 +260,7 @@ int k3_run(const float* x, const float* w, const float* bias, float* y, int B, i
   const size_t need = ((size_t)C * M * 9 * sizeof(float) + 255) & ~(size_t)255;
   if (!ws || wsb < need) { set_error("conv2d_k3: workspace too small"); return NC_ERR_WS; }
   const K3Plan pl = k3_plan(B, C, M, H, W);
-  if (!pl.ok) { set_error("conv2d_k3: tile configuration %d does not apply", g_k3_cfg.load()); return NC_ERR_SHAPE; }
+  if (!pl.ok) { set_error("conv2d_k3: tile configuration %d does not apply", sw::raw(sw::CONV2D_K3_CFG)); return NC_ERR_SHAPE; }
   float* wp = (float*)ws;
   const long total = (long)C * M * 9;
   hipLaunchKernelGGL(k_pack_k3, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, C, sm, sc, total);
@@ -283,9 +279,6 @@ int k3_run(const float* x, const float* w, const float* bias, float* y, int B, i
 
 }  // namespace
 
-bool conv2d_k3_on() { return g_k3_on.load() != 0; }
-void conv2d_k3_set(int on) { g_k3_on = on ? 1 : 0; }
-int conv2d_k3_set_cfg(int cfg) { return g_k3_cfg.exchange(cfg); }
 int conv2d_k3_num_cfgs() { return kK3NumCfgs; }
 // forward: M = K output channels, reduction over C;  data gradient: M = C, reduction over K
 bool conv2d_k3_fwd_supported(const ConvDims& d) { return k3_shape_ok(d, d.C, d.K); }

@@ -5,7 +5,6 @@
 // channels, columns = 32 consecutive positions of one row group.  A workgroup stages the 3 x (R + 2) x (W + 2) input rows it needs
 // (zero padded) in LDS; a tap is then a constant offset of a lane's position; the weights of a wave's 64 output channels live in 28
 // registers.  fp32 products, fp32 accumulation: the arithmetic of the kernel it replaces, in a different summation order.
-#include <cstdlib>
 
 #include "common.hpp"
 
@@ -161,7 +160,7 @@ __global__ void __launch_bounds__(256) k_c1k3_stats_final(const float2* __restri
 }  // namespace
 
 bool c1k3_fwd_supported(const ConvDims& d) {
-  static const bool on = !(getenv("NC_C1K3") && atoi(getenv("NC_C1K3")) == 0);  // A/B switch: the general brick kernel
+  const bool on = sw::raw(sw::C1K3) != 0;  // A/B switch: the general brick kernel
   if (!on || d.C != 1 || d.K % 64 || d.kd != 3 || d.kh != 3 || d.kw != 3) return false;
   if (d.sd != 1 || d.sh != 1 || d.sw != 1 || d.pd != 1 || d.ph != 1 || d.pw != 1) return false;
   // the smallest tile (one output row: 3 planes x 3 rows of W + 2 floats) has to fit the 48 KB the launch stays within

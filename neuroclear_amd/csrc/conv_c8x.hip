@@ -25,8 +25,6 @@
 //     many YOUNGER operations may stay in flight -- the 8 fragment loads of steps s + 1 / s + 2, the DMA pieces the step before
 //     issued, the 32 stores of a tile that just ended.  A brick therefore has two k-steps (and its ring distance) to arrive.
 // Weights are rounded to the 16-bit type at packing (round to nearest, or tap-diffused for deep_linear_gen: conv_h.hip).
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.hpp"
@@ -626,20 +624,9 @@ CPlan c_plan(int N, int D, int H, int W, int Kout, int KS) {
   return pl;
 }
 
-std::atomic<int> g_c8x_mode{-1};
-int c8x_mode() {  // 0 = off (k_conv_h everywhere), 1 = where the launch fills >= 60 % of its rounds of 512 workgroups (default), 2 = wherever the shape fits
-  int m = g_c8x_mode.load(std::memory_order_relaxed);
-  if (m < 0) {
-    m = getenv("NC_C8X") ? atoi(getenv("NC_C8X")) : 1;
-    g_c8x_mode.store(m, std::memory_order_relaxed);
-  }
-  return m;
-}
+// sw::C8X: 0 = off (k_conv_h everywhere), 1 = where the launch fills >= 60 % of its rounds of 512 workgroups (default), 2 = wherever the shape fits
 
 }  // namespace
-
-void c8x_set_mode(int m) { g_c8x_mode.store(m < 0 ? 0 : m > 2 ? 2 : m, std::memory_order_relaxed); }
-int c8x_get_mode() { return c8x_mode(); }
 
 size_t c8x_packed_bytes(int Cin, int Kout, int KS) {
   const int NS = KS * KS * KS * (Cin / 8) / 4;
@@ -648,7 +635,7 @@ size_t c8x_packed_bytes(int Cin, int Kout, int KS) {
 
 // Cin / Kout: channels of the tensor read / written by THIS call (the data gradient swaps the layer's)
 bool c8x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS, bool fp32_out) {
-  if (!c8x_mode() || (KS != 3 && KS != 5)) return false;
+  if (!sw::raw(sw::C8X) || (KS != 3 && KS != 5)) return false;
   if (Cin % (KS == 3 ? 32 : 64) || Kout % 64) return false;  // whole k-steps ((Cin / 8) * KS^3 taps in fours): 3^3 a multiple of three, 5^3 an even number
   const long S = (long)D * H * W;
   if (S * 16 >= (1l << 31)) return false;  // byte offsets inside one 8-channel block stay below the out-of-range mark
@@ -657,12 +644,12 @@ bool c8x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS, bool f
   // 5^3: k_conv_h's pair mode (26 taps x 8 channels per stage, weights shared through LDS by all eight waves, MFMA busy 0.72) is the
   // better kernel in the step -- same-box A/B of the configs[3] step, profiles/r04_ab_c8x.txt: 1,340-1,400 against 1,200-1,300 TFLOP/s --
   // and gives the same bits; the tap-stream kernel takes 5^3 only on request (mode 2: tests, timing)
-  if (KS == 5 && c8x_mode() < 2) return false;
+  if (KS == 5 && sw::raw(sw::C8X) < 2) return false;
   const CPlan pl = c_plan(N, D, H, W, Kout, KS);
   if (!pl.ok) return false;
   // launches that fill only a fraction of ONE round of 512 workgroups (a few planes) run better on k_conv_h's 256-position tiles; from
   // about 60 % on the tap-stream kernel is ahead on every shape measured (tools/c8x_time.py: 1.1-1.2 x at 37^3 ... 148^3)
-  return c8x_mode() >= 2 || pl.eff >= 0.6;
+  return sw::raw(sw::C8X) >= 2 || pl.eff >= 0.6;
 }
 
 // xh: C8 input; w: fp32 master weights; exactly one of y (fp32 NCDHW) / yh (C8, channels [c0, c0 + Kout) of ctot); wp_ws: >=

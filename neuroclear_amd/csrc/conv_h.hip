@@ -20,7 +20,6 @@
 // wait for the DMA: vmcnt retires in order).  Two stage buffers; the DMA of stage s+1 flies under the MFMAs of s.
 // Tile = 64 output channels x PT flattened positions of one output plane; 8 waves x (2 x VB) accumulator tiles.
 // Persistent workgroups walk XCD-contiguous tile ranges (neighbouring planes share input planes in that XCD's L2).
-#include <cstdlib>
 
 #include "common.hpp"
 
@@ -601,8 +600,7 @@ int run_h(const float* x, const void* xh_pre, const float* w, const float* bias,
   p.npb = pl.npb; p.npw = pl.npw; p.SB = pl.SB;
   p.ntiles = (long)d.N * d.D * pl.TPP * p.KT;
   p.tiles_per_xcd = (int)cdiv(p.ntiles, 8);
-  static const int ablate = getenv("NC_H_ABLATE") ? atoi(getenv("NC_H_ABLATE")) : 0;
-  p.ablate = ablate;
+  p.ablate = sw::raw(sw::H_ABLATE);
   const int lds = 2 * pl.SB;
   if (na1) {
     if (KS != 5 || Kout != 64 || yh) { set_error("conv_h: the 32-channel form exists for 5^3, one 64-channel tile, fp32 output"); return NC_ERR_SHAPE; }
@@ -1042,8 +1040,7 @@ int run_wh(const float* x, const void* xh_pre, const float* dy, const void* dyh_
   p.PT = pl.PT; p.PTp = pl.PTp; p.NK = pl.NK; p.npx = pl.npx; p.npd = pl.npd; p.xslot = pl.xslot; p.dybuf = pl.dybuf;
   p.nct = d.C / 32; p.npairs = npairs; p.nwp = nwp; p.steps = steps;
   p.mTx = magic(pl.Tx); p.mXp = magic(pl.Xp); p.mXUp = magic(pl.XUp); p.mPTp = magic(pl.PTp);
-  static const int ablate = getenv("NC_H_ABLATE") ? atoi(getenv("NC_H_ABLATE")) : 0;
-  p.ablate = ablate;
+  p.ablate = sw::raw(sw::H_ABLATE);
   if (int e = raise_dyn_lds((k_wgrad_h<DT, 3>), kLdsMaxH, "wgrad_h")) return e;
   if (int e = raise_dyn_lds((k_wgrad_h<DT, 5>), kLdsMaxH, "wgrad_h")) return e;
   const int lds = NS * pl.xslot + 2 * pl.dybuf;
@@ -1059,8 +1056,7 @@ int run_wh(const float* x, const void* xh_pre, const float* dy, const void* dyh_
 }  // namespace
 
 void h_set_weight_diffusion(int on) {
-  static const bool allowed = !(getenv("NC_W_DIFFUSE") && atoi(getenv("NC_W_DIFFUSE")) == 0);  // A/B switch
-  g_wdiffuse = on && allowed;
+  g_wdiffuse = on && sw::raw(sw::W_DIFFUSE);  // (NC_W_DIFFUSE=0: A/B switch)
 }
 
 bool h_fwd_supported(const ConvDims& d) { return h_shape_ok(d, d.C, d.K); }

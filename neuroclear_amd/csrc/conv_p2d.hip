@@ -20,10 +20,8 @@
 // (1.09), data gradient 0.83 (1.49); 128 -> 256 stride 2 0.33 (0.43) / 0.33 (0.46); 64 -> 128 stride 2 0.37 (0.42) / 0.39 (0.48) -- the
 // stride-2 figures include the space-to-depth / padding conversion, a third of their time at 64 channels; error against fp64 2e-7 of the rms
 // (k_sconv: 5e-7 .. 1.5e-6).  Athena step 101.7 -> 87.2 ms.  The weight gradients of these layers stay on k_swgrad.
-#include <cstdlib>
 #include <type_traits>
 
-#include <atomic>
 
 #include "common.hpp"
 #include "s3_common.hpp"
@@ -603,16 +601,11 @@ int launch_p_ncb(int NCB, const PParams& p, int lds, hipStream_t s) {
 // (tests/test_gpu_fullsize.py::test_athena_step_108_streams_tuner_and_shared_pass_agree runs that comparison in mode 3 and holds mode 1 to fp32
 // rounding).  No range guard here: the layer's input is an InstanceNorm2d + LeakyReLU output (bounded by sqrt(H W)), its dY the norm backward's
 // output, whose per-plane scale is the plane's rstd <= 1 / sqrt(eps) = 316 -- a spread far inside the 2^17 a two-term tensor carries.
-static std::atomic<int> g_p2d_terms{getenv("NC_P2D_TERMS") ? atoi(getenv("NC_P2D_TERMS")) : 1};
 int p2_terms(int kind) {
-  const int mode = g_p2d_terms.load(std::memory_order_relaxed);
+  const int mode = sw::raw(sw::P2D_TERMS);
   if (mode == 2) return 2;
-  return mode == 1 && kind == 0 && s3x_get_terms() == 2 ? 2 : 3;
+  return mode == 1 && kind == 0 && sw::get(sw::SPLIT_TERMS) == 2 ? 2 : 3;
 }
-}  // namespace
-void p2d_set_terms(int m) { g_p2d_terms.store(m == 1 || m == 2 ? m : 3, std::memory_order_relaxed); }
-int p2d_get_terms() { return g_p2d_terms.load(std::memory_order_relaxed); }
-namespace {
 
 size_t p2_packed_bytes(int NS, int Kout, int NT = 3) { return (size_t)(Kout / 64) * 2 * NS * 2 * NT * 1024; }
 size_t p2_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -658,7 +651,7 @@ P2Geom p2_geom(const ConvDims& d, int dgrad) {
 }
 
 bool p2_shape(const ConvDims& d, int dgrad) {
-  static const int on = getenv("NC_P2D") ? atoi(getenv("NC_P2D")) : 7;  // A/B switch: bit 0 = the stride-1 layer, bit 1 = the stride-2 layers; 0: the image-staged fp32 kernels of conv2d_img.hip
+  const int on = sw::raw(sw::P2D);  // A/B switch: bit 0 = the stride-1 layer, bit 1 = the stride-2 layers; 0: the image-staged fp32 kernels of conv2d_img.hip
   if (d.D != 1 || d.kd != 1 || d.kh != 4 || d.kw != 4 || d.sh != d.sw || (d.sh != 1 && d.sh != 2) || d.ph != 1 || d.pw != 1) return false;
   if (!(on & (d.sh == 1 ? 1 : 2))) return false;
   const P2Geom g = p2_geom(d, dgrad);

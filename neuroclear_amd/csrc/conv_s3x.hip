@@ -34,8 +34,6 @@
 // instead of six and three, bricks of two terms; everything else unchanged.  64 -> 64 at 108^3: 3^3 1.14 -> 0.67 ms, 5^3 4.67 -> 2.63 ms,
 // error against fp64 as the three-term form's (tests/test_gpu_h2.py).  A forward input may be a concatenation whose halves were converted
 // with different powers of two: the ratio is folded into the weights of the second half's input channels when they are packed.
-#include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.hpp"
@@ -1154,11 +1152,6 @@ bool x_brick(int PT, int P, int KS, int NT, int& UB, int& npb, int& lds, bool pc
   return npb <= kMaxPieces && lds + (NT == 2 ? kOffTab : 0) <= kLdsMax;
 }
 
-int x_tail_mode() {  // NC_S3X_TAIL=0: the left-over tiles run as one more round of whole tiles (A/B)
-  static const int m = getenv("NC_S3X_TAIL") ? atoi(getenv("NC_S3X_TAIL")) : 1;
-  return m;
-}
-
 XPlan x_plan(int N, int D, int H, int W, int KT, int KS, int NT = 3, bool k32 = false, bool pc = false) {
   XPlan best{};
   double best_cost = 1e30;
@@ -1168,8 +1161,7 @@ XPlan x_plan(int N, int D, int H, int W, int KT, int KS, int NT = 3, bool k32 = 
   for (int NCB : {8, 7, 6, 4, 2}) {
     if (NCB > ncb_max) continue;
     if (k32 && NCB != 4 && NCB != 2) continue;  // (32-channel tiles: the instantiated shapes; a tile is 128 NCB positions)
-    static const int odd_ok = getenv("NC_S3X_NCB7") ? atoi(getenv("NC_S3X_NCB7")) : 1;  // NC_S3X_NCB7=0: even column-block counts only (A/B)
-    if ((NCB & 1) && !odd_ok) continue;
+    if ((NCB & 1) && !sw::raw(sw::S3X_NCB7)) continue;  // NC_S3X_NCB7=0: even column-block counts only (A/B)
     XPlan pl{};
     pl.NCB = NCB; pl.P = P; pl.HP = (int)HP;
     const int PT = (k32 ? 128 : 64) * NCB;
@@ -1184,7 +1176,7 @@ XPlan x_plan(int N, int D, int H, int W, int KT, int KS, int NT = 3, bool k32 = 
     pl.fsub = 1;
     if (pl.rem) {
       int f = 1;  // the left-over tiles in quarters / thirds / halves (8, 6, 4 -> 2 or 4 column blocks per wave) when they then fit one round
-      if (x_tail_mode() && NCB > 2 && NCB % 2 == 0) {
+      if (sw::raw(sw::S3X_TAIL) && NCB > 2 && NCB % 2 == 0) {
         if (pl.rem * (NCB / 2) <= 256) f = NCB / 2;
         else if (NCB == 8 && pl.rem * 2 <= 256) f = 2;
       }
@@ -1208,14 +1200,9 @@ int launch_x(const XParams& p, int lds, hipStream_t s) {
 
 // the W64 form (k_conv_s3w) takes a launch of whole 512-position tiles of a 3^3 layer whose k-steps per tile are a multiple of the weight ring
 // (every multiple of 64 input channels) when its LDS fits.  NC_S3X_W64=0: k_conv_s3x everywhere (A/B, tests)
-static std::atomic<int> g_w64{getenv("NC_S3X_W64") ? atoi(getenv("NC_S3X_W64")) : 1};
 bool w64_applies(int KS, int NCB, int NS, int lds) {
-  return g_w64.load(std::memory_order_relaxed) && KS == 3 && NCB == 8 && NS % kWA == 0 && NS >= 12 && lds + kOffTab + kWExtra <= kLdsMax;
+  return sw::raw(sw::S3X_W64) && KS == 3 && NCB == 8 && NS % kWA == 0 && NS >= 12 && lds + kOffTab + kWExtra <= kLdsMax;
 }
-}  // namespace
-void s3x_w64_set(int on) { g_w64.store(on ? 1 : 0, std::memory_order_relaxed); }
-int s3x_w64_get() { return g_w64.load(std::memory_order_relaxed); }
-namespace {
 template <bool ST>
 int launch_w64(const XParams& p, int lds, hipStream_t s) {
   auto kern = k_conv_s3w<ST>;
@@ -1307,10 +1294,6 @@ __global__ void __launch_bounds__(256) k_s3x_stats_final(const double2* __restri
 
 // 0: off; 1 (default): in the inference forward; 2: in the training forward too (measured: no gain there -- 33.95-34.08 against 33.83-34.01 ms per
 // step, the eight k_in_stats passes it removes cost what the epilogue and the two finalisation launches cost -- so it stays a tested option)
-static std::atomic<int> g_epi_stats{getenv("NC_EPI_STATS") ? atoi(getenv("NC_EPI_STATS")) : 1};
-bool epi_stats_on() { return g_epi_stats.load(std::memory_order_relaxed) != 0; }
-int epi_stats_mode() { return g_epi_stats.load(std::memory_order_relaxed); }
-void epi_stats_set(int on) { g_epi_stats.store(on < 0 ? 0 : on > 2 ? 2 : on, std::memory_order_relaxed); }
 
 // k-steps of a tile: its KS^3 * Cin / 8 taps in fours, made EVEN (the kernel alternates two sets of weight registers per step and a tile must
 // end where it began): channels % 64 give an even count by themselves; 32 channels (two-term launches only: deep_linear_gen's rank-structured
@@ -1328,9 +1311,7 @@ size_t s3x_packed_bytes(int Cin, int Kout, int KS, int NT) {
 // fp32 product; s3_common.hpp, h2.hip) or the three-term bf16 form (six).  2 (default): two-term wherever it exists -- forward, data gradient
 // and weight gradient, layer by layer and in the whole-network training / inference calls; 3: three-term everywhere; 0: two-term in the
 // inference forward nc_unet_deconv_fwd only.  The explicit S3 entry points (nc_conv_*_split, nc_to_s3) are three-term by definition.
-static std::atomic<int> g_terms{getenv("NC_SPLIT_TERMS") ? atoi(getenv("NC_SPLIT_TERMS")) : 2};
-void s3x_set_terms(int t) { g_terms = (t == 0 || t == 3) ? t : 2; }
-int s3x_get_terms() { const int f = frozen_terms(); return f >= 0 ? f : g_terms.load(); }  // (inside a call: the value sampled when the call began)
+// (sw::SPLIT_TERMS; inside a call: the value sampled when the call began)
 
 bool s3x_k32_supported(int N, int D, int H, int W) { return x_plan(N, D, H, W, 1, 5, 2, true).ok && (long)32 * D * H * W * 4 < (1l << 31); }
 bool s3x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS) {
@@ -1380,12 +1361,12 @@ int conv_s3x_h2(const void* xs, const unsigned* cell_a, const unsigned* cell_b, 
   p.N = N; p.NCH = NCH; p.D = D; p.H = H; p.W = W; p.K = Kout;
   p.P = pl.P; p.HP = pl.HP; p.TPP = pl.TPP; p.KT = k32 ? 1 : Kout / 64;
   p.NS = NS; p.mP = magic(pl.P);
-  static const int flush = getenv("NC_S3X_FLUSH") ? atoi(getenv("NC_S3X_FLUSH")) : 4;
+  const int flush = sw::raw(sw::S3X_FLUSH);
   p.flush = flush >= 4 ? flush : flush > 0 ? 4 : 1 << 30;
   // With the W64 form switched on, EVERY two-term 3^3 launch keeps one running accumulator per tile (k_conv_s3w has no second set to restart
   // into): an output element's bits then do not depend on which kernel or which launch (whole tiles / the fractional tiles of the tail, and so
   // on the batch a cube travels in) its tile fell to -- same products, same order, tot = 0 + acc exactly.
-  if (KS == 3 && !k32 && s3x_w64_get()) p.flush = 1 << 30;
+  if (KS == 3 && !k32 && sw::raw(sw::S3X_W64)) p.flush = 1 << 30;
   const bool one = pl.rem && pl.fsub == 1;
   if (pl.full || one) {
     p.fsub = 1; p.UB = pl.UB; p.npb = pl.npb; p.mUB = magic(pl.UB);
@@ -1419,8 +1400,7 @@ static size_t c1k7_al(size_t b) { return (b + 255) & ~(size_t)255; }
 static constexpr int kC1k7Steps = 14;  // 7 bricks of eight (dz, dy) tap slots, in fours
 static size_t c1k7_packed_bytes() { return (size_t)2 * kC1k7Steps * 4 * 1024; }
 bool c1k7_h2_supported(const ConvDims& d) {
-  static const int on = getenv("NC_C1K7_H2") ? atoi(getenv("NC_C1K7_H2")) : 1;  // NC_C1K7_H2=0: the fp32 matrix kernel (A/B)
-  if (!on || s3x_get_terms() != 2) return false;
+  if (!sw::raw(sw::C1K7_H2) || sw::get(sw::SPLIT_TERMS) != 2) return false;  // NC_C1K7_H2=0: the fp32 matrix kernel (A/B)
   if (d.C != 1 || d.K != 64 || d.kd != 7 || d.kh != 7 || d.kw != 7 || d.sd != 1 || d.sh != 1 || d.sw != 1 || d.pd != 3 || d.ph != 3 || d.pw != 3) return false;
   const long S = (long)d.D * d.H * d.W;
   if (d.W < 4 || (long)64 * S * 4 >= (1l << 31) || S * 32 >= (1l << 31)) return false;
@@ -1451,7 +1431,7 @@ int conv_c1k7_h2(const float* x, const float* w, const float* bias, float* y, co
   if (int e = h2_zero_cells(cells, 2, s)) return e;
   if (int e = h2_absmax(x, (long)d.N * S, cells, s)) return e;
   if (int e = h2_absmax(w, (long)64 * 343, cells + 1, s)) return e;
-  const bool guard = h2_guard_on();
+  const bool guard = sw::get(sw::H2_GUARD) != 0;
   if (guard) if (int e = h2_guard_zero(gw, s, 4)) return e;
   {
     long bx = cdiv(S, 256);
@@ -1513,7 +1493,7 @@ int conv_c1k7_h2_dgrad(const float* dy, const float* w, float* dx, const ConvDim
   if (int e = h2_zero_cells(cells, 2, s)) return e;
   if (int e = h2_absmax(dy, (long)d.N * 64 * S, cells, s)) return e;
   if (int e = h2_absmax(w, (long)64 * 343, cells + 1, s)) return e;
-  const bool guard = h2_guard_on();
+  const bool guard = sw::get(sw::H2_GUARD) != 0;
   if (guard) if (int e = h2_guard_zero(gw, s, 4)) return e;
   if (int e = split2h_into(dy, 64 * S, dyh, d.N, 64, S, 64, 0, cells, s, guard ? gw : nullptr)) return e;
   if (guard) if (int e = h2_guard_decide(gw, nullptr, nullptr, gw + kGuardFlag, false, s)) return e;  // counted, never switched
@@ -1588,7 +1568,7 @@ int conv_s3x(const void* xs, const float* w, const float* bias, float* y, int N,
 #ifdef NC_S3X_STAMP
   p.dbg = (long long*)((char*)wp_ws + s3x_packed_bytes(Cin, Kout, KS));  // (the workspace has slack behind the packed weights in the timing tool)
 #endif
-  static const int flush = getenv("NC_S3X_FLUSH") ? atoi(getenv("NC_S3X_FLUSH")) : 4;
+  const int flush = sw::raw(sw::S3X_FLUSH);
   p.flush = flush >= 4 ? flush : flush > 0 ? 4 : 1 << 30;  // >= 4: the previous tile's sums leave `tot` during the first four k-steps
   const bool one = pl.rem && pl.fsub == 1;  // the left-over tiles are whole tiles: one launch, some workgroups take one tile more
   if (pl.full || one) {

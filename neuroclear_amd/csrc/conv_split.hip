@@ -23,7 +23,6 @@
 // Accuracy: the matrix core's rounding error grows with the running sum in its accumulator, so the accumulators restart per
 // stage group (forward / dgrad) or every 64 steps (wgrad) and the pieces are added in fp32 -- with that the error against fp64
 // is below the fp32 MFMA kernels' at every shape tested ("Split-operand fp32 convolutions").
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.hpp"
@@ -549,8 +548,7 @@ int run_s3(const float* x, const void* xs_pre, const float* w, const float* bias
     if (int e = check_launch("split3")) return e;
   }
   // the tap-stream kernel (conv_s3x.hip: 16x16x32 MFMAs, no zero tap) takes every shape it covers; NC_S3X=0: the pair kernel below
-  static const int use_x = getenv("NC_S3X") ? atoi(getenv("NC_S3X")) : 1;
-  if (use_x && s3x_supported(d.N, Cin, d.D, d.H, d.W, Kout, KS) && s3x_packed_bytes(Cin, Kout, KS) <= wb)
+  if (sw::raw(sw::S3X) && s3x_supported(d.N, Cin, d.D, d.H, d.W, Kout, KS) && s3x_packed_bytes(Cin, Kout, KS) <= wb)
     return conv_s3x(xs, w, bias, y, d.N, Cin, d.D, d.H, d.W, Kout, KS, so, si, flip, wp, s);
   const long total = (long)(s_packed_bytes(Cin, Kout, KS) / 2);
   hipLaunchKernelGGL(k_pack_w_s3, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, s, w, wp, Cin / 8, KS, so, si, flip, total);
@@ -1163,10 +1161,8 @@ struct WsPlan {
 
 int pad_4mod8(int v) { return v + ((4 - (v & 7)) & 7); }  // sub-block stride that keeps the transposed reads conflict-free
 
-int ws_kstep() {  // voxels per k-step: 32 = the 16x16x32 kernel (default), 16 = the 32x32x16 kernel (NC_S3X_WGRAD=0)
-  static const int x = getenv("NC_S3X_WGRAD") ? atoi(getenv("NC_S3X_WGRAD")) : 1;
-  return x ? 32 : 16;
-}
+// voxels per k-step: 32 = the 16x16x32 kernel (default), 16 = the 32x32x16 kernel (NC_S3X_WGRAD=0)
+int ws_kstep() { return sw::raw(sw::S3X_WGRAD) ? 32 : 16; }
 
 // k_wgrad_s3x addresses a (sample, k-tile)'s 8 NT sub-blocks through one buffer descriptor with 32-bit offsets (bit 31 = "padding")
 int ws_kv(const ConvDims& d, int NT = 3) { return (NT == 1 || ws_kstep() == 32) && (long)d.D * d.H * d.W * 128 * NT < (1l << 31) ? 32 : 16; }
@@ -1200,11 +1196,9 @@ WsPlan ws_plan(const ConvDims& d, int NT = 3) {
   return best;
 }
 
-static thread_local int tl_force3 = 0;
 bool s3_layer_h2(const ConvDims& d) {
-  if (s3x_get_terms() != 2 || tl_force3) return false;
-  static const int use_x = getenv("NC_S3X") ? atoi(getenv("NC_S3X")) : 1;  // (NC_S3X=0 / NC_S3X_WGRAD=0: the round-2 kernels, three-term only)
-  if (!use_x) return false;
+  if (sw::get(sw::SPLIT_TERMS) != 2 || force_three_term()) return false;
+  if (!sw::raw(sw::S3X)) return false;  // (NC_S3X=0 / NC_S3X_WGRAD=0: the round-2 kernels, three-term only)
   if (d.kd != d.kh || d.kd != d.kw || (d.kd != 3 && d.kd != 5) || d.sd != 1 || d.sh != 1 || d.sw != 1 || d.pd != d.kd / 2 || d.ph != d.pd || d.pw != d.pd)
     return false;
   if (d.C % 64 || d.K % 64 || (d.K / 64) * (d.C / 32) * (d.kd == 5 ? 5 : 1) > 256) return false;
@@ -1429,8 +1423,7 @@ int run_wsx(const void* xh, const void* dyh, float* dw, const ConvDims& d, void*
 }  // namespace
 
 bool c8x_wgrad_supported(const ConvDims& d) {
-  static const int on = getenv("NC_HX_WGRAD") ? atoi(getenv("NC_HX_WGRAD")) : 1;  // NC_HX_WGRAD=0: conv_h.hip's k_wgrad_h (A/B)
-  return on && wsx_shape_ok(d);
+  return sw::raw(sw::HX_WGRAD) && wsx_shape_ok(d);  // NC_HX_WGRAD=0: conv_h.hip's k_wgrad_h (A/B)
 }
 size_t c8x_wgrad_part_bytes(const ConvDims& d) {
   const int T3 = d.kd * d.kh * d.kw, TW = d.kd == 3 ? 27 : 25;
@@ -1469,7 +1462,7 @@ int conv_wgrad_s3(const float* x, const void* xs, const float* dy, const void* d
 // The two-term forward kernel on an fp32 input of 32 x n channels (converted here, measured cell, guard counted): deep_linear_gen's
 // rank-structured data gradient (gen_nets.hip) -- s3_layer_h2 admits multiples of 64 only
 bool conv_fwd_h2_c32_supported(const ConvDims& d) {
-  if (s3x_get_terms() != 2 || d.C % 32 || d.K % 64 || d.kd != d.kh || d.kd != d.kw || (d.kd != 3 && d.kd != 5)) return false;
+  if (sw::get(sw::SPLIT_TERMS) != 2 || d.C % 32 || d.K % 64 || d.kd != d.kh || d.kd != d.kw || (d.kd != 3 && d.kd != 5)) return false;
   if (d.sd != 1 || d.sh != 1 || d.sw != 1 || d.pd != d.kd / 2 || d.ph != d.pd || d.pw != d.pd) return false;
   return s3x_supported(d.N, 64, d.D, d.H, d.W, d.K, d.kd);  // (the planner does not look at the input channels)
 }
@@ -1485,7 +1478,7 @@ int conv_fwd_h2_c32(const float* x, const float* w, float* y, const ConvDims& d,
 // The two-term 5^3 forward onto 32 output channels (k_conv_s3x K32), x converted into xs_keep as conv_fwd_keep does (measured cell, guard
 // counted, no fallback): deep_linear_gen's collapsed forward, which wants 27 channels of layer 1's output space and never the 64 (gen_nets.hip)
 bool conv_fwd_h2_k32_supported(const ConvDims& d) {
-  if (s3x_get_terms() != 2 || d.C % 64 || d.K != 32 || d.kd != 5 || d.kh != 5 || d.kw != 5 || d.sd != 1 || d.sh != 1 || d.sw != 1 || d.pd != 2 || d.ph != 2 || d.pw != 2)
+  if (sw::get(sw::SPLIT_TERMS) != 2 || d.C % 64 || d.K != 32 || d.kd != 5 || d.kh != 5 || d.kw != 5 || d.sd != 1 || d.sh != 1 || d.sw != 1 || d.pd != 2 || d.ph != 2 || d.pw != 2)
     return false;
   return s3x_k32_supported(d.N, d.D, d.H, d.W);
 }
@@ -1495,7 +1488,7 @@ int conv_fwd_h2_k32_keep(const float* x, const float* w, float* y, const ConvDim
 }
 // The two-term weight-gradient kernel on operands of the caller's choice (x / dy fp32, or xs / dys H2 tensors with their cells): any C % 32,
 // K % 64 the plan covers -- not only the layers s3_layer_h2 admits (deep_linear_gen's collapsed backward uses C = 32, gen_nets.hip)
-bool wgrad_h2_supported(const ConvDims& d) { return s3x_get_terms() == 2 && ws_shape_ok(d) && ws_kv(d, 2) == 32 && ws_plan(d, 2).ok && ws_part_bytes(d, 2) != 0; }
+bool wgrad_h2_supported(const ConvDims& d) { return sw::get(sw::SPLIT_TERMS) == 2 && ws_shape_ok(d) && ws_kv(d, 2) == 32 && ws_plan(d, 2).ok && ws_part_bytes(d, 2) != 0; }
 int conv_wgrad_h2(const float* x, const void* xs, const float* dy, const void* dys, float* dw, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
   if (!wgrad_h2_supported(d)) { set_error("conv_wgrad_h2: shape not covered"); return NC_ERR_SHAPE; }
   return run_ws_h2(x, xs, dy, dys, dw, d, ws, wsb, s, nullptr);
@@ -1601,25 +1594,6 @@ int act_operand(const ConvDims& d, const float* x, const float* mean, const floa
   return act_split2h(x, mean, rstd, slope, y, ystride, ys, N, C, S, ctot, c0, sqrtf((float)S), mine, C == ctot ? cells + 1 : nullptr, s);
 }
 bool conv_layer_h2(const ConvDims& d) { return s3_layer_h2(d); }
-static thread_local int tl_net_depth = 0;
-static thread_local int tl_sw_depth = 0, tl_sw_terms = -1, tl_sw_guard = -1, tl_sw_fold = -1, tl_sw_stream = -1;
-SwitchScope::SwitchScope() {
-  if (tl_sw_depth++ == 0) { tl_sw_terms = s3x_get_terms(); tl_sw_guard = h2_guard_mode(); tl_sw_fold = in_bwd_fold_raw(); tl_sw_stream = stream_passes_raw(); }
-}
-SwitchScope::~SwitchScope() {
-  if (--tl_sw_depth == 0) { tl_sw_terms = -1; tl_sw_guard = -1; tl_sw_fold = -1; tl_sw_stream = -1; }
-}
-ForceTwoTerm::ForceTwoTerm() : prev_terms(tl_sw_terms), prev_depth(tl_sw_depth) { tl_sw_terms = 2; ++tl_sw_depth; }
-ForceTwoTerm::~ForceTwoTerm() { tl_sw_terms = prev_terms; --tl_sw_depth; if (tl_sw_depth == 0) { tl_sw_terms = -1; tl_sw_guard = -1; tl_sw_fold = -1; tl_sw_stream = -1; } }
-int frozen_terms() { return tl_sw_terms; }
-int frozen_guard() { return tl_sw_guard; }
-int frozen_fold() { return tl_sw_fold; }
-int frozen_stream() { return tl_sw_stream; }
-NetworkScope::NetworkScope() { ++tl_net_depth; if (tl_sw_depth++ == 0) { tl_sw_terms = s3x_get_terms(); tl_sw_guard = h2_guard_mode(); tl_sw_fold = in_bwd_fold_raw(); tl_sw_stream = stream_passes_raw(); } }
-NetworkScope::~NetworkScope() { --tl_net_depth; if (--tl_sw_depth == 0) { tl_sw_terms = -1; tl_sw_guard = -1; tl_sw_fold = -1; tl_sw_stream = -1; } }
-bool h2_guard_can_flip() { return h2_guard_mode() == 2 || (h2_guard_mode() == 1 && tl_net_depth == 0); }
-ForceThreeTerm::ForceThreeTerm() { ++tl_force3; }
-ForceThreeTerm::~ForceThreeTerm() { --tl_force3; }
 
 int conv_fwd_s3(const float* x, const void* xs, const float* w, const float* b, float* y, const ConvDims& d, void* ws, size_t wsb,
                 hipStream_t s, void* xs_keep, float* stats_part, const S3xPrepared* prep) {

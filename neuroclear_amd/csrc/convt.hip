@@ -280,7 +280,7 @@ namespace nc {
 bool convT_fwd_s3_supported(int N, int C, int D, int H, int W, int K) {
   static const bool mfma_on = true;
   const long S = (long)D * H * W;
-  return mfma_on && !g_force_direct && K % 32 == 0 && C == 128 && (long)N * K * 8 * S < (1L << 40);
+  return mfma_on && !sw::raw(sw::FORCE_DIRECT) && K % 32 == 0 && C == 128 && (long)N * K * 8 * S < (1L << 40);
 }
 static int convT_fwd_impl(const float* x, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K,
                           void* ys, int ctot, int c0, void* stream);
@@ -307,7 +307,7 @@ static int nc::convT_fwd_impl(const float* x, const float* w, const float* bias,
   hipStream_t s = (hipStream_t)stream;
   static const bool mfma_on = true;  // A/B switch
   // (measured: 128 -> 64 at 70^3 0.77 -> 0.55 ms, at 54^3 0.34 -> 0.28; 256 -> 128 at 35^3 0.30 -> 0.36: the VALU kernel keeps it)
-  if (mfma_on && !g_force_direct && K % 32 == 0 && C == 128 && (long)N * K * 8 * S < (1L << 40)) {
+  if (mfma_on && !sw::raw(sw::FORCE_DIRECT) && K % 32 == 0 && C == 128 && (long)N * K * 8 * S < (1L << 40)) {
     long gx = cdiv(cdiv(S, 32) * N, 4);
     const long cap = cdiv(2048, 2 * (K / 32));
     if (gx > cap) gx = cap;
@@ -338,7 +338,7 @@ int nc_convT_k2s2_dgrad(const float* dy, const float* w, float* dx, int N, int C
   if (!dy || !w || !dx) { set_error("convT_dgrad: null pointer"); return NC_ERR_ARG; }
   if (int e = convT_check("convT_dgrad", N, C, D, H, W, K)) return e;
   ConvDims cd;
-  if (!g_force_direct && C >= 64 && convT_as_conv(cd, N, C, D, H, W, K) && gemm_fwd_supported(cd) &&
+  if (!sw::raw(sw::FORCE_DIRECT) && C >= 64 && convT_as_conv(cd, N, C, D, H, W, K) && gemm_fwd_supported(cd) &&
       (gemm_ws_bytes(cd) == 0 || (ws && ws_bytes >= gemm_ws_bytes(cd)))) {
     // dx[ci][pos] = sum_(co, t) w[ci][co][t] * dy[co][2 pos + t]  ==  the FORWARD pass of Conv3d(K -> C, k 2, s 2, p 0) on dy
     // with the transposed-conv weight read as [C][K][2][2][2]: MFMA gather GEMM (60-70 TFLOP/s) instead of the VALU
@@ -361,7 +361,7 @@ int nc_convT_k2s2_wgrad(const float* x, const float* dy, float* dw, float* dbias
   if (int e = convT_check("convT_wgrad", N, C, D, H, W, K)) return e;
   hipStream_t s = (hipStream_t)stream;
   ConvDims cd;
-  if (!g_force_direct && convT_as_conv(cd, N, C, D, H, W, K) && ws && ws_bytes >= gemm_ws_bytes(cd)) {
+  if (!sw::raw(sw::FORCE_DIRECT) && convT_as_conv(cd, N, C, D, H, W, K) && ws && ws_bytes >= gemm_ws_bytes(cd)) {
     // dW_T[ci][co][t] = sum_pos x[ci][pos] * dy[co][2 pos + t]  ==  conv_wgrad(input = dy, grad_output = x)
     if (int e = conv_wgrad_gemm(dy, x, dw, cd, ws, ws_bytes, s)) return e;
   } else if (C % 4 == 0 && K % 4 == 0) {

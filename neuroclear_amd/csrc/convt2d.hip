@@ -234,7 +234,7 @@ static int convT2d_check(const char* what, int N, int C, int H, int W, int K) {
 
 // the matrix-core forward: the U-Nets' channel pairs (512, 256), (256, 128), (128, 64) and what shares their form
 static bool convT2d_fwd_mfma_ok(int N, int C, int H, int W, int K) {
-  return !g_force_direct && K % 32 == 0 && C % 16 == 0 && C >= 128 && cdiv(cdiv((long)H * W, 32) * N, 4) < (1L << 31);
+  return !sw::raw(sw::FORCE_DIRECT) && K % 32 == 0 && C % 16 == 0 && C >= 128 && cdiv(cdiv((long)H * W, 32) * N, 4) < (1L << 31);
 }
 
 }  // namespace nc
@@ -272,7 +272,7 @@ int nc_convT2d_k2s2_dgrad(const float* dy, const float* w, float* dx, int N, int
   if (!dy || !w || !dx) { set_error("convT2d_dgrad: null pointer"); return NC_ERR_ARG; }
   if (int e = convT2d_check("convT2d_dgrad", N, C, H, W, K)) return e;
   ConvDims cd;
-  if (!g_force_direct && C >= 64 && convT2d_as_conv(cd, N, C, H, W, K) && gemm_fwd_supported(cd) &&
+  if (!sw::raw(sw::FORCE_DIRECT) && C >= 64 && convT2d_as_conv(cd, N, C, H, W, K) && gemm_fwd_supported(cd) &&
       (gemm_ws_bytes(cd) == 0 || (ws && ws_bytes >= gemm_ws_bytes(cd)))) {
     // dx[ci][pos] = sum_(co, t) w[ci][co][t] * dy[co][2 pos + t]  ==  the FORWARD pass of Conv2d(K -> C, k 2, s 2, p 0) on dy with the
     // transposed-conv weight read as [C][K][2][2]
@@ -294,7 +294,7 @@ int nc_convT2d_k2s2_wgrad(const float* x, const float* dy, float* dw, float* dbi
   if (int e = convT2d_check("convT2d_wgrad", N, C, H, W, K)) return e;
   hipStream_t s = (hipStream_t)stream;
   ConvDims cd;
-  if (!g_force_direct && convT2d_as_conv(cd, N, C, H, W, K) && ws && ws_bytes >= gemm_ws_bytes(cd)) {
+  if (!sw::raw(sw::FORCE_DIRECT) && convT2d_as_conv(cd, N, C, H, W, K) && ws && ws_bytes >= gemm_ws_bytes(cd)) {
     // dW_T[ci][co][t] = sum_pos x[ci][pos] * dy[co][2 pos + t]  ==  conv_wgrad(input = dy, grad_output = x)
     if (int e = conv_wgrad_gemm(dy, x, dw, cd, ws, ws_bytes, s)) return e;
   } else if (C % 4 == 0 && K % 4 == 0) {

@@ -11,7 +11,6 @@
 // The results leave as the S3 form of the output (8-byte halves of a unit: a lane holds channels 4g .. 4g + 3) and / or as fp32.
 // The fp32 matrix-core kernel this replaces (convt.hip k_convT_fwd_mfma) re-read the input once per (32 channels, a) and ran at
 // ~75 TFLOP/s; the 256 -> 128 layer was still on the VALU kernel.
-#include <cstdlib>
 
 #include "common.hpp"
 #include "s3_common.hpp"
@@ -218,7 +217,7 @@ int qn_for(int C) { return (C / 32) * 8 * 3 * 1024 <= 128 * 1024 ? 8 : 4; }
 }  // namespace
 
 bool convT_s3x_supported(int N, int C, int D, int H, int W, int K) {
-  static const bool on = !(getenv("NC_CONVT_S3X") && atoi(getenv("NC_CONVT_S3X")) == 0);  // A/B switch: the fp32 kernels of convt.hip
+  const bool on = sw::raw(sw::CONVT_S3X) != 0;  // A/B switch: the fp32 kernels of convt.hip
   const long S = (long)D * H * W;
   if (!on || C % 32 || K % 16 || C > 256 || N < 1) return false;
   if ((C / 32) * qn_for(C) * 3 * 1024 > 128 * 1024) return false;

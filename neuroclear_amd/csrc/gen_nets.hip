@@ -11,8 +11,6 @@
 // Parameter blob = the tensors in state-dict order, packed back to back.  `saved` receives what the
 // backward needs (raw conv outputs, activations, InstanceNorm statistics); sizes from the *_saved_floats queries.
 
-#include <atomic>
-#include <cstdlib>
 
 #include "common.hpp"
 
@@ -42,7 +40,6 @@ size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 //             the rank-one form) -- no 64-channel data gradient of one_by_one is written or read.
 // Every lean form applies to a block in the two-term form only; with three terms, the split kernels off or NC_S3_TRAIN_FUSE=0 the calls launch
 // what they launched before.
-std::atomic<int> g_unet_lean{getenv("NC_UNET_LEAN") ? (atoi(getenv("NC_UNET_LEAN")) != 0) : 1};
 constexpr int kLeanBit0 = 10;                     // kept bits 10 .. 14
 constexpr int kLeanBlocks[5] = {1, 3, 5, 6, 8};   // the blocks whose fp32 input the lean forward leaves out (a1, a2, b1, b2, e2a)
 int lean_index(int consumer) {
@@ -62,7 +59,6 @@ const UBlock kUB[10] = {{1, 64, 0},    {64, 64, 0},    {64, 128, 1},  {128, 128,
 // for them.  Blocks 7 and 9 take a concatenation: their forward packs fold in the ratio of the two halves' cells, the InstanceNorm bound and the
 // transposed convolution's output bound (convt_s3.hip), which the pass computes from the weights as well; with NC_CONVT_H2=0 that half's cell is
 // measured, and those two forward packs stay with the per-layer launches.
-std::atomic<int> g_unet_wprep{getenv("NC_UNET_WPREP") ? (atoi(getenv("NC_UNET_WPREP")) != 0) : 1};
 constexpr unsigned kKeptWPrep = 1u << 15;
 // THE WINNER BYTES of the two max-pools (nc_set_in_bwd_fold, default on; norm_act.hip PoolGrad): the forward's pool kernel also writes one byte per
 // pooled element, the index of its window's winner, into `saved` (UPlan::parg); `kept` bit 26 records that they exist.  The backward of blocks 1
@@ -182,11 +178,6 @@ size_t u_ws_bytes(const UPlan& p, bool bwd) {
 
 extern "C" {
 
-void nc_set_unet_wprep(int on) { g_unet_wprep.store(on != 0, std::memory_order_relaxed); }
-int nc_get_unet_wprep(void) { return g_unet_wprep.load(std::memory_order_relaxed); }
-void nc_set_unet_lean(int on) { g_unet_lean.store(on != 0, std::memory_order_relaxed); }
-int nc_get_unet_lean(void) { return g_unet_lean.load(std::memory_order_relaxed); }
-
 size_t nc_unet_deconv_param_floats(void) { return u_offsets().total; }
 
 int nc_unet_wprep_layout(int N, int S0, int S1, int S2, int block, int form, size_t* pack_off, size_t* pack_bytes, size_t* cell_off,
@@ -248,8 +239,8 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   // that input -- the normalisation + ReLU pass of the block in front, or the conversion of a transposed convolution's output -- writes
   // the S3 form straight into the consumer's slot of `saved` (xs3[i]) instead of a separate conversion pass over the fp32 tensor
   // (k_act_split3; a block fed by a max-pool still converts inside conv_fwd_keep).  NC_S3_TRAIN_FUSE=0: every block converts for itself.
-  static const bool fuse_on = !(getenv("NC_S3_TRAIN_FUSE") && atoi(getenv("NC_S3_TRAIN_FUSE")) == 0);
-  const bool lean = g_unet_lean.load(std::memory_order_relaxed) != 0;
+  const bool fuse_on = sw::raw(sw::S3_TRAIN_FUSE) != 0;
+  const bool lean = sw::raw(sw::UNET_LEAN) != 0;
   bool use[10], pre[10], h2l[10];  // h2l: the block's operands in the two-term form (nc_set_split_terms(2); conv_split.hip s3_layer_h2)
   ConvDims cd[10];
   for (int i = 0; i < 10; ++i) {
@@ -269,7 +260,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   // Two-term form: the transposed convolution writes the H2 form of its half itself -- its power of two comes from a BOUND (one tap per input
   // channel and output voxel: max column sum of |w| times the InstanceNorm bound of its input, convt_s3.hip), so nothing is measured and the
   // whole forward is independent of what else is in the batch.  NC_CONVT_H2=0: fp32 output, measured and converted.
-  static const bool ct_h2 = !(getenv("NC_CONVT_H2") && atoi(getenv("NC_CONVT_H2")) == 0);
+  const bool ct_h2 = sw::raw(sw::CONVT_H2) != 0;
   const bool ct2h = ct2 && h2l[7] && ct_h2;
   const bool ct1 = nc_convT_k2s2_split_active(1, 128, d1[0], d1[1], d1[2], 64) &&
                    p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 128, d1[0], d1[1], d1[2], 64);
@@ -280,7 +271,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   // the prepared weights (see kKeptWPrep): every two-term block's cells and packs, both forms, before the first convolution
   S3xPrepared prep[18] = {};
   bool bound7 = false, bound9 = false;  // the pass set cell7 / cell9
-  if (g_unet_wprep.load(std::memory_order_relaxed) != 0) {
+  if (sw::raw(sw::UNET_WPREP)) {
     WPrepSeg sg[18];
     wprep_segs(sg);
     WPrepBound wb[2];
@@ -322,7 +313,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     // Two-term form with the input already converted by its producer (a power of two known by construction: nothing can fall back): the
     // convolution's epilogue can leave the partial InstanceNorm sums (conv_s3x.hip ST) instead of a statistics pass over its output --
     // nc_set_epi_stats(2): an option, not the default (no measurable gain in the training step)
-    const bool epi = pre[i] && h2l[i] && epi_stats_mode() == 2 && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) <= p.in_ws;
+    const bool epi = pre[i] && h2l[i] && sw::raw(sw::EPI_STATS) == 2 && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) <= p.in_ws;
     if (pre[i]) {  // the producers left the S3 input in saved
       NC_TRY(conv_fwd_pre(V + p.xs3[i], P + o.w[i], P + o.b[i], V + p.raw[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream,
                           epi ? (float*)iws : nullptr, i >= 1 ? prep_of(2 * (i - 1)) : nullptr));
@@ -354,7 +345,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   };
   NC_TRY(block(0, x, V + p.a1, (size_t)64 * S, 1, 64));
   NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128));
-  const bool pool_arg = in_bwd_fold_on();  // (the pools also leave their winner bytes, see kKeptPoolArg)
+  const bool pool_arg = sw::get(sw::IN_BWD_FOLD) != 0;  // (the pools also leave their winner bytes, see kKeptPoolArg)
   if (pool_arg) kept_mask |= kKeptPoolArg;
   for (int n = 0; n < N; ++n) {
     if (pool_arg)
@@ -452,9 +443,8 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   const long S = p.S[0], Sh = p.S[1], Sq = p.S[2];
   const int *d0 = p.d[0], *d1 = p.d[1], *d2 = p.d[2];
   const unsigned kept_mask = kept;
-  static const bool fuse_bwd = !(getenv("NC_S3_TRAIN_FUSE") && atoi(getenv("NC_S3_TRAIN_FUSE")) == 0) &&
-                               true;
-  const bool wprep_now = g_unet_wprep.load(std::memory_order_relaxed) != 0;
+  const bool fuse_bwd = sw::raw(sw::S3_TRAIN_FUSE) != 0;
+  const bool wprep_now = sw::raw(sw::UNET_WPREP) != 0;
   S3xPrepared prepd[10] = {};  // block i's data-gradient pack in `saved` (wprep_run's layout: cells, then the segments in order)
   {
     WPrepSeg sg[18];
@@ -540,7 +530,7 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   // block 9's InstanceNorm backward forms w12[c] * s2[v] itself; the conditions are block_bwd's own for that path.  (dW12 / db12 stay with the
   // matrix kernel over e1: their summation order is part of what the step computes.)
   ConvDims cd9;
-  const bool r1 = g_unet_lean.load(std::memory_order_relaxed) != 0 && N == 1 && fuse_bwd &&
+  const bool r1 = sw::raw(sw::UNET_LEAN) != 0 && N == 1 && fuse_bwd &&
                   make_dims(cd9, N, 128, d0[0], d0[1], d0[2], 64, 3, 3, 3, 1, 1) && conv_layer_h2(cd9) &&
                   conv_bwd_pre_supported(N, 128, d0[0], d0[1], d0[2], 64, 3, true, p.conv_ws) && instnorm_bwd_s3_supported(N, 64, S);
   NC_TRY(nc_conv_wgrad(V + p.e1, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
@@ -798,14 +788,12 @@ __global__ void __launch_bounds__(256) k_dl_tail_w345(const float* __restrict__ 
 }
 
 // 0: layer by layer; 1: the collapsed tail + the rank forms of the 5^3 layer (round 5); 2 (default): layers 1 .. 5 as one position-typed 7^3 kernel
-// where the shape admits it (dl_typed.hip), else as 1
-std::atomic<int> g_dl_collapse{getenv("NC_DL_COLLAPSE") ? (atoi(getenv("NC_DL_COLLAPSE")) < 0 ? 0 : atoi(getenv("NC_DL_COLLAPSE")) > 2 ? 2 : atoi(getenv("NC_DL_COLLAPSE"))) : 2};
+// where the shape admits it (dl_typed.hip), else as 1: sw::DL_COLLAPSE
 
 }  // namespace
 
 // the same weight-space steps for the 16-bit path (gen_nets_lp.hip)
 namespace nc {
-bool dl_collapse_on() { return g_dl_collapse.load(std::memory_order_relaxed) != 0; }
 size_t dl_tail_bytes() { return LTail::bytes; }
 const float* dl_tail_E(const char* tail) { return (const float*)(tail + LTail::E); }
 const float* dl_tail_Ef(const char* tail) { return (const float*)(tail + LTail::Ef); }
@@ -897,9 +885,6 @@ size_t nc_deep_linear_ws_bytes(int N, int S0, int S1, int S2) {
   return l_plan(p, N, S0, S1, S2) ? align256(p.conv_ws) + p.grads * sizeof(float) + 256 + align256(LTail::bytes) + dl_typed_bytes(N, S0, S1, S2) : 0;
 }
 
-void nc_set_dl_collapse(int on) { g_dl_collapse.store(on < 0 ? 0 : on > 2 ? 2 : on, std::memory_order_relaxed); }
-int nc_get_dl_collapse(void) { return g_dl_collapse.load(std::memory_order_relaxed); }
-
 // saved == NULL: inference -- the intermediate activations ping-pong through the workspace instead
 int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* saved, int N, int S0, int S1, int S2, void* ws,
                        size_t ws_bytes, void* stream, unsigned* kept) {
@@ -913,15 +898,15 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
   const float* in = x;
   unsigned kept_mask = 0;
   if (kept) *kept = 0;
-  const bool collapse = g_dl_collapse.load(std::memory_order_relaxed) != 0;
+  const bool collapse = sw::raw(sw::DL_COLLAPSE) != 0;
   char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
   hipStream_t hs = (hipStream_t)stream;
-  static const bool k32_on = !(getenv("NC_DL_K32") && atoi(getenv("NC_DL_K32")) == 0);
+  const bool k32_on = sw::raw(sw::DL_K32) != 0;
   char* typed = tail + align256(LTail::bytes);
   ConvDims d0;
   // layers 1 .. 5 as ONE position-typed 7^3 convolution 64 -> 1 of act0 (dl_typed.hip): the interior kernel on the two-term
   // pseudo-channel kernel of Conv3d(1, 64, 7)'s data gradient, the voxels on a face recomputed with their own kernels
-  const bool typed_ok = g_dl_collapse.load(std::memory_order_relaxed) == 2 && saved && dl_typed_supported(N, S0, S1, S2) && make_dims(d0, N, 1, S0, S1, S2, 64, 7, 7, 7, 1, 3) && c1k7_h2_supported(d0) &&
+  const bool typed_ok = sw::raw(sw::DL_COLLAPSE) == 2 && saved && dl_typed_supported(N, S0, S1, S2) && make_dims(d0, N, 1, S0, S1, S2, 64, 7, 7, 7, 1, 3) && c1k7_h2_supported(d0) &&
                         c1_wgrad_supported(d0) && c1k7_h2_dgrad_ws_bytes(d0) <= p.conv_ws && c1k7_h2_ws_bytes(d0) <= p.conv_ws &&
                         c1_wgrad_ws_bytes(d0) <= p.conv_ws;
   for (int i = 0; i < 6; ++i) {
@@ -989,8 +974,8 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
   // layer 1's backward from the rank structure of its dY (see k_dl_shift27): decided here, because with both halves in that form dL/dact1 is
   // never formed
   ConvDims dsh, cd1;
-  static const bool rank_on = !(getenv("NC_DL_RANK_WGRAD") && atoi(getenv("NC_DL_RANK_WGRAD")) == 0);
-  static const bool rank_dg_on = !(getenv("NC_DL_RANK_DGRAD") && atoi(getenv("NC_DL_RANK_DGRAD")) == 0);
+  const bool rank_on = sw::raw(sw::DL_RANK_WGRAD) != 0;
+  const bool rank_dg_on = sw::raw(sw::DL_RANK_DGRAD) != 0;
   const bool h2_1 = make_dims(cd1, N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2) && conv_layer_h2(cd1);
   const bool have1 = ((kept_mask >> 1) & 1) && ((kept_mask >> 17) & 1) != 0;
   const bool rank_w = (kept_mask & kKeptCollapsed) && rank_on && h2_1 && have1 && make_dims(dsh, N, 32, S0, S1, S2, 64, 5, 5, 5, 1, 2) &&

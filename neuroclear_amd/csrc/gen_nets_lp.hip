@@ -13,7 +13,6 @@
 // deep_linear_gen's pointwise tail 64 -> 32 -> 16 -> 1 has no bias and no activation: it IS a single 64-vector
 // w_eff = W6 W5 W4, and every weight gradient of the three layers is an outer product with q = sum_v dy[v] f3[:, v]
 // (one output channel => rank 1).  The tail is evaluated in that form (k_lin_tail_*): no 32- / 16-channel tensors exist.
-#include <cstdlib>
 
 #include "common.hpp"
 
@@ -151,10 +150,7 @@ UWs ulp_ws(const ULp& p, void* ws) {
 
 namespace {
 // NC_C1_WGRAD=0: the one-channel layers' weight gradient back on the fp32 tap-axis kernel (A/B runs)
-bool c1_wgrad_on() {
-  static const bool on = !(getenv("NC_C1_WGRAD") && atoi(getenv("NC_C1_WGRAD")) == 0);
-  return on;
-}
+bool c1_wgrad_on() { return sw::raw(sw::C1_WGRAD) != 0; }
 struct WeightDiffusion {
   WeightDiffusion() { nc::h_set_weight_diffusion(1); }
   ~WeightDiffusion() { nc::h_set_weight_diffusion(0); }
@@ -436,7 +432,7 @@ bool llp_plan(LLp& p, int N, int S0, int S1, int S2) {
 // the rank-structured backward of the 5^3 layer (gen_nets.hip) is available at this shape: 32-channel shapes of the weight-gradient and
 // forward kernels fit the plan's workspace
 bool llp_rank_ok(const LLp& p, ConvDims& dsh) {
-  static const bool rank_on = !(getenv("NC_DL_RANK_WGRAD") && atoi(getenv("NC_DL_RANK_WGRAD")) == 0);
+  const bool rank_on = sw::raw(sw::DL_RANK_WGRAD) != 0;
   return rank_on && p.c1 && p.c3 && make_dims(dsh, p.N, 32, p.d[0], p.d[1], p.d[2], 64, 5, 5, 5, 1, 2) && c8x_wgrad_supported(dsh) &&
          c8x_wgrad_part_bytes(dsh) <= p.conv_ws && h_fwd_supported(dsh) && h_ws_bytes(dsh) <= p.conv_ws;
 }
@@ -493,8 +489,8 @@ int nc_deep_linear_lp_fwd(const float* params, const float* x, float* y, void* s
   make_dims(c5, N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2);
   make_dims(c3, N, 64, S0, S1, S2, 64, 3, 3, 3, 1, 1);
   ConvDims dshf;
-  static const bool k32_on = !(getenv("NC_DL_K32") && atoi(getenv("NC_DL_K32")) == 0);
-  if (k32_on && dl_collapse_on() && c1_wgrad_on() && llp_rank_ok(p, dshf)) {
+  const bool k32_on = sw::raw(sw::DL_K32) != 0;
+  if (k32_on && sw::raw(sw::DL_COLLAPSE) && c1_wgrad_on() && llp_rank_ok(p, dshf)) {
     // layers 1 .. 5 without f2 (gen_nets.hip, "the forward without act1"): Z = F (*) f1 on the first 32 channels of a 64-channel tile (half the
     // matrix work of the 5^3 layer), y = its 27-term shifted sum.  The backward in its rank form does not miss f2 (q comes from P).
     char* tail = G + p.tail;
@@ -506,7 +502,7 @@ int nc_deep_linear_lp_fwd(const float* params, const float* x, float* y, void* s
     return dl_combine27(Ff, y, N, S0, S1, S2, 64, hs);
   }
   NC_TRY(conv_fwd_h_c8(V + p.f1h, params + p.w[1], nullptr, V + p.f2h, 64, 0, c5, dtype, cws, p.conv_ws, hs));
-  if (p.c3 && dl_collapse_on() && c1_wgrad_on()) {
+  if (p.c3 && sw::raw(sw::DL_COLLAPSE) && c1_wgrad_on()) {
     // layers 2 .. 5 as ONE 64 -> 1 convolution of f2 (gen_nets.hip, "the collapsed tail"): the data-gradient form of the one-channel 3^3 kernel
     // with the tap-flipped composed weights IS that convolution.
     char* tail = G + p.tail;

@@ -3,8 +3,6 @@
 // units like S3 with two sub-blocks.  The power of two comes from a CELL, one unsigned per tensor holding the float bits of a magnitude that
 // bounds the tensor from above within a factor of two: the largest finite |x| (k_absmax; atomicMax, order-independent, deterministic), or a
 // bound known by construction (h2_set_cell: |InstanceNorm output| <= sqrt(S - 1)).
-#include <atomic>
-#include <cstdlib>
 #include <mutex>
 
 #include "common.hpp"
@@ -309,20 +307,15 @@ int split2h_into(const float* x, long xstride, void* xs, int N, int C, long S, i
   if (C % 8 || ctot % 8 || c0 % 8) { set_error("split2h: channels must be multiples of 8"); return NC_ERR_SHAPE; }
   long bx = cdiv(S, 256);
   const long ny = (long)N * C / 8;
-  if (guard && h2_guard_on() && bx * ny > 4096) bx = cdiv(4096, ny) < bx ? cdiv(4096, ny) : bx;  // (see the kernel: few atomics)
+  if (guard && sw::get(sw::H2_GUARD) && bx * ny > 4096) bx = cdiv(4096, ny) < bx ? cdiv(4096, ny) : bx;  // (see the kernel: few atomics)
   hipLaunchKernelGGL(k_split2h, dim3((unsigned)bx, (unsigned)ny), dim3(256), 0, s, x, (uint4*)xs, S, C / 8, ctot / 8, c0 / 8, xstride,
-                     cell, h2_guard_on() ? guard : nullptr);
+                     cell, sw::get(sw::H2_GUARD) ? guard : nullptr);
   return check_launch("split2h");
 }
 
 // ---- the range guard (common.hpp) -----------------------------------------------------------------------------------------------------------
-static std::atomic<int> g_guard{getenv("NC_H2_GUARD") ? atoi(getenv("NC_H2_GUARD")) : 1};
-int h2_guard_mode() { const int f = frozen_guard(); return f >= 0 ? f : g_guard.load(); }  // (inside a call: the value sampled when the call began)
-bool h2_guard_on() { return h2_guard_mode() != 0; }
-namespace { unsigned long long* guard_stats_dev(); }
-// (the pinned counter block is allocated HERE, off the launch path -- a first allocation inside h2_guard_decide could land in a stream capture
-// and invalidate it -- and portable, so that every device of the process sees it)
-void h2_guard_set(int on) { g_guard = on == 2 ? 2 : on ? 1 : 0; if (on) (void)guard_stats_dev(); }
+// sw::H2_GUARD: 0 off; 1 (default): in-call fallback in the per-layer entry points, whole-network calls count only; 2: in-call fallback everywhere
+// (the pinned counter block is allocated by nc_set_h2_guard, off the launch path, and portable, so that every device of the process sees it)
 namespace {
 std::mutex g_stats_mu;
 unsigned long long* g_stats_host = nullptr;  // 4 counters in pinned host memory the device adds to (system-scope atomics): readable without a sync
@@ -356,7 +349,7 @@ int h2_guard_zero(unsigned* g, hipStream_t s, int nwords) {
   return check_launch("h2_guard_zero");
 }
 int h2_guard_decide(unsigned* ga, unsigned* gb, unsigned* prior, unsigned* flag, bool can_flip, hipStream_t s, unsigned long long total_a) {
-  if (!h2_guard_on() && !prior) return NC_OK;  // (the words were zeroed: the flag reads 0)
+  if (!sw::get(sw::H2_GUARD) && !prior) return NC_OK;  // (the words were zeroed: the flag reads 0)
   hipLaunchKernelGGL(k_h2_guard_decide, dim3(1), dim3(64), 0, s, ga, gb, prior, flag, can_flip ? 1 : 0, guard_stats_dev(), total_a);
   return check_launch("h2_guard_decide");
 }

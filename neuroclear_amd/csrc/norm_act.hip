@@ -3,7 +3,6 @@
 // All of these are pure streams: 16-byte loads where the instance length allows it, fp64 accumulation for every
 // statistic (1.26 M elements per instance at 108^3 -- fp32 sums would not hold the stated tolerance).
 #include <atomic>
-#include <cstdlib>
 
 #include "common.hpp"
 #include "s3_common.hpp"
@@ -919,12 +918,12 @@ __global__ void k_maxpool2_bwd(const float* __restrict__ dy, const float* __rest
 // the plain sums / apply pass with the prefetch of nc_set_stream_passes (off: one iteration at a time, the kernels as they were)
 static void launch_in_bwd_sums(const float* dy, const float* x, const float* mean, const float* rstd, float slope, long S, int splits, int NC,
                                double* part, hipStream_t s) {
-  if (stream_passes_on()) hipLaunchKernelGGL(k_in_bwd_sums<8>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part);
+  if (sw::get(sw::STREAM_PASSES)) hipLaunchKernelGGL(k_in_bwd_sums<8>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part);
   else hipLaunchKernelGGL(k_in_bwd_sums<1>, dim3(splits, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part);
 }
 static void launch_in_bwd_apply(const float* dy, const float* x, const float* mean, const float* rstd, float slope, long S, int splits, int NC,
                                 long bx, const double* part, float* dx, double* rowpart, hipStream_t s) {
-  if (stream_passes_on())
+  if (sw::get(sw::STREAM_PASSES))
     hipLaunchKernelGGL(k_in_bwd_apply<4>, dim3((unsigned)bx, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part, dx, rowpart);
   else
     hipLaunchKernelGGL(k_in_bwd_apply<1>, dim3((unsigned)bx, NC), dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, part, dx, rowpart);
@@ -1267,12 +1266,12 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
   // of channels or a region far below the rest loses bits the same way.  guard (nullable): the words conv_bwd_s3 reads (conv_bwd_guard_words);
   // the apply pass counts its low chunks, the decision is taken on the device, and a flagged tensor is written AGAIN by the S3 twin of the
   // apply pass (same values, three exact bf16 terms, over the H2 form: the buffer has the S3 capacity) for the three-term kernels
-  unsigned* g = guard && h2_guard_on() ? guard : nullptr;
+  unsigned* g = guard && sw::get(sw::H2_GUARD) ? guard : nullptr;
   // Inside a whole-network call mode 1 (default) COUNTS a flagged tensor (nc_h2_guard_stats [2]) and leaves the switch to the caller (the
   // Python models go to the three-term form when they see it, models/base_model.py): the in-call fallback costs the training step ~65
   // near-empty launches, 0.5 ms of 35, for an event InstanceNorm networks do not produce.  Mode 2: in-call fallback here too.
   const bool flip = g && h2_guard_can_flip();
-  const bool fold = in_bwd_fold_on() && !flip;
+  const bool fold = sw::get(sw::IN_BWD_FOLD) && !flip;
   if (pool && (!fold || w1)) { set_error("instnorm_act_bwd_dbias_h2: the pooled form needs the folded path"); return NC_ERR_ARG; }
   const PoolGrad none{};
   hipLaunchKernelGGL(k_zero_u32, dim3((unsigned)cdiv(64 + 2 * NC, 256)), dim3(256), 0, s, cells, 64 + 2 * NC, fold ? guard : (unsigned*)nullptr, 8);
@@ -1282,7 +1281,7 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
   // (103.6 -> 100.6 us at 64 x 108^3).  The POOL and the plain form gained nothing from 8 (both grids together 117.7 -> 119.5 and 33.2 -> 34.3 us,
   // DESIGN.md 4.1): the switch does not change them.
   constexpr int U = 4, U_R1 = 8;
-  const bool sp = stream_passes_on();
+  const bool sp = sw::get(sw::STREAM_PASSES) != 0;
 #define NC_SUMS(R1_, POOL_, U_, pq_) \
   hipLaunchKernelGGL((k_in_bwd_sums_h2<R1_, POOL_, U_>), gs, dim3(256), 0, s, dy, x, mean, rstd, slope, S, splits, (double*)ws, gmax, xmax, w1, pq_)
   if (pool) NC_SUMS(false, true, U, *pool);
@@ -1338,8 +1337,8 @@ static int in_bwd_dbias_h2(const float* dy, const float* w1, const float* x, con
 // and the forward's winner bytes [N][C][D/2 * H/2 * W/2].  false: take nc_maxpool2_bwd_add and the plain form.
 bool instnorm_bwd_h2_pool_supported(int N, int C, int D, int H, int W, unsigned* guard) {
   const long S = (long)D * H * W;
-  return D >= 2 && H >= 2 && W >= 2 && !((D | H | W) & 1) && S < 0x7fffffffL && instnorm_bwd_s3_supported(N, C, S) && in_bwd_fold_on() &&
-         !(guard && h2_guard_on() && h2_guard_can_flip());
+  return D >= 2 && H >= 2 && W >= 2 && !((D | H | W) & 1) && S < 0x7fffffffL && instnorm_bwd_s3_supported(N, C, S) && sw::get(sw::IN_BWD_FOLD) &&
+         !(guard && sw::get(sw::H2_GUARD) && h2_guard_can_flip());
 }
 int instnorm_act_bwd_dbias_h2_pool(const float* skip, long skip_stride, const float* gp, const unsigned char* arg, const float* x, const float* mean,
                                    const float* rstd, float slope, void* dxs, float* dbias, int N, int C, int D, int H, int W, void* ws,
@@ -1360,14 +1359,6 @@ int maxpool2_fwd_arg(const float* x, float* y, unsigned char* arg, int NC, int D
   hipLaunchKernelGGL(k_maxpool2_fwd<true>, dim3(flat_grid(total)), dim3(256), 0, s, x, y, arg, NC, D, H, W, D / 2, H / 2, W / 2, 2);
   return check_launch("maxpool2_fwd_arg");
 }
-// nc_set_in_bwd_fold: process-wide; inside a call the value sampled when the call began (SwitchScope)
-static std::atomic<int> g_in_bwd_fold{getenv("NC_IN_BWD_FOLD") ? (atoi(getenv("NC_IN_BWD_FOLD")) != 0) : 1};
-int in_bwd_fold_raw() { return g_in_bwd_fold.load(std::memory_order_relaxed); }
-bool in_bwd_fold_on() { const int f = frozen_fold(); return (f >= 0 ? f : in_bwd_fold_raw()) != 0; }
-// nc_set_stream_passes: the same
-static std::atomic<int> g_stream_passes{1};
-int stream_passes_raw() { return g_stream_passes.load(std::memory_order_relaxed); }
-bool stream_passes_on() { const int f = frozen_stream(); return (f >= 0 ? f : stream_passes_raw()) != 0; }
 static std::atomic<int> g_in_bwd_launches[2];  // [0] the two-term norm backward, [1] nc_maxpool2_bwd_add
 void count_in_bwd_launches(int n, int which) { g_in_bwd_launches[which].fetch_add(n, std::memory_order_relaxed); }
 int instnorm_act_bwd_dbias_h2(const float* dy, const float* x, const float* mean, const float* rstd, float slope, void* dxs,
@@ -1393,10 +1384,6 @@ int nc_instnorm_act_bwd_dbias_s3(const float* dy, const float* x, const float* m
   return instnorm_act_bwd_dbias_s3(dy, x, mean, rstd, slope, dxs, dbias, N, C, S, ws, ws_bytes, stream);
 }
 
-int nc_set_in_bwd_fold(int on) { return g_in_bwd_fold.exchange(on != 0, std::memory_order_relaxed); }
-int nc_get_in_bwd_fold(void) { return in_bwd_fold_raw(); }
-int nc_set_stream_passes(int on) { return g_stream_passes.exchange(on != 0, std::memory_order_relaxed); }
-int nc_get_stream_passes(void) { return stream_passes_raw(); }
 int nc_in_bwd_launches(int which, int reset) {
   std::atomic<int>& c = g_in_bwd_launches[which == 1 ? 1 : 0];
   return reset ? c.exchange(0, std::memory_order_relaxed) : c.load(std::memory_order_relaxed);

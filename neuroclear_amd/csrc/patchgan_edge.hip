@@ -321,7 +321,7 @@ int conv_dgrad_pg1(const float* g, const float* act, float slope, const float* w
   Pg1 p = make(d);
   p.g = g; p.act = act; p.slope = slope; p.w = w; p.dx = dx;
   const long nthr = (long)d.N * ((d.H + 1) / 2) * ((d.W + 1) / 2);
-  static const int few = getenv("NC_PG1_FEW") ? atoi(getenv("NC_PG1_FEW")) : 1;  // A/B: 0 = the one-thread-per-pixel-block kernel at every size
+  const int few = sw::raw(sw::PG1_FEW);  // A/B: 0 = the one-thread-per-pixel-block kernel at every size
   if (few && nthr < 128 * 256) hipLaunchKernelGGL(k_pg1_dgrad_few, dim3((unsigned)cdiv(nthr, 32)), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(k_pg1_dgrad, dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, s, p);
   return check_launch("conv_dgrad_pg1");

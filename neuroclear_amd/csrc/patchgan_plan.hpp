@@ -1,7 +1,6 @@
 // Layer plan of the whole-network PatchGAN entry points (nets.hip: nc_patchgan_*; patchgan_gp.hip: nc_patchgan_gp_*):
 // per-conv shapes, offsets of every parameter tensor in the packed blob and of every stored tensor in `saved`.
 #pragma once
-#include <cstdlib>
 
 #include "common.hpp"
 
@@ -42,7 +41,7 @@ inline bool pg_plan(PgPlan& P, int B, int D, int H, int W, int n_layers, int ndf
     const bool head = i == P.nl - 1;
     if (i == 0) {
       mult = 1;
-      static const bool pg1 = !(getenv("NC_PG1") && atoi(getenv("NC_PG1")) == 0);
+      const bool pg1 = sw::raw(sw::PG1) != 0;
       ConvDims c0;
       P.fused0 = pg1 && nd == 2 && make_dims(c0, B, 1, 1, h, w, ndf, 1, 4, 4, 2, 1) && pg1_supported(c0);
     }

@@ -99,7 +99,7 @@ int wprep_run(const WPrepSeg* segs, int n, const WPrepBound* bounds, int nb, voi
   char* packs = (char*)region + kWPrepCellBytes;
   WPrepDevTable t{};
   WPrepDevBounds tb{};
-  const bool frag = stream_passes_on();  // (k_wprep_absmax_rows + k_wprep_pack_frag; off: the kernels as they were)
+  const bool frag = sw::get(sw::STREAM_PASSES) != 0;  // (k_wprep_absmax_rows + k_wprep_pack_frag; off: the kernels as they were)
   if (frag && ((uintptr_t)packs & 15) != 0) { set_error("wprep_run: the region must be 16-byte aligned"); return NC_ERR_ARG; }  // (the convolutions read the packs as uint4)
   t.nseg = n;
   size_t off = 0;

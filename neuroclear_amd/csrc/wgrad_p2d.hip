@@ -16,7 +16,6 @@
 // wave owns 4 units (tap, 16 channels) x all 64 k, six products per fp32 product, partial sums restarted every F steps and summed in a
 // fixed order by k_wgrad_p2d_reduce (deterministic).  The stride-2 layers stay on k_swgrad: their input rows are four times the output
 // row and a ring of them does not fit next to a 64 x 32 tile.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.hpp"
@@ -379,8 +378,7 @@ QPlan q_plan(const ConvDims& d) {
 }
 
 bool q_shape(const ConvDims& d) {
-  static const int on = getenv("NC_P2D") ? atoi(getenv("NC_P2D")) : 7;  // bit 2 = this kernel (bits 0, 1: conv_p2d.hip)
-  if (!(on & 4)) return false;
+  if (!(sw::raw(sw::P2D) & 4)) return false;  // bit 2 = this kernel (bits 0, 1: conv_p2d.hip)
   if (d.D != 1 || d.kd != 1 || d.kh != 4 || d.kw != 4 || d.sh != 1 || d.sw != 1 || d.ph != 1 || d.pw != 1) return false;
   if (d.C % 32 || d.K % 64 || (d.K / 64) * (d.C / 32) > 256) return false;
   static const long minpos = 8192;
