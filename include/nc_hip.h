@@ -88,6 +88,33 @@ int nc_conv2d_k3_active(int what, int N, int C, int H, int W, int K);
 int nc_conv2d_k3_set_cfg(int cfg);            /* returns the previous pin */
 int nc_conv2d_k3_num_cfgs(void);
 
+/* ---- The ResNet generators (networks.py:724-837, --netG resnet_6blocks | resnet_9blocks; 2-D only).
+ *      ReflectionPad2d(1) + Conv2d(C, K, 3) of a ResnetBlock (networks.py:808-830) as ONE layer: x[N,C,H,W], w[K,C,3,3], bias[K] or NULL, y[N,K,H,W],
+ *      H, W >= 2.  Where nc_conv2d_k3_active covers the zero-padded layer of the same dimensions (same rule, same switches nc_set_conv2d_k3 /
+ *      nc_conv2d_k3_set_cfg), forward and data gradient run on the image-tiled kernel of csrc/conv2d_k3.hip: the forward with mirrored halo slots, the
+ *      data gradient as the zero-padded data gradient on the (H + 2) x (W + 2) domain followed by the fold of nc_reflect_pad2d_bwd.  Elsewhere the same
+ *      entry points pad explicitly into the workspace and call nc_conv_* with padding 0; the weight gradient always does.  Run-to-run identical bits. */
+size_t nc_conv2d_k3_reflect_ws_bytes(int N, int C, int H, int W, int K);
+int nc_conv2d_k3_reflect_active(int what, int N, int C, int H, int W, int K); /* what: 0 forward, 1 data gradient */
+int nc_conv2d_k3_reflect_fwd(const float* x, const float* w, const float* bias, float* y, int N, int C, int H, int W, int K,  /* networks.py:809,817 / 823,830 */
+                             void* ws, size_t ws_bytes, void* stream);
+int nc_conv2d_k3_reflect_dgrad(const float* dy, const float* w, float* dx, int N, int C, int H, int W, int K,  /* backward of networks.py:809,817 / 823,830 */
+                               void* ws, size_t ws_bytes, void* stream);
+int nc_conv2d_k3_reflect_wgrad(const float* x, const float* dy, float* dw, float* dbias /* or NULL */, int N, int C, int H, int W, int K,  /* backward of networks.py:817,830 */
+                               void* ws, size_t ws_bytes, void* stream);
+/* nn.ReflectionPad2d(p), p in {1, 3}, H and W > p (networks.py:747,772 p 3; :809,823 p 1): x[NC,H,W] -> y[NC,H+2p,W+2p], a pure copy; the backward
+ * gathers the up-to-nine padded positions of a pixel in a fixed order (csrc/resnet2d.hip), no atomics. */
+int nc_reflect_pad2d_fwd(const float* x, float* y, int NC, int H, int W, int p, void* stream);   /* networks.py:747,772 */
+int nc_reflect_pad2d_bwd(const float* dy, float* dx, int NC, int H, int W, int p, void* stream); /* backward of networks.py:747,772 */
+/* The tail of a ResnetBlock with instance norm, `x + conv_block(x)` (networks.py:830,836): y = skip + (x - mean) * rstd in one pass; mean / rstd from
+ * nc_instnorm_stats.  Backward: the skip gradient is dy itself, the other branch nc_instnorm_act_bwd with slope 1. */
+int nc_instnorm_res_fwd(const float* x, const float* mean, const float* rstd, const float* skip, float* y, int NC, long S, void* stream);
+/* y = a + b: the same skip connection behind a BatchNorm (networks.py:836 with --norm batch). */
+int nc_residual_add(const float* a, const float* b, float* y, long n, void* stream);
+/* nn.Dropout(0.5) of a ResnetBlock in training mode (networks.py:818-819): y = mask ? scale * x : 0 with one mask byte (0 / 1) per element; the
+ * backward is the same call on dy. */
+int nc_dropout_mul(const float* x, const void* mask, float scale, float* y, long n, void* stream);
+
 /* ---- The same convolution on the 16-bit matrix cores (BASELINE.json configs[3]: "fp16 MFMA path with fp32
  *      InstanceNorm accumulate").  Tensors and master weights stay fp32 at this boundary; inside, operands are rounded
  *      (round-to-nearest-even) to `dtype` (NC_DT_BF16: v_mfma_f32_32x32x16_bf16, NC_DT_F16: ..._f16), products are

@@ -416,6 +416,69 @@ int nc_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias, int 
   return NC_OK;
 }
 
+// ---- ReflectionPad2d(1) + Conv2d(C, K, 3) of a ResnetBlock (reference models/networks.py:808-830) as one layer.  Workspace:
+// [the padded input / the extended data gradient, N C (H + 2)(W + 2) floats][the convolution's own workspace].
+static size_t k3r_pad_bytes(int N, int C, int H, int W) { return ((size_t)N * C * (H + 2) * (W + 2) * sizeof(float) + 255) & ~(size_t)255; }
+static int k3r_args(const char* what, ConvDims& d, const void* a, const void* b, const void* c, int N, int C, int H, int W, int K, void* ws,
+                    size_t ws_bytes) {
+  if (int e = conv_args(what, d, a, b, c, N, C, 1, H, W, K, 1, 3, 3, 1, 1)) return e;
+  if (!conv2d_k3_reflect_ok(d)) { set_error("%s: bad shape N=%d C=%d H=%d W=%d K=%d (a mirror needs H, W >= 2)", what, N, C, H, W, K); return NC_ERR_SHAPE; }
+  if (!ws || ws_bytes < nc_conv2d_k3_reflect_ws_bytes(N, C, H, W, K)) { set_error("%s: workspace too small", what); return NC_ERR_WS; }
+  return NC_OK;
+}
+
+size_t nc_conv2d_k3_reflect_ws_bytes(int N, int C, int H, int W, int K) {
+  ConvDims d;
+  if (!make_dims(d, N, C, 1, H, W, K, 1, 3, 3, 1, 1) || !conv2d_k3_reflect_ok(d)) return 0;
+  size_t b = nc_conv_ws_bytes(N, C, 1, H + 2, W + 2, K, 1, 3, 3, 1, 0);  // the fallback: the explicitly padded image, padding 0
+  if (conv2d_k3_ws_bytes(d) > b) b = conv2d_k3_ws_bytes(d);               // the tiled kernel's packed weights
+  return k3r_pad_bytes(N, C, H, W) + b;
+}
+
+// the zero-padded layer's coverage rule and switches (nc_conv2d_k3_active), and a second pixel to mirror
+int nc_conv2d_k3_reflect_active(int what, int N, int C, int H, int W, int K) {
+  return (H >= 2 && W >= 2 && (what == 0 || what == 1)) ? nc_conv2d_k3_active(what, N, C, H, W, K) : 0;
+}
+
+int nc_conv2d_k3_reflect_fwd(const float* x, const float* w, const float* bias, float* y, int N, int C, int H, int W, int K, void* ws,
+                             size_t ws_bytes, void* stream) {
+  ConvDims d;
+  if (int e = k3r_args("conv2d_k3_reflect_fwd", d, x, w, y, N, C, H, W, K, ws, ws_bytes)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t pb = k3r_pad_bytes(N, C, H, W);
+  if (nc_conv2d_k3_reflect_active(0, N, C, H, W, K)) {
+    ProfScope ps(0, 12, d, 0, s);
+    return conv_fwd_k3_reflect(x, w, bias, y, d, (char*)ws + pb, ws_bytes - pb, s);
+  }
+  if (int e = reflect_pad_fwd(x, (float*)ws, (long)N * C, H, W, 1, s)) return e;
+  return nc_conv_fwd((const float*)ws, w, bias, y, N, C, 1, H + 2, W + 2, K, 1, 3, 3, 1, 0, (char*)ws + pb, ws_bytes - pb, stream);
+}
+
+int nc_conv2d_k3_reflect_dgrad(const float* dy, const float* w, float* dx, int N, int C, int H, int W, int K, void* ws, size_t ws_bytes,
+                               void* stream) {
+  ConvDims d;
+  if (int e = k3r_args("conv2d_k3_reflect_dgrad", d, dy, w, dx, N, C, H, W, K, ws, ws_bytes)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t pb = k3r_pad_bytes(N, C, H, W);
+  float* dxe = (float*)ws;  // the gradient at the padded input, [N][C][H + 2][W + 2]
+  if (nc_conv2d_k3_reflect_active(1, N, C, H, W, K)) {
+    ProfScope ps(1, 12, d, 0, s);
+    if (int e = conv_dgrad_k3_reflect_ext(dy, w, dxe, d, (char*)ws + pb, ws_bytes - pb, s)) return e;
+  } else {
+    if (int e = nc_conv_dgrad(dy, w, dxe, N, C, 1, H + 2, W + 2, K, 1, 3, 3, 1, 0, (char*)ws + pb, ws_bytes - pb, stream)) return e;
+  }
+  return reflect_pad_bwd(dxe, dx, (long)N * C, H, W, 1, s);
+}
+
+int nc_conv2d_k3_reflect_wgrad(const float* x, const float* dy, float* dw, float* dbias, int N, int C, int H, int W, int K, void* ws,
+                               size_t ws_bytes, void* stream) {
+  ConvDims d;
+  if (int e = k3r_args("conv2d_k3_reflect_wgrad", d, x, dy, dw, N, C, H, W, K, ws, ws_bytes)) return e;
+  const size_t pb = k3r_pad_bytes(N, C, H, W);
+  if (int e = reflect_pad_fwd(x, (float*)ws, (long)N * C, H, W, 1, (hipStream_t)stream)) return e;
+  return nc_conv_wgrad((const float*)ws, dy, dw, dbias, N, C, 1, H + 2, W + 2, K, 1, 3, 3, 1, 0, (char*)ws + pb, ws_bytes - pb, stream);
+}
+
 // Backward of one convolution layer: dx (nullable) and dw (+ dbias) from x, dy, w.  The same results as nc_conv_dgrad followed
 // by nc_conv_wgrad; on the split-operand kernels dY is converted to its three-term form once for both.
 int nc_conv_bwd(const float* x, const float* dy, const float* w, float* dx, float* dw, float* dbias, int N, int C, int D, int H, int W,

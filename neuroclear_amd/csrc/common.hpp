@@ -147,6 +147,14 @@ bool conv2d_k3_dgrad_supported(const ConvDims& d);
 size_t conv2d_k3_ws_bytes(const ConvDims& d);
 int conv_fwd_k3(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 int conv_dgrad_k3(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
+// the same kernel behind ReflectionPad2d(1) (the ResNet generators' blocks): forward with mirrored halo slots; data gradient as the zero-padded
+// one on the (H + 2) x (W + 2) domain (dxe [N][C][H + 2][W + 2]), which reflect_pad_bwd folds.  d: the layer as Conv2d(k 3, s 1, p 1) on H x W.
+bool conv2d_k3_reflect_ok(const ConvDims& d);
+int conv_fwd_k3_reflect(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
+int conv_dgrad_k3_reflect_ext(const float* dy, const float* w, float* dxe, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
+// resnet2d.hip: ReflectionPad2d(p) copy and its gather-form fold
+int reflect_pad_fwd(const float* x, float* y, long NC, int H, int W, int p, hipStream_t s);
+int reflect_pad_bwd(const float* g, float* dx, long NC, int H, int W, int p, hipStream_t s);
 bool sconv_wgrad_supported(const ConvDims& d);
 size_t sconv_wgrad_ws_bytes(const ConvDims& d);
 int conv_wgrad_sconv(const float* x, const float* dy, float* dw, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);

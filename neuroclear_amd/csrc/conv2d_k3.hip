@@ -31,7 +31,9 @@ struct K3Params {
   const float* wp;    // packed weights [M / 64][C / 2][9][2][32][2]
   const float* bias;  // nullable
   float* y;           // output [B][M][H][W]
-  int B, C, M, H, W;
+  int B, C, M, H, W;  // H x W: the input image (the bounds of the source table)
+  int OH, OW, org;    // output image OH x OW; output pixel (oy, ox) sits at input pixel (oy + org, ox + org): H, W, 0 but for the reflect data gradient
+  int reflect;        // halo slots one pixel outside the input image: 0 the zero page (Conv2d padding 1), 1 the mirrored pixel (ReflectionPad2d(1))
   int TH, TW;         // tile: TH rows x TW columns, TH * TW == WM * VB * 32
   int ntx, nty;       // tiles per image
   int CK, CS;         // channels per chunk; floats per staged channel image: (TH + 2) * (TW + 2) rounded up to 64
@@ -57,12 +59,18 @@ __global__ void __launch_bounds__(WM* WN * 64) k_conv2d_k3(const K3Params p) {
   const int cot = blockIdx.y * WN + wn;
   const int Wp = p.TW + 2;
   const int used = (p.TH + 2) * Wp;  // floats of a channel image actually staged (<= CS)
-  const long Sin = (long)p.H * p.W;
+  const long Sin = (long)p.H * p.W, Sout = (long)p.OH * p.OW;
 
-  // ---- per-tile source table: slot s of a staged channel image -> element offset inside a channel image, or -1 (zero)
+  // ---- per-tile source table: slot s of a staged channel image -> element offset inside a channel image, or -1 (zero).  The reflect form
+  // differs only in the slots exactly one pixel outside the image: row -1 reads row 1, row H reads row H - 2, the same for the columns, the
+  // corners through both (H, W >= 2); slots further out (the overhang of the last tiles) keep the zero page.
   for (int s = tid; s < used; s += NT) {
     const int r = s / Wp, c = s - r * Wp;
-    const int iy = ty0 - 1 + r, ix = tx0 - 1 + c;
+    int iy = ty0 + p.org - 1 + r, ix = tx0 + p.org - 1 + c;
+    if (p.reflect) {
+      iy = iy == -1 ? 1 : iy == p.H ? p.H - 2 : iy;
+      ix = ix == -1 ? 1 : ix == p.W ? p.W - 2 : ix;
+    }
     const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
     tab[s] = ok ? iy * p.W + ix : -1;
   }
@@ -76,7 +84,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_conv2d_k3(const K3Params p) {
     const int pr = q / p.TW, pc = q - pr * p.TW;
     const int oy = ty0 + pr, ox = tx0 + pc;
     base[v] = DT > 0 ? pr * Wp + pc : (pr + 2) * Wp + pc + 2;
-    oaddr[v] = (oy < p.H && ox < p.W) ? ((long)b * p.M + cot * 64) * Sin + (long)oy * p.W + ox : -1;
+    oaddr[v] = (oy < p.OH && ox < p.OW) ? ((long)b * p.M + cot * 64) * Sout + (long)oy * p.OW + ox : -1;
   }
   __syncthreads();  // table complete
 
@@ -164,7 +172,7 @@ __global__ void __launch_bounds__(WM* WN * 64) k_conv2d_k3(const K3Params p) {
       if (oaddr[v] >= 0) {
         float* yo = p.y + oaddr[v];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) yo[(long)(a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) * Sin] = acc[a][v][e] + bvs[e];
+        for (int e = 0; e < 16; ++e) yo[(long)(a * 32 + (e & 3) + 8 * (e >> 2) + 4 * h) * Sout] = acc[a][v][e] + bvs[e];
       }
   }
 }
@@ -254,12 +262,13 @@ int k3_launch_cfg(const K3Plan& pl, const K3Params& p, hipStream_t s) {
   return check_launch("conv2d_k3");
 }
 
+// H x W: the input image; OH x OW, org: the output image and its origin inside the input (K3Params); reflect: the halo mode
 template <int DT>
-int k3_run(const float* x, const float* w, const float* bias, float* y, int B, int C, int M, int H, int W, long sm, long sc, void* ws, size_t wsb,
-           hipStream_t s) {
+int k3_run(const float* x, const float* w, const float* bias, float* y, int B, int C, int M, int H, int W, int OH, int OW, int org, int reflect,
+           long sm, long sc, void* ws, size_t wsb, hipStream_t s) {
   const size_t need = ((size_t)C * M * 9 * sizeof(float) + 255) & ~(size_t)255;
   if (!ws || wsb < need) { set_error("conv2d_k3: workspace too small"); return NC_ERR_WS; }
-  const K3Plan pl = k3_plan(B, C, M, H, W);
+  const K3Plan pl = k3_plan(B, C, M, OH, OW);
   if (!pl.ok) { set_error("conv2d_k3: tile configuration %d does not apply", sw::raw(sw::CONV2D_K3_CFG)); return NC_ERR_SHAPE; }
   float* wp = (float*)ws;
   const long total = (long)C * M * 9;
@@ -268,6 +277,7 @@ int k3_run(const float* x, const float* w, const float* bias, float* y, int B, i
   K3Params p{};
   p.x = x; p.wp = wp; p.bias = bias; p.y = y;
   p.B = B; p.C = C; p.M = M; p.H = H; p.W = W;
+  p.OH = OH; p.OW = OW; p.org = org; p.reflect = reflect;
   p.TH = pl.TH; p.TW = pl.TW; p.ntx = pl.ntx; p.nty = pl.nty; p.CK = pl.CK; p.CS = pl.CS;
   switch (pl.cfg) {
     case 0: return k3_launch_cfg<DT, 4, 1, 2>(pl, p, s);
@@ -290,12 +300,29 @@ size_t conv2d_k3_ws_bytes(const ConvDims& d) {
 
 int conv_fwd_k3(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
   if (!conv2d_k3_fwd_supported(d)) { set_error("conv2d_k3_fwd: shape not covered"); return NC_ERR_SHAPE; }
-  return k3_run<1>(x, w, bias, y, d.N, d.C, d.K, d.H, d.W, (long)d.C * 9, 9L, ws, wsb, s);
+  return k3_run<1>(x, w, bias, y, d.N, d.C, d.K, d.H, d.W, d.H, d.W, 0, 0, (long)d.C * 9, 9L, ws, wsb, s);
 }
 
 int conv_dgrad_k3(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
   if (!conv2d_k3_dgrad_supported(d)) { set_error("conv2d_k3_dgrad: shape not covered"); return NC_ERR_SHAPE; }
-  return k3_run<-1>(dy, w, nullptr, dx, d.N, d.K, d.C, d.H, d.W, 9L, (long)d.C * 9, ws, wsb, s);
+  return k3_run<-1>(dy, w, nullptr, dx, d.N, d.K, d.C, d.H, d.W, d.H, d.W, 0, 0, 9L, (long)d.C * 9, ws, wsb, s);
+}
+
+// ---- ReflectionPad2d(1) + Conv2d(k 3, s 1, p 0) of a ResnetBlock (reference models/networks.py:808-830) on the same kernel.  d describes the
+// layer as the zero-padded one (H x W image, padding 1): the coverage is that layer's rule, and H, W >= 2 (a mirror needs a second pixel).
+bool conv2d_k3_reflect_ok(const ConvDims& d) { return d.H >= 2 && d.W >= 2 && (long)d.N * d.C * (d.H + 2) * (d.W + 2) < (1L << 31); }
+
+// forward: only the source table differs (K3Params::reflect)
+int conv_fwd_k3_reflect(const float* x, const float* w, const float* bias, float* y, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
+  if (!conv2d_k3_fwd_supported(d) || !conv2d_k3_reflect_ok(d)) { set_error("conv2d_k3_reflect_fwd: shape not covered"); return NC_ERR_SHAPE; }
+  return k3_run<1>(x, w, bias, y, d.N, d.C, d.K, d.H, d.W, d.H, d.W, 0, 1, (long)d.C * 9, 9L, ws, wsb, s);
+}
+
+// data gradient, first half: the ZERO-padded data gradient on the (H + 2) x (W + 2) domain of the padded input -- dxe[c][i][j], i in -1 .. H,
+// j in -1 .. W, with dy zero outside the image -- written densely as [N][C][H + 2][W + 2].  The caller folds the border back (reflect_pad_bwd).
+int conv_dgrad_k3_reflect_ext(const float* dy, const float* w, float* dxe, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
+  if (!conv2d_k3_dgrad_supported(d) || !conv2d_k3_reflect_ok(d)) { set_error("conv2d_k3_reflect_dgrad: shape not covered"); return NC_ERR_SHAPE; }
+  return k3_run<-1>(dy, w, nullptr, dxe, d.N, d.K, d.C, d.H, d.W, d.H + 2, d.W + 2, -1, 0, 9L, (long)d.C * 9, ws, wsb, s);
 }
 
 }  // namespace nc

@@ -8,9 +8,12 @@ discriminator (:1147-1179), which are built from the same kernels; `get_norm_lay
 generators `linearkernel`, `linearkernel_double`, `linearkernel_LK31` (:840-871, :183-188), and the KernelGAN patch discriminator
 `kernelGAN` (:1113-1145, :243-244).  The two U-Nets built with dimension=2 (the reference's TestModel passes opt.image_dimension,
 test_model.py:41-45) run layer by layer in fp32 under every --precision: Conv2d / MaxPool2d / norm kernels the discriminators already use, and
-ConvTranspose2d(k 2, s 2) on csrc/convt2d.hip; the whole-network and 16-bit shortcuts stay 3-D only.  Every forward/backward runs HIP kernels from libnc_hip.so through neuroclear_amd.ops; there is no
-torch.nn.functional compute and no CPU fallback.  Networks outside the scope table (resnet, VGG, linearkernel_NC,
-fixed_kernel, ...) raise NotImplementedError exactly like an unknown name does in the reference (:196, :246).
+ConvTranspose2d(k 2, s 2) on csrc/convt2d.hip; the whole-network and 16-bit shortcuts stay 3-D only.  The ResNet generators `resnet_6blocks` /
+`resnet_9blocks` (:177-180, ResnetGenerator :724-780, ResnetBlock :783-837) are 2-D only, as the reference's layers are: their reflect-padded
+3 x 3 convolutions run on the image-tiled kernel of csrc/conv2d_k3.hip where it covers the shape, the transposed convolutions as data gradients of
+the stride-2 convolution, the rest on csrc/resnet2d.hip and the kernels above.  Every forward/backward runs HIP kernels from libnc_hip.so
+through neuroclear_amd.ops; there is no torch.nn.functional compute and no CPU fallback.  Networks outside the scope table (SURVEY.md 8a:
+unet_twoouts, VGG, linearkernel_NC, fixed_kernel, ...) raise NotImplementedError exactly like an unknown name does in the reference (:196, :246).
 """
 import functools
 import os
@@ -444,6 +447,149 @@ class Unet_vanilla(nn.Module):
         return ops.sigmoid(self.one_by_one(ex1))
 
 
+class ReflectionPad2d(nn.Module):
+    """nn.ReflectionPad2d(p) in front of the 7 x 7 convolutions (networks.py:747,772), on nc_reflect_pad2d_*."""
+
+    def __init__(self, padding):
+        super().__init__()
+        self.padding = padding
+
+    def forward(self, x):
+        return ops.reflect_pad2d(x, self.padding)
+
+    def extra_repr(self):
+        return '%d' % self.padding
+
+
+class FusedReflectionPad(nn.Module):
+    """Placeholder at the Sequential index where a ResnetBlock has nn.ReflectionPad2d(1) (networks.py:809,823): the convolution behind it
+    mirrors its own halo (ops.conv_reflect3), this module is the identity."""
+
+    def forward(self, x):
+        return x
+
+
+class Dropout(nn.Module):
+    """nn.Dropout(p) (networks.py:818-819): the identity in eval(); in training mode a device-drawn mask and a HIP multiply (ops.dropout)."""
+
+    def __init__(self, p=0.5):
+        super().__init__()
+        self.p = p
+
+    def forward(self, x):
+        return ops.dropout(x, self.p, self.training)
+
+    def extra_repr(self):
+        return 'p=%g' % self.p
+
+
+class Sigmoid(nn.Module):
+    def forward(self, x):
+        return ops.sigmoid(x)
+
+
+class ConvTransposeK3S2(nn.Module):
+    """nn.ConvTranspose2d(C, K, kernel 3, stride 2, padding 1, output_padding 1) (networks.py:766-769): weight (C, K, 3, 3), bias (K,) or none.
+    Runs as the data gradient of the stride-2 convolution with the same weight tensor (ops.conv_transpose_k3s2)."""
+
+    def __init__(self, in_channels, out_channels, bias=True):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(in_channels, out_channels, 3, 3))
+        self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
+        init.kaiming_uniform_(self.weight, a=5 ** 0.5)
+
+    def forward(self, x, link=None):
+        return ops.conv_transpose_k3s2(x, self.weight, self.bias, link)
+
+    def extra_repr(self):
+        return '%s, stride=2, padding=1, output_padding=1' % (tuple(self.weight.shape),)
+
+
+class ResnetBlock(nn.Module):
+    """networks.py:783-837 with padding_type 'reflect' (the only one ResnetGenerator is built with): x + conv_block(x), conv_block =
+    [ReflectionPad2d(1), Conv 3 x 3, norm, ReLU, (Dropout(0.5),) ReflectionPad2d(1), Conv 3 x 3, norm] -- convolutions at Sequential indices
+    1 / 5 (1 / 6 with dropout).  With instance norm the convolutions' biases cannot reach the output: the parameters stay, the add is skipped,
+    and the tail (second norm + skip) is one pass.  The second norm has no activation: slope 1 makes `v > 0 ? v : v * slope` the identity bit
+    for bit, forward and backward."""
+
+    def __init__(self, dim, norm_layer, use_dropout, use_bias):
+        super().__init__()
+        seq = [FusedReflectionPad(), Conv(dim, dim, 3, 1, 0, bias=use_bias, dimension=2), norm_layer(dim, 0.0), FusedActivation()]
+        if use_dropout:
+            seq += [Dropout(0.5)]
+        seq += [FusedReflectionPad(), Conv(dim, dim, 3, 1, 0, bias=use_bias, dimension=2), norm_layer(dim, 1.0)]
+        self.conv_block = nn.Sequential(*seq)
+        self.instance, self.use_dropout = _is_instance_norm(norm_layer), use_dropout
+
+    def forward(self, x):
+        cb = self.conv_block
+        conv1, norm1, conv2, norm2 = cb[1], cb[2], cb[-2], cb[-1]
+        linked = self.instance and torch.is_grad_enabled()
+        link = ops.BiasLink() if linked else None
+        h = ops.conv_reflect3(x, conv1.weight, conv1.bias, self.instance, link)
+        h = norm1(h, link) if self.instance else norm1(h)
+        if self.use_dropout:
+            h = cb[4](h)
+        link = ops.BiasLink() if linked else None
+        h = ops.conv_reflect3(h, conv2.weight, conv2.bias, self.instance, link)
+        if self.instance:
+            return ops.instance_norm_residual(h, x, norm2.eps, link)
+        return ops.residual_add(x, norm2(h))
+
+
+class ResnetGenerator(nn.Module):
+    """networks.py:724-780: ReflectionPad2d(3), Conv 7 x 7, norm, ReLU; two Conv 3 x 3 stride 2 (+ norm, ReLU); n_blocks ResnetBlocks at 4 ngf
+    channels; two ConvTranspose2d(3 x 3, stride 2, padding 1, output_padding 1) (+ norm, ReLU); ReflectionPad2d(3), Conv 7 x 7 with bias,
+    Sigmoid.  State-dict keys, shapes and order are the reference's (modules without parameters keep the reference's Sequential indices);
+    use_bias is true exactly with InstanceNorm (:742-745).  2-D only, fp32 under every conv precision."""
+
+    def __init__(self, input_nc, output_nc, ngf=64, norm_layer=None, use_dropout=False, n_blocks=6):
+        assert n_blocks >= 0
+        super().__init__()
+        if norm_layer is None:   # --norm none: the reference calls norm_layer(ngf) with None (networks.py:749)
+            raise TypeError("'NoneType' object is not callable")
+        use_bias = _is_instance_norm(norm_layer)
+        model = [ReflectionPad2d(3), Conv(input_nc, ngf, 7, 1, 0, bias=use_bias, dimension=2), norm_layer(ngf, 0.0), FusedActivation()]
+        for i in range(2):
+            mult = 2 ** i
+            model += [Conv(ngf * mult, ngf * mult * 2, 3, 2, 1, bias=use_bias, dimension=2), norm_layer(ngf * mult * 2, 0.0), FusedActivation()]
+        for i in range(n_blocks):
+            model += [ResnetBlock(ngf * 4, norm_layer, use_dropout, use_bias)]
+        for i in range(2):
+            mult = 2 ** (2 - i)
+            model += [ConvTransposeK3S2(ngf * mult, ngf * mult // 2, bias=use_bias), norm_layer(ngf * mult // 2, 0.0), FusedActivation()]
+        model += [ReflectionPad2d(3), Conv(ngf, output_nc, 7, 1, 0, dimension=2), Sigmoid()]
+        self.model = nn.Sequential(*model)
+
+    def forward(self, input):
+        if input.dim() != 4:
+            raise ValueError('ResnetGenerator: expected an NCHW input (its layers are 2-D only), got %s' % (tuple(input.shape),))
+        if min(input.shape[2:]) < 4:
+            raise ValueError('ResnetGenerator: H and W must be at least 4 (ReflectionPad2d(3), networks.py:747), got %s' % (tuple(input.shape[2:]),))
+        mods = list(self.model)
+        x, i = input, 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, (Conv, ConvTransposeK3S2)) and i + 1 < len(mods) and isinstance(mods[i + 1], InstanceNormAct) \
+                    and torch.is_grad_enabled():
+                link = ops.BiasLink()   # the norm's backward hands the layer in front of it its bias gradient
+                x = mods[i + 1](self._layer(m, x, link, True), link)
+                i += 2
+            else:
+                x = self._layer(m, x, None, i + 1 < len(mods) and isinstance(mods[i + 1], InstanceNormAct))
+                i += 1
+        return x
+
+    @staticmethod
+    def _layer(m, x, link, dead_bias):
+        """dead_bias: an InstanceNorm(affine=False) follows, the layer's bias cannot reach the output and is not added."""
+        if isinstance(m, Conv):
+            return ops.conv(x, m.weight, m.bias, m.stride, m.padding, link, None, dead_bias)
+        if isinstance(m, ConvTransposeK3S2):
+            return m(x, link)
+        return m(x)
+
+
 class DeepLinearGenerator(nn.Module):
     """networks.py:893-917: bias-free linear chain, each layer zero-pads its own input."""
 
@@ -626,7 +772,14 @@ def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, in
                                   '(super(LinearKernel, self), networks.py:876)')
     elif netG == 'fixed_kernel':
         raise NotImplementedError('Generator [fixed_kernel] needs given_psf, which no model of the reference passes (networks.py:189-190)')
-    elif netG in ('unet_twoouts', 'resnet_9blocks', 'resnet_6blocks', 'VGG'):
+    elif netG in ('resnet_9blocks', 'resnet_6blocks'):
+        if dimension != 2:
+            raise NotImplementedError('Generator [%s] with dimension=%s: the reference builds it from nn.Conv2d, nn.ReflectionPad2d and '
+                                      'nn.ConvTranspose2d whatever the dimension (networks.py:747-774) -- its layers are 2-D only; pass '
+                                      'dimension=2 (--image_dimension 2)' % (netG, dimension))
+        net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=norm_layer, use_dropout=use_dropout,
+                              n_blocks=9 if netG == 'resnet_9blocks' else 6)   # :177-180
+    elif netG in ('unet_twoouts', 'VGG'):
         raise NotImplementedError('Generator [%s] is outside the MI355X hot path (SURVEY.md 8a)' % netG)
     else:
         raise NotImplementedError('Generator model name [%s] is not recognized' % netG)

@@ -283,8 +283,9 @@ def lp_fwd_dtype(x_shape, w_shape, stride, pad):
 
 class _Conv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, stride, pad, link=None, prev=None):
+    def forward(ctx, x, w, b, stride, pad, link=None, prev=None, dead_bias=False):
         x = x.contiguous()
+        bf = None if dead_bias else b   # a dead bias (conv()) stays a parameter with a gradient; only the add is skipped
         ctx.link = link
         if link is not None:
             link.want = b is not None and ctx.needs_input_grad[2]
@@ -299,7 +300,7 @@ class _Conv(torch.autograd.Function):
                 xh, prev.xh = prev.xh, None  # emitted by the norm in front of this layer
             else:
                 xh = to_c8(x, dt)
-            y = conv_fwd_raw(x, w, b, stride, pad, xh=xh)
+            y = conv_fwd_raw(x, w, bf, stride, pad, xh=xh)
             keep = _lp(2, dims, K, k3, stride, pad) == dt
             if link is not None:  # backward operands: ask the norm behind this layer for dy in C8
                 dd = _lp(1, dims, K, k3, stride, pad) if ctx.needs_input_grad[0] else 0
@@ -311,7 +312,7 @@ class _Conv(torch.autograd.Function):
             return y
         ctx.x_is_c8 = False
         ctx.save_for_backward(x, w)
-        return conv_fwd_raw(x, w, b, stride, pad)
+        return conv_fwd_raw(x, w, bf, stride, pad)
 
     @staticmethod
     def backward(ctx, dy):
@@ -344,7 +345,7 @@ class _Conv(torch.autograd.Function):
                                             x_shape=ctx.x_shape)
                 else:
                     dw, db = conv_wgrad_raw(x, dy, w.shape, stride, pad, want_b, dyh=dyh if same else None)
-            return dx, dw, db if db_link is None else db_link, None, None, None, None
+            return dx, dw, db if db_link is None else db_link, None, None, None, None, None
         big = x.numel() >= (1 << 20)  # small layers gain nothing from a second stream
         if want_w and ctx.needs_input_grad[0] and overlap_wgrad and big and prof is None:
             main = torch.cuda.current_stream()
@@ -356,18 +357,19 @@ class _Conv(torch.autograd.Function):
             x.record_stream(side)
             dx = conv_dgrad_raw(dy, w, x.shape, stride, pad)
             main.wait_stream(side)  # dw / db are consumed (accumulated into .grad) on the main stream
-            return dx, dw, db if db_link is None else db_link, None, None, None, None
+            return dx, dw, db if db_link is None else db_link, None, None, None, None, None
         if ctx.needs_input_grad[0]:
             dx = conv_dgrad_raw(dy, w, x.shape, stride, pad)
         if want_w:
             dw, db = conv_wgrad_raw(x, dy, w.shape, stride, pad, want_b)
-        return dx, dw, db if db_link is None else db_link, None, None, None, None
+        return dx, dw, db if db_link is None else db_link, None, None, None, None, None
 
 
-def conv(x, w, b=None, stride=1, padding=0, link=None, prev=None):
+def conv(x, w, b=None, stride=1, padding=0, link=None, prev=None, dead_bias=False):
     """nn.Conv3d / nn.Conv2d (models/networks.py:361-369).  link / prev: BiasLink shared with the InstanceNorm behind /
-    in front of this layer."""
-    return _Conv.apply(x, w, b, int(stride), int(padding), link, prev)
+    in front of this layer.  dead_bias: an InstanceNorm(affine=False) follows, so b cannot reach the output -- the add is skipped, the
+    parameter keeps its (mathematically zero) gradient, taken as for every other bias (ResnetGenerator's 7 x 7 and stride-2 layers)."""
+    return _Conv.apply(x, w, b, int(stride), int(padding), link, prev, bool(dead_bias))
 
 
 def _lk_ok(x, w):
@@ -1547,3 +1549,235 @@ class _SpectralNorm(torch.autograd.Function):
 def spectral_norm_weight(w_orig, u, v, power_iteration):
     """weight = w_orig / sigma with one power iteration on (u, v) (in place) when `power_iteration`."""
     return _SpectralNorm.apply(w_orig, u, v, bool(power_iteration))
+
+
+# ---- the ResNet generators (ResnetGenerator / ResnetBlock, networks.py:724-837; 2-D only) -----------------------------------------------
+def _nchw(x, what):
+    if x.dim() != 4:
+        raise _lib.NcError('%s: expected an NCHW tensor, got %s' % (what, tuple(x.shape)))
+    return tuple(int(s) for s in x.shape)
+
+
+class _ReflectPad2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p):
+        x = x.contiguous()
+        _chk(x)
+        _f32(x)
+        N, C, H, W = _nchw(x, 'reflect_pad2d')
+        y = torch.empty((N, C, H + 2 * p, W + 2 * p), dtype=torch.float32, device=x.device)
+        check(lib().nc_reflect_pad2d_fwd(_ptr(x), _ptr(y), N * C, H, W, p, _stream()), 'nc_reflect_pad2d_fwd')
+        ctx.cfg = (N, C, H, W, p)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, C, H, W, p = ctx.cfg
+        dy = dy.contiguous()
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=dy.device)
+        check(lib().nc_reflect_pad2d_bwd(_ptr(dy), _ptr(dx), N * C, H, W, p, _stream()), 'nc_reflect_pad2d_bwd')
+        return dx, None
+
+
+def reflect_pad2d(x, p):
+    """nn.ReflectionPad2d(p), p 1 or 3 (networks.py:747,772): the explicit pad in front of the 7 x 7 convolutions."""
+    return _ReflectPad2d.apply(x, int(p))
+
+
+class _ConvReflect3(torch.autograd.Function):
+    """ReflectionPad2d(1) + Conv2d(C, K, 3) as one layer on nc_conv2d_k3_reflect_*.  dead_bias: an InstanceNorm(affine=False) follows, the bias
+    cannot reach the output -- the add is skipped; its gradient (the sum of the gradient at this layer's output: mathematically zero) comes from
+    the norm's backward through `link`, as for ops.conv, or from the weight-gradient call's own sum."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, dead_bias, link):
+        x = x.contiguous()
+        _chk(x, w, b)
+        _f32(x, w, b)
+        N, C, H, W = _nchw(x, 'conv_reflect3')
+        K = w.shape[0]
+        if tuple(w.shape) != (K, C, 3, 3):
+            raise _lib.NcError('conv_reflect3: weight %s does not fit %d input channels (K, C, 3, 3)' % (tuple(w.shape), C))
+        ctx.link = link
+        if link is not None:
+            link.want = b is not None and ctx.needs_input_grad[2]
+        y = torch.empty((N, K, H, W), dtype=torch.float32, device=x.device)
+        ws = workspace(lib().nc_conv2d_k3_reflect_ws_bytes(N, C, H, W, K), x.device, 'ws_k3r')
+        check(lib().nc_conv2d_k3_reflect_fwd(_ptr(x), _ptr(w), _ptr(None if dead_bias else b), _ptr(y), N, C, H, W, K, _ptr(ws), ws.numel(),
+                                             _stream()), 'nc_conv2d_k3_reflect_fwd')
+        ctx.save_for_backward(x, w)
+        ctx.has_b = b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        N, C, H, W = x.shape
+        K = w.shape[0]
+        L = lib()
+        dx = dw = db = None
+        want_b = ctx.has_b and ctx.needs_input_grad[2]
+        if want_b and ctx.link is not None and ctx.link.dbias is not None:
+            db, ctx.link.dbias = ctx.link.dbias, None
+            want_b = False
+        ws = workspace(L.nc_conv2d_k3_reflect_ws_bytes(N, C, H, W, K), x.device, 'ws_k3r')
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            check(L.nc_conv2d_k3_reflect_dgrad(_ptr(dy), _ptr(w), _ptr(dx), N, C, H, W, K, _ptr(ws), ws.numel(), _stream()),
+                  'nc_conv2d_k3_reflect_dgrad')
+        if ctx.needs_input_grad[1] or want_b:
+            dw = torch.empty_like(w)
+            if want_b:
+                db = torch.empty(K, dtype=torch.float32, device=x.device)
+            check(L.nc_conv2d_k3_reflect_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db if want_b else None), N, C, H, W, K, _ptr(ws), ws.numel(),
+                                               _stream()), 'nc_conv2d_k3_reflect_wgrad')
+        return dx, dw, db, None, None
+
+
+def conv_reflect3(x, w, b=None, dead_bias=False, link=None):
+    """nn.ReflectionPad2d(1) followed by nn.Conv2d(C, K, 3, padding 0) (ResnetBlock, networks.py:808-830)."""
+    return _ConvReflect3.apply(x, w, b, bool(dead_bias), link)
+
+
+class _ConvT2dK3S2(torch.autograd.Function):
+    """nn.ConvTranspose2d(C, K, 3, stride 2, padding 1, output_padding 1) (networks.py:766-769) as the data gradient of the Conv2d(K -> C, 3 x 3,
+    stride 2, padding 1) whose weight tensor IS the (C, K, 3, 3) parameter -- no flip, no copy: forward nc_conv_dgrad with the 2H x 2W image as
+    its input size, data gradient nc_conv_fwd, weight gradient nc_conv_wgrad with the roles of x and dy exchanged.  Every such layer of the
+    reference sits in front of a norm: its bias exists only with InstanceNorm(affine=False), where it cannot reach the output -- it is never
+    added, and its gradient comes from the norm's backward through `link`."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, link):
+        x = x.contiguous()
+        _chk(x, w, b)
+        _f32(x, w, b)
+        N, C, H, W = _nchw(x, 'conv_transpose_k3s2')
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.shape[0] != C:
+            raise _lib.NcError('conv_transpose_k3s2: weight %s does not fit x %s (C, K, 3, 3)' % (tuple(w.shape), tuple(x.shape)))
+        ctx.link, ctx.has_b = link, b is not None
+        if link is not None:
+            link.want = b is not None and ctx.needs_input_grad[2]
+        ctx.save_for_backward(x, w)
+        return conv_dgrad_raw(x, w, (N, w.shape[1], 2 * H, 2 * W), 2, 1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.link is not None and ctx.link.dbias is not None:
+            db, ctx.link.dbias = ctx.link.dbias, None
+        if ctx.has_b and ctx.needs_input_grad[2] and db is None:
+            raise _lib.NcError('conv_transpose_k3s2: the bias gradient is taken by the InstanceNorm behind the layer (link), and none ran')
+        if ctx.needs_input_grad[0]:
+            dx = conv_fwd_raw(dy, w, None, 2, 1)
+        if ctx.needs_input_grad[1]:
+            dw, _ = conv_wgrad_raw(dy, x, w.shape, 2, 1, False)
+        return dx, dw, db, None
+
+
+def conv_transpose_k3s2(x, w, b=None, link=None):
+    """The upsampling layers of ResnetGenerator (networks.py:766-769): x [N, C, H, W], w [C, K, 3, 3] -> [N, K, 2H, 2W].  b is a dead bias (see
+    _ConvT2dK3S2): accepted, never added."""
+    return _ConvT2dK3S2.apply(x, w, b, link)
+
+
+class _InstNormRes(torch.autograd.Function):
+    """skip + InstanceNorm2d(affine=False)(x): the tail of a ResnetBlock (networks.py:830,836) in one pass (nc_instnorm_res_fwd).  Backward: the
+    skip gradient is dy itself; the other branch is the norm's backward without activation -- nc_instnorm_act_bwd with slope 1, whose
+    `v > 0 ? g : g * slope` is the identity bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, skip, eps, link):
+        x, skip = x.contiguous(), skip.contiguous()
+        _chk(x, skip)
+        _f32(x, skip)
+        if x.shape != skip.shape:
+            raise _lib.NcError('instance_norm_residual: x %s and skip %s differ' % (tuple(x.shape), tuple(skip.shape)))
+        ctx.link = link
+        mean, rstd = instnorm_stats(x, eps)
+        NC = mean.numel()
+        y = torch.empty_like(x)
+        check(lib().nc_instnorm_res_fwd(_ptr(x), _ptr(mean), _ptr(rstd), _ptr(skip), _ptr(y), NC, x.numel() // NC, _stream()),
+              'nc_instnorm_res_fwd')
+        ctx.save_for_backward(x, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd = ctx.saved_tensors
+        dy = dy.contiguous()
+        NC = mean.numel()
+        S = x.numel() // NC
+        dx = None
+        link = ctx.link
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            if link is not None and link.want:
+                N, C = x.shape[0], x.shape[1]
+                db = torch.empty(C, dtype=torch.float32, device=x.device)
+                ws = workspace(lib().nc_instnorm_bwd_dbias_ws_bytes(NC, S), x.device, 'in')
+                check(lib().nc_instnorm_act_bwd_dbias(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), 1.0, _ptr(dx), _ptr(db), N, C, S, _ptr(ws),
+                                                      ws.numel(), _stream()), 'nc_instnorm_act_bwd_dbias')
+                link.dbias = db
+            else:
+                ws = workspace(lib().nc_instnorm_ws_bytes(NC, S), x.device, 'in')
+                check(lib().nc_instnorm_act_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), 1.0, _ptr(dx), NC, S, _ptr(ws), ws.numel(),
+                                                _stream()), 'nc_instnorm_act_bwd')
+        return dx, (dy if ctx.needs_input_grad[1] else None), None, None
+
+
+def instance_norm_residual(x, skip, eps=1e-5, link=None):
+    return _InstNormRes.apply(x, skip, float(eps), link)
+
+
+class _ResidualAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = a.contiguous(), b.contiguous()
+        _chk(a, b)
+        _f32(a, b)
+        if a.shape != b.shape:
+            raise _lib.NcError('residual_add: %s and %s differ' % (tuple(a.shape), tuple(b.shape)))
+        y = torch.empty_like(a)
+        check(lib().nc_residual_add(_ptr(a), _ptr(b), _ptr(y), a.numel(), _stream()), 'nc_residual_add')
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, dy
+
+
+def residual_add(a, b):
+    """x + conv_block(x) behind a BatchNorm (networks.py:836 with --norm batch)."""
+    return _ResidualAdd.apply(a, b)
+
+
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p):
+        x = x.contiguous()
+        _chk(x)
+        _f32(x)
+        # the mask is drawn on the device from torch's generator (torch.manual_seed governs it); matching nn.Dropout's own mask is not a goal
+        mask = torch.empty(x.shape, dtype=torch.uint8, device=x.device).bernoulli_(1.0 - p)
+        ctx.mask, ctx.scale = mask, 1.0 / (1.0 - p)
+        y = torch.empty_like(x)
+        check(lib().nc_dropout_mul(_ptr(x), _ptr(mask), ctx.scale, _ptr(y), x.numel(), _stream()), 'nc_dropout_mul')
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        check(lib().nc_dropout_mul(_ptr(dy), _ptr(ctx.mask), ctx.scale, _ptr(dx), dy.numel(), _stream()), 'nc_dropout_mul')
+        return dx, None
+
+
+def dropout(x, p=0.5, training=True):
+    """nn.Dropout(p) (ResnetBlock, networks.py:818-819): the identity in evaluation mode; in training mode survivors are multiplied by
+    1 / (1 - p) (exactly 2 for p = 0.5) in a HIP kernel and the backward multiplies dy by the same mask."""
+    if not training:
+        return x
+    return _Dropout.apply(x, float(p))

@@ -152,6 +152,39 @@ def unet_vanilla_spec(dimension=3):
     return spec
 
 
+def resnet_spec(n_blocks, ngf=64, input_nc=1, output_nc=1, norm='instance', use_dropout=False):
+    """(key, shape) list of ``ResnetGenerator`` (``models/networks.py:724-780``) in state-dict order.  Sequential indices: 7 x 7 conv at 1,
+    stride-2 convs at 4 / 7, the blocks at 10 .. 9 + n (``conv_block.{1,5}``, ``{1,6}`` with dropout), the transposed convs (weight
+    (Cin, Cout, 3, 3)) and the last 7 x 7 conv behind them.  ``norm='instance'``: every conv carries a bias; ``norm='batch'``: only the last
+    one does (``use_bias``, ``:742-745``) and every norm layer adds its five entries at conv index + 1."""
+    bias = norm == 'instance'
+    spec = []
+
+    def layer(name, shape, has_bias, normed=True):
+        spec.append((name + '.weight', shape))
+        if has_bias:
+            spec.append((name + '.bias', (shape[1] if name in tconvs else shape[0],)))
+        if normed and norm == 'batch':
+            c = shape[1] if name in tconvs else shape[0]
+            pre = '.'.join(name.split('.')[:-1] + [str(int(name.split('.')[-1]) + 1)])
+            spec.extend([(pre + '.weight', (c,)), (pre + '.bias', (c,)), (pre + '.running_mean', (c,)), (pre + '.running_var', (c,)),
+                         (pre + '.num_batches_tracked', ())])
+
+    up0 = 10 + n_blocks
+    tconvs = ('model.%d' % up0, 'model.%d' % (up0 + 3))
+    layer('model.1', (ngf, input_nc, 7, 7), bias)
+    layer('model.4', (ngf * 2, ngf, 3, 3), bias)
+    layer('model.7', (ngf * 4, ngf * 2, 3, 3), bias)
+    second = 6 if use_dropout else 5
+    for b in range(n_blocks):
+        for i in (1, second):
+            layer('model.%d.conv_block.%d' % (10 + b, i), (ngf * 4, ngf * 4, 3, 3), bias)
+    layer(tconvs[0], (ngf * 4, ngf * 2, 3, 3), bias)
+    layer(tconvs[1], (ngf * 2, ngf, 3, 3), bias)
+    layer('model.%d' % (up0 + 7), (output_nc, ngf, 7, 7), True, normed=False)
+    return spec
+
+
 def pixel_spec(dimension=2, input_nc=1, ndf=64):
     """(key, shape) list of ``PixelDiscriminator`` (``models/networks.py:1147-1179``) with instance norm (every 1x1
     conv carries a bias): net.0 (1->ndf), net.2 (ndf->2ndf) + norm + LeakyReLU, net.5 (2ndf->1)."""
