@@ -256,11 +256,13 @@ int nc_mean_fwd(const float* pred, long n, float* out, void* ws, size_t ws_bytes
 }
 int nc_bce_logits_const_bwd(const float* pred, long n, float target, const float* gscale, float* dpred, void* stream) {
   if (!pred || !gscale || !dpred) { set_error("bce_logits_const_bwd: null pointer"); return NC_ERR_ARG; }
+  if (n < 1) { set_error("bce_logits_const_bwd: empty input"); return NC_ERR_SHAPE; }
   hipLaunchKernelGGL(k_logit_bwd, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, pred, n, target, 2, gscale, dpred);
   return check_launch("bce_logits_const_bwd");
 }
 int nc_mean_bwd(long n, const float* gscale, float* dpred, void* stream) {
   if (!gscale || !dpred) { set_error("mean_bwd: null pointer"); return NC_ERR_ARG; }
+  if (n < 1) { set_error("mean_bwd: empty input"); return NC_ERR_SHAPE; }
   hipLaunchKernelGGL(k_logit_bwd, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)nullptr, n, 0.f, 3, gscale, dpred);
   return check_launch("mean_bwd");
 }
@@ -269,11 +271,13 @@ int nc_l1_fwd(const float* a, const float* b, long n, float* out, void* ws, size
 }
 int nc_mse_const_bwd(const float* pred, long n, float target, const float* gscale, float* dpred, void* stream) {
   if (!pred || !gscale || !dpred) { set_error("mse_const_bwd: null pointer"); return NC_ERR_ARG; }
+  if (n < 1) { set_error("mse_const_bwd: empty input"); return NC_ERR_SHAPE; }
   hipLaunchKernelGGL(k_mse_bwd, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, pred, n, target, gscale, dpred);
   return check_launch("mse_const_bwd");
 }
 int nc_l1_bwd(const float* a, const float* b, long n, const float* gscale, float* da, void* stream) {
   if (!a || !b || !gscale || !da) { set_error("l1_bwd: null pointer"); return NC_ERR_ARG; }
+  if (n < 1) { set_error("l1_bwd: empty input"); return NC_ERR_SHAPE; }
   hipLaunchKernelGGL(k_l1_bwd, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, n, gscale, da);
   return check_launch("l1_bwd");
 }

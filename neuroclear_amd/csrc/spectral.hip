@@ -2,7 +2,7 @@
 // conv wrapped in torch.nn.utils.spectral_norm).  W = weight_orig viewed as [K][M] (M = C * taps).  Per forward pass in
 // training mode ONE power iteration (torch's n_power_iterations = 1, eps = 1e-12):
 //     v <- W^T u / max(|W^T u|, eps);   u <- W v / max(|W v|, eps);   sigma = u . (W v);   weight = W / sigma
-// (u, v updated in place, treated as constants by the backward).  The matrices are small (<= 512 x 8192): one workgroup
+// (u, v updated in place, treated as constants by the backward).  The matrices are small (<= 512 x 8192 in the 2-D PatchGAN, 64 x 16384 in the 3-D one; every loop strides, no size is assumed): one workgroup
 // of 1024 threads does the whole thing in one launch -- two passes over W (L2-resident) plus the scaling pass.
 // Backward of weight = W / (u^T W v):   dW = (G - <G, weight> u v^T) / sigma.
 #include "common.hpp"
