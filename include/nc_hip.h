@@ -283,6 +283,25 @@ int nc_assemble_finalize(const float* acc, void* out, int out_is_u16, int P0, in
 int nc_assemble_finalize_slab(const float* acc_slab, void* out, int out_is_u16, int P0, int P1, int P2, int L0, int L1, int L2, int roi,
                               int overlap, int z0, int nz, int za, void* stream);
 
+/* ---- 2-D dice / assemble for the 2-D generators (--image_dimension 2): the arithmetic above on the two in-plane axes of a stack
+ *      [L0,L1,L2] of planes; axis 0 is not diced, padded or reflected.  P1, P2 and the grid n1 x n2 are util/util.py:196-215 and
+ *      data/diceImage_dataset.py:91-93 of (L1, L2); tile t lies in plane t / (n1 n2) at yi = (t % (n1 n2)) / n2, xi = t % n2
+ *      (data/diceImage_dataset.py:100-106, x fastest).  Each call handles the `count` tiles from `first` on in ONE launch; a batch may
+ *      straddle planes.
+ *      cut_tiles (data/diceImage_dataset.py:95-96, :108-120 + base_dataset.py:134-143): tiles [count][E][E], E = roi + 2*border, float32
+ *      in [0,1], zero dicing pad then reflect border.                                                                              */
+int nc_dice2d_cut_tiles(const void* img, int is_u16, int L0, int L1, int L2, int roi, int overlap, int border, long first, int count,
+                        float* tiles, void* stream);
+/*      scatter_add (util/assemble_dice.py:143-145, :167-173): acc[L0][P1][P2] += tile[border:-border]^2 / 8 at each tile's origin.  One
+ *      thread per accumulator pixel adds the tiles of the batch that cover it in ascending tile index (no atomics): the bits do not
+ *      depend on how the tile sequence is cut into batches and equal those of adding the tiles one by one.                          */
+int nc_assemble2d_scatter_add(const float* tiles, float* acc, int L0, int P1, int P2, int roi, int overlap, int border, long first,
+                              int count, void* stream);
+/*      finalize (util/assemble_dice.py:176-183, :202-213): out[L0][L1][L2] = (acc / cnt) * 8 * scale, truncating cast, crop of the
+ *      dicing pad; cnt = cover(y) * cover(x) from the grid.                                                                         */
+int nc_assemble2d_finalize(const float* acc, void* out, int out_is_u16, int L0, int P1, int P2, int L1, int L2, int roi, int overlap,
+                           void* stream);
+
 /* ---- --normalize_intensity (util/assemble_dice.py:188-192): merged = (acc / count) * 8 on the padded volume;
  *      nc_radix_hist = one pass of an exact radix select (order-preserving 32-bit key of a float: pass 0 bins key >> 20,
  *      pass 1 bins (key >> 8) & 0xfff among key >> 20 == prefix, pass 2 bins key & 0xff among key >> 8 == prefix;
