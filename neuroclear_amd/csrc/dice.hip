@@ -5,69 +5,9 @@
 //   acc   += cube / 8   in cube-index order                  (assemble_dice.py:167-173)
 //   out    = uint16( ((acc / cnt) * 8) * 65535 )  truncating (assemble_dice.py:183, :202-207)
 // The volume stays resident in HBM as uint16/uint8; the zero dicing pad and the reflect border are index arithmetic.
-#include "common.hpp"
+#include "dice_geom.hpp"
 
 namespace nc {
-
-__device__ __forceinline__ int reflect_idx(int q, int P) {  // np.pad(mode='reflect') for |overhang| < P
-  if (q < 0) q = -q;
-  if (q >= P) q = 2 * (P - 1) - q;
-  return q;
-}
-
-struct DiceGeom {
-  int L0, L1, L2, P0, P1, P2, n0, n1, n2, roi, overlap, border, step;
-};
-
-__host__ __device__ inline int pad_len(int L, int roi, int overlap) {
-  const int step = roi - overlap;
-  return step * ((L + overlap) / step) + roi;  // L + pad
-}
-
-// ---- "clean rotation" training augmentation on the device (reference data/base_dataset.py:306-460): every z-slice is
-//      rotated about its centre (cv2.warpAffine, bilinear, zero border) and cropped to the inscribed rectangle; the
-//      reference rotates the WHOLE volume on the host for every training crop.  Here only the voxels of the requested
-//      crop are produced: out[z][y][x] = warpAffine-bilinear(vol[z0 + z], inv * (x0 + x, y0 + y, 1)), rounded to the source integer
-//      type and normalised (/65535 or /255 in fp64, then fp32) exactly like the crop-only path.
-// The sampling arithmetic is cv2.warpAffine's (flags = INTER_LINEAR, BORDER_CONSTANT 0) as OpenCV 4.5.0 publishes it
-// (modules/imgproc/src/imgwarp.cpp: WarpAffineInvoker + remapBilinear + initInterTab2D): m = the canvas -> source matrix warpAffine
-// derives from the forward one (host: data/rotation.py).  Coordinates are fixed point: cvRound of the column term and of the row term at
-// 2^-10 each, + 2^4, >> 5 -> 5 fractional bits; uint8 blends with the 15-bit integer weights 32 (32 - fy)(32 - fx) ... and a rounding
-// shift, uint16 with the float weights (1 - fy/32)(1 - fx/32) ... in float32, products and sums left to right, then cvRound + saturation.
-template <typename T>
-__global__ void k_rotate_crop(const T* __restrict__ vol, int H, int W, int z0, int y0, int x0, int cz, int cy, int cx,
-                              double m00, double m01, double m02, double m10, double m11, double m12, double den,
-                              double vmax, float* __restrict__ out) {
-  const long total = (long)cz * cy * cx;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % cx), y = (int)((i / cx) % cy), z = (int)(i / ((long)cx * cy));
-    const double dx = (double)(x0 + x), dy = (double)(y0 + y);
-    const int ad = (int)rint(m00 * dx * 1024.0), bd = (int)rint(m10 * dx * 1024.0);
-    const int X0 = (int)rint((m01 * dy + m02) * 1024.0) + 16, Y0 = (int)rint((m11 * dy + m12) * 1024.0) + 16;
-    const int X = (X0 + ad) >> 5, Y = (Y0 + bd) >> 5;  // arithmetic shifts: floor for negative coordinates, as in OpenCV
-    const int ix = X >> 5, iy = Y >> 5, fx = X & 31, fy = Y & 31;
-    const T* sl = vol + (long)(z0 + z) * H * W;
-    auto tap = [&](int yy, int xx) -> unsigned {
-      return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? (unsigned)sl[(long)yy * W + xx] : 0u;
-    };
-    const unsigned v00 = tap(iy, ix), v01 = tap(iy, ix + 1), v10 = tap(iy + 1, ix), v11 = tap(iy + 1, ix + 1);
-    double v;
-    if (sizeof(T) == 1) {
-      const int w00 = 32 * (32 - fy) * (32 - fx), w01 = 32 * (32 - fy) * fx, w10 = 32 * fy * (32 - fx), w11 = 32 * fy * fx;
-      const int r = (int)(v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-      v = (double)(r < 0 ? 0 : r > 255 ? 255 : r);
-    } else {
-      const float cy0 = 1.f - (float)fy * 0.03125f, cy1 = (float)fy * 0.03125f, cx0 = 1.f - (float)fx * 0.03125f, cx1 = (float)fx * 0.03125f;
-      float r = __fmul_rn((float)v00, __fmul_rn(cy0, cx0));
-      r = __fadd_rn(r, __fmul_rn((float)v01, __fmul_rn(cy0, cx1)));
-      r = __fadd_rn(r, __fmul_rn((float)v10, __fmul_rn(cy1, cx0)));
-      r = __fadd_rn(r, __fmul_rn((float)v11, __fmul_rn(cy1, cx1)));
-      v = (double)rintf(r);
-      v = v < 0.0 ? 0.0 : (v > vmax ? vmax : v);
-    }
-    out[i] = (float)(v / den);
-  }
-}
 
 template <typename T>
 __global__ void k_cut_cube(const T* __restrict__ vol, DiceGeom g, int z0, int y0, int x0, double den,
@@ -97,33 +37,8 @@ __global__ void k_scatter_add(const float* __restrict__ cube, float* __restrict_
   }
 }
 
-__device__ __forceinline__ int cover_count(int p, int n, int step, int roi) {
-  // number of cube indices i in [0, n) with i*step <= p < i*step + roi
-  int hi = p / step;
-  if (hi > n - 1) hi = n - 1;
-  int lo = p - roi + 1;
-  lo = lo <= 0 ? 0 : (lo + step - 1) / step;
-  return hi - lo + 1;
-}
-
-template <typename T>
-__global__ void k_finalize(const float* __restrict__ acc, T* __restrict__ out, DiceGeom g, float scale) {
-  const long total = (long)g.L0 * g.L1 * g.L2;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int x = (int)(i % g.L2), y = (int)((i / g.L2) % g.L1), z = (int)(i / ((long)g.L2 * g.L1));
-    float v = acc[((long)z * g.P1 + y) * g.P2 + x];
-    if (g.overlap > 0) {
-      const float cnt = (float)(cover_count(z, g.n0, g.step, g.roi) * cover_count(y, g.n1, g.step, g.roi) *
-                                cover_count(x, g.n2, g.step, g.roi));
-      v = (v / cnt) * 8;
-    }
-    v = v * scale;
-    out[i] = (T)v;  // truncation toward zero == ndarray.astype for in-range values
-  }
-}
-
-// The same for a z-slab: planes [z0, z0 + nz) of the (un-padded) volume from an accumulator that holds the padded planes from `za`
-// on (multi-GPU inference: every rank finalises the slab it owns, test_dice.py assemble='slab').
+// Planes [z0, z0 + nz) of the (un-padded) volume from an accumulator that holds the padded planes from `za` on: the whole volume is
+// z0 = 0, nz = L0, za = 0; a z-slab is multi-GPU inference (every rank finalises the slab it owns, test_dice.py assemble='slab').
 template <typename T>
 __global__ void k_finalize_slab(const float* __restrict__ acc, T* __restrict__ out, DiceGeom g, float scale, int z0, int nz, int za) {
   const long total = (long)nz * g.L1 * g.L2;
@@ -136,7 +51,7 @@ __global__ void k_finalize_slab(const float* __restrict__ acc, T* __restrict__ o
       v = (v / cnt) * 8;
     }
     v = v * scale;
-    out[i] = (T)v;
+    out[i] = (T)v;  // truncation toward zero == ndarray.astype for in-range values
   }
 }
 
@@ -194,21 +109,6 @@ __global__ void k_rescale_cast(const float* __restrict__ merged, T* __restrict__
   }
 }
 
-static bool make_geom(DiceGeom& g, int L0, int L1, int L2, int roi, int overlap, int border) {
-  if (L0 < 1 || L1 < 1 || L2 < 1 || roi < 1 || overlap < 0 || overlap >= roi || border < 1) return false;
-  g.L0 = L0; g.L1 = L1; g.L2 = L2; g.roi = roi; g.overlap = overlap; g.border = border; g.step = roi - overlap;
-  g.P0 = pad_len(L0, roi, overlap); g.P1 = pad_len(L1, roi, overlap); g.P2 = pad_len(L2, roi, overlap);
-  g.n0 = (g.P0 - overlap) / g.step; g.n1 = (g.P1 - overlap) / g.step; g.n2 = (g.P2 - overlap) / g.step;
-  // np.pad(mode='reflect') with border >= padded length is multi-fold; the reference never gets there
-  return border < g.P0 && border < g.P1 && border < g.P2;
-}
-
-static unsigned flat_grid(long n) {
-  long b = cdiv(n, 256);
-  if (b > 8192) b = 8192;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
 }  // namespace nc
 
 using namespace nc;
@@ -219,8 +119,11 @@ int nc_dice_cut_cube(const void* vol, int is_u16, int L0, int L1, int L2, int ro
                      float* cube, void* stream) {
   if (!vol || !cube) { set_error("dice_cut_cube: null pointer"); return NC_ERR_ARG; }
   DiceGeom g;
-  if (!make_geom(g, L0, L1, L2, roi, overlap, border)) { set_error("dice_cut_cube: bad geometry (border_cut must be >= 1)"); return NC_ERR_SHAPE; }
-  const long n = (long)g.n0 * g.n1 * g.n2;
+  if (!make_geom(g, kVolume, kOriginal, L0, L1, L2, roi, overlap, border) || !g.reflect_fits(kVolume)) {
+    set_error("dice_cut_cube: bad geometry (border_cut must be >= 1)");
+    return NC_ERR_SHAPE;
+  }
+  const long n = g.pieces();
   if (index < 0 || index >= n) { set_error("dice_cut_cube: cube index %d out of [0,%ld)", index, n); return NC_ERR_SHAPE; }
   const int xi = index % g.n2, yi = (index % (g.n2 * g.n1)) / g.n2, zi = index / (g.n2 * g.n1);
   const long E = roi + 2 * border;
@@ -234,84 +137,53 @@ int nc_dice_cut_cube(const void* vol, int is_u16, int L0, int L1, int L2, int ro
   return check_launch("dice_cut_cube");
 }
 
-int nc_rotate_crop(const void* vol, int is_u16, int D, int H, int W, int z0, int y0, int x0, int cz, int cy, int cx,
-                   const double* inv_affine, float* out, void* stream) {
-  if (!vol || !out || !inv_affine) { set_error("rotate_crop: null pointer"); return NC_ERR_ARG; }
-  if (D < 1 || H < 1 || W < 1 || cz < 1 || cy < 1 || cx < 1 || z0 < 0 || z0 + cz > D) {
-    set_error("rotate_crop: bad shape D=%d H=%d W=%d crop=(%d,%d,%d) z0=%d", D, H, W, cz, cy, cx, z0);
-    return NC_ERR_SHAPE;
-  }
-  const double* m = inv_affine;
-  hipStream_t s = (hipStream_t)stream;
-  const long total = (long)cz * cy * cx;
-  if (is_u16)
-    hipLaunchKernelGGL(k_rotate_crop<uint16_t>, dim3(flat_grid(total)), dim3(256), 0, s, (const uint16_t*)vol, H, W, z0,
-                       y0, x0, cz, cy, cx, m[0], m[1], m[2], m[3], m[4], m[5], 65535.0, 65535.0, out);
-  else
-    hipLaunchKernelGGL(k_rotate_crop<uint8_t>, dim3(flat_grid(total)), dim3(256), 0, s, (const uint8_t*)vol, H, W, z0,
-                       y0, x0, cz, cy, cx, m[0], m[1], m[2], m[3], m[4], m[5], 255.0, 255.0, out);
-  return check_launch("rotate_crop");
-}
-
 int nc_assemble_scatter_add(const float* cube, float* acc, int P0, int P1, int P2, int roi, int overlap, int border,
                             int index, void* stream) {
   if (!cube || !acc) { set_error("assemble_scatter_add: null pointer"); return NC_ERR_ARG; }
   if (overlap < 1) { set_error("assemble_scatter_add: overlap must be >= 1 (the reference assembler adds nothing for overlap 0, util/assemble_dice.py:170)"); return NC_ERR_SHAPE; }
-  if (roi < 1 || overlap >= roi || border < 1) { set_error("assemble_scatter_add: bad geometry (border_cut must be >= 1)"); return NC_ERR_SHAPE; }
-  DiceGeom g{};
-  g.roi = roi; g.overlap = overlap; g.border = border; g.step = roi - overlap;
-  g.P0 = P0; g.P1 = P1; g.P2 = P2;
-  g.n0 = (P0 - overlap) / g.step; g.n1 = (P1 - overlap) / g.step; g.n2 = (P2 - overlap) / g.step;
-  const long n = (long)g.n0 * g.n1 * g.n2;
-  if (g.n0 < 1 || g.n1 < 1 || g.n2 < 1 || index < 0 || index >= n) { set_error("assemble_scatter_add: cube index out of range"); return NC_ERR_SHAPE; }
-  const int xi = index % g.n2, yi = (index % (g.n2 * g.n1)) / g.n2, zi = index / (g.n2 * g.n1);
-  if (zi * g.step + roi > P0 || yi * g.step + roi > P1 || xi * g.step + roi > P2) { set_error("assemble_scatter_add: cube outside the volume"); return NC_ERR_SHAPE; }
+  DiceGeom g;  // (no reflect_fits: the overlap-add reflects nothing, a border of the padded length or more is fine here)
+  if (!make_geom(g, kVolume, kPadded, P0, P1, P2, roi, overlap, border)) { set_error("assemble_scatter_add: bad geometry (border_cut must be >= 1)"); return NC_ERR_SHAPE; }
+  if (index < 0 || index >= g.pieces()) { set_error("assemble_scatter_add: cube index out of range"); return NC_ERR_SHAPE; }
+  const int xi = index % g.n2, yi = (index % (g.n2 * g.n1)) / g.n2, zi = index / (g.n2 * g.n1);  // (n0 - 1) step + roi <= P0: inside the volume
   hipLaunchKernelGGL(k_scatter_add, dim3(flat_grid((long)roi * roi * roi)), dim3(256), 0, (hipStream_t)stream, cube, acc,
                      g, zi * g.step, yi * g.step, xi * g.step);
   return check_launch("assemble_scatter_add");
 }
 
-int nc_assemble_finalize(const float* acc, void* out, int out_is_u16, int P0, int P1, int P2, int L0, int L1, int L2,
-                         int roi, int overlap, void* stream) {
-  if (!acc || !out) { set_error("assemble_finalize: null pointer"); return NC_ERR_ARG; }
-  if (overlap < 1) { set_error("assemble_finalize: overlap must be >= 1 (util/assemble_dice.py:170)"); return NC_ERR_SHAPE; }
+// nc_assemble_finalize and nc_assemble_finalize_slab
+static int finalize_planes(const char* who, const float* acc, void* out, int out_is_u16, int P0, int P1, int P2, int L0, int L1, int L2, int roi,
+                           int overlap, int z0, int nz, int za, void* stream) {
+  if (!acc || !out) { set_error("%s: null pointer", who); return NC_ERR_ARG; }
+  if (overlap < 1) { set_error("%s: overlap must be >= 1 (util/assemble_dice.py:170)", who); return NC_ERR_SHAPE; }
   DiceGeom g;
-  if (!make_geom(g, L0, L1, L2, roi, overlap, 1) || g.P0 != P0 || g.P1 != P1 || g.P2 != P2) {
-    set_error("assemble_finalize: padded size does not match pad_for_dicing of the original size");
+  if (!make_geom(g, kVolume, kOriginal, L0, L1, L2, roi, overlap, 1) || g.P0 != P0 || g.P1 != P1 || g.P2 != P2) {
+    set_error("%s: padded size does not match pad_for_dicing of the original size", who);
     return NC_ERR_SHAPE;
   }
-  const long total = (long)L0 * L1 * L2;
+  if (z0 < 0 || nz < 1 || z0 + nz > L0 || za < 0 || za > z0) { set_error("%s: bad slab", who); return NC_ERR_SHAPE; }
+  const long total = (long)nz * L1 * L2;
   hipStream_t s = (hipStream_t)stream;
   if (out_is_u16)
-    hipLaunchKernelGGL(k_finalize<uint16_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc, (uint16_t*)out, g, 65535.f);
+    hipLaunchKernelGGL(k_finalize_slab<uint16_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc, (uint16_t*)out, g, 65535.f, z0, nz, za);
   else
-    hipLaunchKernelGGL(k_finalize<uint8_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc, (uint8_t*)out, g, 255.f);
-  return check_launch("assemble_finalize");
+    hipLaunchKernelGGL(k_finalize_slab<uint8_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc, (uint8_t*)out, g, 255.f, z0, nz, za);
+  return check_launch(who);
+}
+
+int nc_assemble_finalize(const float* acc, void* out, int out_is_u16, int P0, int P1, int P2, int L0, int L1, int L2,
+                         int roi, int overlap, void* stream) {
+  return finalize_planes("assemble_finalize", acc, out, out_is_u16, P0, P1, P2, L0, L1, L2, roi, overlap, 0, L0, 0, stream);
 }
 
 int nc_assemble_finalize_slab(const float* acc_slab, void* out, int out_is_u16, int P0, int P1, int P2, int L0, int L1, int L2, int roi,
                               int overlap, int z0, int nz, int za, void* stream) {
-  if (!acc_slab || !out) { set_error("assemble_finalize_slab: null pointer"); return NC_ERR_ARG; }
-  if (overlap < 1) { set_error("assemble_finalize_slab: overlap must be >= 1 (util/assemble_dice.py:170)"); return NC_ERR_SHAPE; }
-  DiceGeom g;
-  if (!make_geom(g, L0, L1, L2, roi, overlap, 1) || g.P0 != P0 || g.P1 != P1 || g.P2 != P2) {
-    set_error("assemble_finalize_slab: padded size does not match pad_for_dicing of the original size");
-    return NC_ERR_SHAPE;
-  }
-  if (z0 < 0 || nz < 1 || z0 + nz > L0 || za < 0 || za > z0) { set_error("assemble_finalize_slab: bad slab"); return NC_ERR_SHAPE; }
-  const long total = (long)nz * L1 * L2;
-  hipStream_t s = (hipStream_t)stream;
-  if (out_is_u16)
-    hipLaunchKernelGGL(k_finalize_slab<uint16_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc_slab, (uint16_t*)out, g, 65535.f, z0, nz, za);
-  else
-    hipLaunchKernelGGL(k_finalize_slab<uint8_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc_slab, (uint8_t*)out, g, 255.f, z0, nz, za);
-  return check_launch("assemble_finalize_slab");
+  return finalize_planes("assemble_finalize_slab", acc_slab, out, out_is_u16, P0, P1, P2, L0, L1, L2, roi, overlap, z0, nz, za, stream);
 }
 
 int nc_assemble_merge(const float* acc, float* merged, int L0, int L1, int L2, int roi, int overlap, void* stream) {
   if (!acc || !merged) { set_error("assemble_merge: null pointer"); return NC_ERR_ARG; }
   DiceGeom g;
-  if (overlap < 1 || !make_geom(g, L0, L1, L2, roi, overlap, 1)) { set_error("assemble_merge: bad geometry"); return NC_ERR_SHAPE; }
+  if (overlap < 1 || !make_geom(g, kVolume, kOriginal, L0, L1, L2, roi, overlap, 1)) { set_error("assemble_merge: bad geometry"); return NC_ERR_SHAPE; }
   hipLaunchKernelGGL(k_merge, dim3(flat_grid((long)g.P0 * g.P1 * g.P2)), dim3(256), 0, (hipStream_t)stream, acc, merged, g);
   return check_launch("assemble_merge");
 }
@@ -328,7 +200,7 @@ int nc_assemble_rescale_finalize(const float* merged, void* out, int out_is_u16,
                                  int overlap, float lo, float hi, float range, void* stream) {
   if (!merged || !out) { set_error("assemble_rescale_finalize: null pointer"); return NC_ERR_ARG; }
   DiceGeom g;
-  if (overlap < 1 || !make_geom(g, L0, L1, L2, roi, overlap, 1) || !(hi > lo) || !(range > 0.f)) {
+  if (overlap < 1 || !make_geom(g, kVolume, kOriginal, L0, L1, L2, roi, overlap, 1) || !(hi > lo) || !(range > 0.f)) {
     set_error("assemble_rescale_finalize: bad geometry or empty intensity range");
     return NC_ERR_SHAPE;
   }

@@ -7,63 +7,12 @@
 // Every entry point handles `count` consecutive tiles in ONE launch.  The scatter-add runs one thread per ACCUMULATOR pixel, which adds the
 // tiles of the batch that cover it in ascending tile index: no two threads write one address (no atomics), and the sum does not depend
 // on how the tile sequence is cut into batches.
-#include "common.hpp"
+#include "dice_geom.hpp"
 
 namespace nc {
 
-struct Dice2dGeom {
-  int L0, L1, L2, P1, P2, n1, n2, roi, overlap, border, step;
-  long ntiles;
-};
-
-namespace {
-
-__device__ __forceinline__ int reflect2d(int q, int P) {  // np.pad(mode='reflect') for |overhang| < P
-  if (q < 0) q = -q;
-  if (q >= P) q = 2 * (P - 1) - q;
-  return q;
-}
-
-inline int pad_len2d(int L, int roi, int overlap) {
-  const int step = roi - overlap;
-  return step * ((L + overlap) / step) + roi;  // L + pad
-}
-
-// the tile indices i in [0, n) with i*step <= p < i*step + roi are lo .. hi
-__device__ __forceinline__ void cover_range(int p, int n, int step, int roi, int& lo, int& hi) {
-  hi = p / step;
-  if (hi > n - 1) hi = n - 1;
-  lo = p - roi + 1;
-  lo = lo <= 0 ? 0 : (lo + step - 1) / step;
-}
-
-// the grid of the padded plane P1 x P2; false for a geometry the reference cannot dice
-bool grid2d(Dice2dGeom& g, int L0, int P1, int P2, int roi, int overlap, int border) {
-  if (L0 < 1 || P1 < 1 || P2 < 1 || roi < 1 || overlap < 0 || overlap >= roi || border < 1) return false;
-  g.L0 = L0; g.P1 = P1; g.P2 = P2; g.roi = roi; g.overlap = overlap; g.border = border; g.step = roi - overlap;
-  g.n1 = (P1 - overlap) / g.step; g.n2 = (P2 - overlap) / g.step;
-  if (g.n1 < 1 || g.n2 < 1) return false;
-  g.ntiles = (long)L0 * g.n1 * g.n2;
-  // np.pad(mode='reflect') with border >= padded length is multi-fold; the reference never gets there
-  return border < P1 && border < P2;
-}
-
-bool geom2d(Dice2dGeom& g, int L0, int L1, int L2, int roi, int overlap, int border) {
-  if (L1 < 1 || L2 < 1 || roi < 1 || overlap < 0 || overlap >= roi) return false;
-  g.L1 = L1; g.L2 = L2;
-  return grid2d(g, L0, pad_len2d(L1, roi, overlap), pad_len2d(L2, roi, overlap), roi, overlap, border);
-}
-
-unsigned flat_grid2d(long n) {
-  long b = cdiv(n, 256);
-  if (b > 8192) b = 8192;
-  return (unsigned)(b < 1 ? 1 : b);
-}
-
-}  // namespace
-
 template <typename T>
-__global__ void k_cut_tiles2d(const T* __restrict__ img, Dice2dGeom g, long first, int count, double den, float* __restrict__ tiles) {
+__global__ void k_cut_tiles2d(const T* __restrict__ img, DiceGeom g, long first, int count, double den, float* __restrict__ tiles) {
   const int E = g.roi + 2 * g.border;
   const long per = (long)g.n1 * g.n2, total = (long)count * E * E;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -71,8 +20,8 @@ __global__ void k_cut_tiles2d(const T* __restrict__ img, Dice2dGeom g, long firs
     const long t = first + i / ((long)E * E);
     const long z = t / per;
     const int r = (int)(t % per), yi = r / g.n2, xi = r % g.n2;
-    const int qy = reflect2d(yi * g.step + cy - g.border, g.P1);
-    const int qx = reflect2d(xi * g.step + cx - g.border, g.P2);
+    const int qy = reflect_idx(yi * g.step + cy - g.border, g.P1);
+    const int qx = reflect_idx(xi * g.step + cx - g.border, g.P2);
     float v = 0.f;
     if (qy < g.L1 && qx < g.L2) v = (float)((double)img[(z * g.L1 + qy) * g.L2 + qx] / den);
     tiles[i] = v;
@@ -80,7 +29,7 @@ __global__ void k_cut_tiles2d(const T* __restrict__ img, Dice2dGeom g, long firs
 }
 
 // rows [row0, row0 + nrows) of the accumulator seen as (L0 * P1) rows of P2 floats: the rows from the first tile's first to the last tile's last
-__global__ void k_scatter_add2d(const float* __restrict__ tiles, float* __restrict__ acc, Dice2dGeom g, long first, int count, long row0,
+__global__ void k_scatter_add2d(const float* __restrict__ tiles, float* __restrict__ acc, DiceGeom g, long first, int count, long row0,
                                 long nrows) {
   const int E = g.roi + 2 * g.border;
   const long per = (long)g.n1 * g.n2, total = nrows * g.P2, last = first + count;
@@ -107,15 +56,12 @@ __global__ void k_scatter_add2d(const float* __restrict__ tiles, float* __restri
 }
 
 template <typename T>
-__global__ void k_finalize2d(const float* __restrict__ acc, T* __restrict__ out, Dice2dGeom g, float scale) {
+__global__ void k_finalize2d(const float* __restrict__ acc, T* __restrict__ out, DiceGeom g, float scale) {
   const long total = (long)g.L0 * g.L1 * g.L2;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int x = (int)(i % g.L2), y = (int)((i / g.L2) % g.L1);
     const long z = i / ((long)g.L2 * g.L1);
-    int ylo, yhi, xlo, xhi;
-    cover_range(y, g.n1, g.step, g.roi, ylo, yhi);
-    cover_range(x, g.n2, g.step, g.roi, xlo, xhi);
-    const float cnt = (float)((yhi - ylo + 1) * (xhi - xlo + 1));
+    const float cnt = (float)(cover_count(y, g.n1, g.step, g.roi) * cover_count(x, g.n2, g.step, g.roi));
     float v = acc[(z * g.P1 + y) * g.P2 + x];
     v = __fmul_rn(__fmul_rn(__fdiv_rn(v, cnt), 8.f), scale);
     out[i] = (T)v;  // truncation toward zero == ndarray.astype for in-range values
@@ -131,19 +77,22 @@ extern "C" {
 int nc_dice2d_cut_tiles(const void* img, int is_u16, int L0, int L1, int L2, int roi, int overlap, int border, long first, int count,
                         float* tiles, void* stream) {
   if (!img || !tiles) { set_error("dice2d_cut_tiles: null pointer"); return NC_ERR_ARG; }
-  Dice2dGeom g;
-  if (!geom2d(g, L0, L1, L2, roi, overlap, border)) { set_error("dice2d_cut_tiles: bad geometry (border_cut must be >= 1)"); return NC_ERR_SHAPE; }
-  if (first < 0 || count < 1 || first + count > g.ntiles) {
-    set_error("dice2d_cut_tiles: tiles [%ld, %ld + %d) out of [0,%ld)", first, first, count, g.ntiles);
+  DiceGeom g;
+  if (!make_geom(g, kPlanes, kOriginal, L0, L1, L2, roi, overlap, border) || !g.reflect_fits(kPlanes)) {
+    set_error("dice2d_cut_tiles: bad geometry (border_cut must be >= 1)");
+    return NC_ERR_SHAPE;
+  }
+  if (first < 0 || count < 1 || first + count > g.pieces()) {
+    set_error("dice2d_cut_tiles: tiles [%ld, %ld + %d) out of [0,%ld)", first, first, count, g.pieces());
     return NC_ERR_SHAPE;
   }
   const long E = roi + 2 * border;
   hipStream_t s = (hipStream_t)stream;
   if (is_u16)
-    hipLaunchKernelGGL(k_cut_tiles2d<uint16_t>, dim3(flat_grid2d(count * E * E)), dim3(256), 0, s, (const uint16_t*)img, g, first, count,
+    hipLaunchKernelGGL(k_cut_tiles2d<uint16_t>, dim3(flat_grid(count * E * E)), dim3(256), 0, s, (const uint16_t*)img, g, first, count,
                        65535.0, tiles);
   else
-    hipLaunchKernelGGL(k_cut_tiles2d<uint8_t>, dim3(flat_grid2d(count * E * E)), dim3(256), 0, s, (const uint8_t*)img, g, first, count, 255.0,
+    hipLaunchKernelGGL(k_cut_tiles2d<uint8_t>, dim3(flat_grid(count * E * E)), dim3(256), 0, s, (const uint8_t*)img, g, first, count, 255.0,
                        tiles);
   return check_launch("dice2d_cut_tiles");
 }
@@ -152,13 +101,16 @@ int nc_assemble2d_scatter_add(const float* tiles, float* acc, int L0, int P1, in
                               int count, void* stream) {
   if (!tiles || !acc) { set_error("assemble2d_scatter_add: null pointer"); return NC_ERR_ARG; }
   if (overlap < 1) { set_error("assemble2d_scatter_add: overlap must be >= 1 (the reference assembler adds nothing for overlap 0, util/assemble_dice.py:170)"); return NC_ERR_SHAPE; }
-  Dice2dGeom g{};
-  if (!grid2d(g, L0, P1, P2, roi, overlap, border)) { set_error("assemble2d_scatter_add: bad geometry (border_cut must be >= 1)"); return NC_ERR_SHAPE; }
-  if (first < 0 || count < 1 || first + count > g.ntiles) { set_error("assemble2d_scatter_add: tile index out of range"); return NC_ERR_SHAPE; }
+  DiceGeom g;
+  if (!make_geom(g, kPlanes, kPadded, L0, P1, P2, roi, overlap, border) || !g.reflect_fits(kPlanes)) {
+    set_error("assemble2d_scatter_add: bad geometry (border_cut must be >= 1)");
+    return NC_ERR_SHAPE;
+  }
+  if (first < 0 || count < 1 || first + count > g.pieces()) { set_error("assemble2d_scatter_add: tile index out of range"); return NC_ERR_SHAPE; }
   const long per = (long)g.n1 * g.n2, tl = first + count - 1;
   const long row0 = (first / per) * P1 + ((first % per) / g.n2) * (long)g.step;
   const long row1 = (tl / per) * P1 + ((tl % per) / g.n2) * (long)g.step + roi;  // <= (plane + 1) * P1: (n1 - 1) step + roi <= P1
-  hipLaunchKernelGGL(k_scatter_add2d, dim3(flat_grid2d((row1 - row0) * P2)), dim3(256), 0, (hipStream_t)stream, tiles, acc, g, first, count,
+  hipLaunchKernelGGL(k_scatter_add2d, dim3(flat_grid((row1 - row0) * P2)), dim3(256), 0, (hipStream_t)stream, tiles, acc, g, first, count,
                      row0, row1 - row0);
   return check_launch("assemble2d_scatter_add");
 }
@@ -167,17 +119,17 @@ int nc_assemble2d_finalize(const float* acc, void* out, int out_is_u16, int L0, 
                            void* stream) {
   if (!acc || !out) { set_error("assemble2d_finalize: null pointer"); return NC_ERR_ARG; }
   if (overlap < 1) { set_error("assemble2d_finalize: overlap must be >= 1 (util/assemble_dice.py:170)"); return NC_ERR_SHAPE; }
-  Dice2dGeom g;
-  if (!geom2d(g, L0, L1, L2, roi, overlap, 1) || g.P1 != P1 || g.P2 != P2) {
+  DiceGeom g;
+  if (!make_geom(g, kPlanes, kOriginal, L0, L1, L2, roi, overlap, 1) || g.P1 != P1 || g.P2 != P2) {
     set_error("assemble2d_finalize: padded size does not match pad_for_dicing of the original size");
     return NC_ERR_SHAPE;
   }
   const long total = (long)L0 * L1 * L2;
   hipStream_t s = (hipStream_t)stream;
   if (out_is_u16)
-    hipLaunchKernelGGL(k_finalize2d<uint16_t>, dim3(flat_grid2d(total)), dim3(256), 0, s, acc, (uint16_t*)out, g, 65535.f);
+    hipLaunchKernelGGL(k_finalize2d<uint16_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc, (uint16_t*)out, g, 65535.f);
   else
-    hipLaunchKernelGGL(k_finalize2d<uint8_t>, dim3(flat_grid2d(total)), dim3(256), 0, s, acc, (uint8_t*)out, g, 255.f);
+    hipLaunchKernelGGL(k_finalize2d<uint8_t>, dim3(flat_grid(total)), dim3(256), 0, s, acc, (uint8_t*)out, g, 255.f);
   return check_launch("assemble2d_finalize");
 }
 

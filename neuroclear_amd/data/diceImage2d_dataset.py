@@ -5,14 +5,11 @@ The input is one plane (L1, L2) or a stack (L0, L1, L2) that is diced plane by p
 reflected, and a plane is held as a stack of one.  The ORIGINAL uint16 / uint8 image is uploaded once and stays resident in
 HBM; `cut(first, count)` launches nc_dice2d_cut_tiles ONCE for `count` consecutive tiles -- the zero dicing pad, the reflect
 border and v / 65535 (fp64, then rounded to fp32 like numpy does) are index arithmetic on the device, as in the 3-D set."""
-import os
-
-import numpy as np
 import torch
 
 from .._lib import L_, P, check, lib
 from ..util import util
-from .diceImage_dataset import _load_volume
+from .diceImage_dataset import load_resident
 
 
 class DiceImage2DDataSet:
@@ -26,34 +23,13 @@ class DiceImage2DDataSet:
         if self.border_cut < 1:
             raise ValueError('border_cut must be >= 1: the reference crops cube[b:-b], which is empty for b = 0 '
                              '(util/assemble_dice.py:143-145)')
-        if image is None:
-            names = sorted(f for f in os.listdir(opt.dataroot) if not f.startswith('.') and
-                           f.endswith(('.npy', '.tif', '.tiff')))
-            if not names:
-                raise FileNotFoundError('no image (.npy/.tif) under %s' % opt.dataroot)
-            image = _load_volume(os.path.join(opt.dataroot, names[0]))
-        if isinstance(image, np.ndarray):
-            if image.dtype not in (np.uint8, np.uint16):
-                raise TypeError('input volume must be uint8 or uint16 (data/base_dataset.py:134-143), got %s'
-                                % image.dtype)
-            self.is_u16 = image.dtype == np.uint16
-            image = np.ascontiguousarray(image) if image.flags.writeable else image.copy()  # (torch takes no read-only array)
-            # torch has no uint16 arithmetic; the bytes are only ever read by the HIP kernel
-            host = torch.from_numpy(image.view(np.int16) if self.is_u16 else image)
-        else:
-            if image.dtype not in (torch.uint8, torch.int16, torch.uint16):
-                raise TypeError('input volume must be uint8 or uint16 (data/base_dataset.py:134-143), got %s'
-                                % image.dtype)
-            self.is_u16 = image.dtype != torch.uint8
-            host = image
-        if host.dim() not in (2, 3):
+        self.image, self.is_u16, self.device = load_resident(opt, image, 'image')
+        if self.image.dim() not in (2, 3):
             raise ValueError('expected one plane (L1, L2) or a stack of planes (L0, L1, L2)')
-        self.single_plane = host.dim() == 2
+        self.single_plane = self.image.dim() == 2
         if self.single_plane:
-            host = host.unsqueeze(0)
-        self.device = torch.device('cuda', opt.gpu_ids[0]) if getattr(opt, 'gpu_ids', None) else torch.device('cuda')
-        self.image = host.contiguous().to(self.device)
-        self.image_size_original = tuple(int(s) for s in host.shape)
+            self.image = self.image.unsqueeze(0)
+        self.image_size_original = tuple(int(s) for s in self.image.shape)
         L0 = self.image_size_original[0]
         self.image_size = (L0,) + util.padded_shape(self.image_size_original[1:], self.roi_size, self.overlap)
         self.steps = (L0,) + util.grid_steps(self.image_size[1:], self.roi_size, self.overlap)

@@ -21,6 +21,31 @@ def _load_volume(path):
     return tiff.imread(path)  # uncompressed grayscale TIFF stacks (what the reference's skimage.io.imsave writes)
 
 
+def load_resident(opt, image, what='volume'):
+    """The input of a dice dataset, resident on the device: the first .npy / .tif under opt.dataroot, or `image` given directly (numpy / torch,
+    uint8 or uint16).  Returns (tensor on the device -- uint16 as int16 bits --, is_u16, device)."""
+    if image is None:
+        names = sorted(f for f in os.listdir(opt.dataroot) if not f.startswith('.') and
+                       f.endswith(('.npy', '.tif', '.tiff')))
+        if not names:
+            raise FileNotFoundError('no %s (.npy/.tif) under %s' % (what, opt.dataroot))
+        image = _load_volume(os.path.join(opt.dataroot, names[0]))
+    if isinstance(image, np.ndarray):
+        if image.dtype not in (np.uint8, np.uint16):
+            raise TypeError('input volume must be uint8 or uint16 (data/base_dataset.py:134-143), got %s' % image.dtype)
+        is_u16 = image.dtype == np.uint16
+        image = np.ascontiguousarray(image) if image.flags.writeable else image.copy()  # (torch takes no read-only array)
+        # torch has no uint16 arithmetic; the bytes are only ever read by the HIP kernel
+        host = torch.from_numpy(image.view(np.int16) if is_u16 else image)
+    else:
+        if image.dtype not in (torch.uint8, torch.int16, torch.uint16):
+            raise TypeError('input volume must be uint8 or uint16 (data/base_dataset.py:134-143), got %s' % image.dtype)
+        is_u16 = image.dtype != torch.uint8
+        host = image
+    device = torch.device('cuda', opt.gpu_ids[0]) if getattr(opt, 'gpu_ids', None) else torch.device('cuda')
+    return host.contiguous().to(device), is_u16, device
+
+
 class DiceImageDataSet:
     @staticmethod
     def modify_commandline_options(parser, is_train=False):
@@ -38,27 +63,10 @@ class DiceImageDataSet:
         if self.border_cut < 1:
             raise ValueError('border_cut must be >= 1: the reference crops cube[b:-b], which is empty for b = 0 '
                              '(util/assemble_dice.py:143-145)')
-        if volume is None:
-            names = sorted(f for f in os.listdir(opt.dataroot) if not f.startswith('.') and
-                           f.endswith(('.npy', '.tif', '.tiff')))
-            if not names:
-                raise FileNotFoundError('no volume (.npy/.tif) under %s' % opt.dataroot)
-            volume = _load_volume(os.path.join(opt.dataroot, names[0]))
-        if isinstance(volume, np.ndarray):
-            if volume.dtype not in (np.uint8, np.uint16):
-                raise TypeError('input volume must be uint8 or uint16 (data/base_dataset.py:134-143), got %s'
-                                % volume.dtype)
-            self.is_u16 = volume.dtype == np.uint16
-            # torch has no uint16 arithmetic; the bytes are only ever read by the HIP kernel
-            host = torch.from_numpy(volume.view(np.int16) if self.is_u16 else volume)
-        else:
-            self.is_u16 = volume.dtype in (torch.int16, torch.uint16)
-            host = volume
-        if host.dim() != 3:
+        self.volume, self.is_u16, self.device = load_resident(opt, volume)
+        if self.volume.dim() != 3:
             raise ValueError('expected a 3-D volume')
-        self.device = torch.device('cuda', opt.gpu_ids[0]) if getattr(opt, 'gpu_ids', None) else torch.device('cuda')
-        self.volume = host.contiguous().to(self.device)
-        self.image_size_original = tuple(int(s) for s in host.shape)
+        self.image_size_original = tuple(int(s) for s in self.volume.shape)
         self.image_size = util.padded_shape(self.image_size_original, self.roi_size, self.overlap)
         self.steps = util.grid_steps(self.image_size, self.roi_size, self.overlap)
 

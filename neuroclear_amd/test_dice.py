@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from .data.diceImage_dataset import DiceImageDataSet
+from .dice_cli import build_parser, load_first, save_results
 from .util.assemble_dice import Assemble_Dice, match_cube
 
 
@@ -455,44 +456,8 @@ def write_outputs(opt, web_dir, fake_volume, real_volume=None, gt_volume=None):
 
 
 def main(argv=None):
-    import argparse
-    import os
     from . import models
-    p = argparse.ArgumentParser(description='test_dice.py on MI355X (reference README.md:150-157)')
-    p.add_argument('--dataroot', required=True)
-    p.add_argument('--name', default='experiment_name')
-    p.add_argument('--checkpoints_dir', default='./checkpoints')
-    p.add_argument('--results_dir', default='./results/')
-    p.add_argument('--gpu_ids', default='0')
-    p.add_argument('--model', default='test')
-    p.add_argument('--model_suffix', default='')
-    p.add_argument('--netG', default='unet_deconv')
-    p.add_argument('--norm', default='instance')
-    p.add_argument('--init_type', default='normal')
-    p.add_argument('--init_gain', type=float, default=0.02)
-    p.add_argument('--input_nc', type=int, default=1)
-    p.add_argument('--output_nc', type=int, default=1)
-    p.add_argument('--ngf', type=int, default=64)
-    p.add_argument('--image_dimension', type=int, default=3)
-    p.add_argument('--dice_size', type=int, nargs='+', default=[120, 120, 120])
-    p.add_argument('--overlap', type=int, default=15)
-    p.add_argument('--border_cut', type=int, default=10)
-    p.add_argument('--data_type', default='uint16')
-    p.add_argument('--epoch', default='latest')
-    p.add_argument('--load_iter', type=int, default=0)
-    p.add_argument('--skip_real', action='store_true')
-    p.add_argument('--no_dropout', action='store_true')
-    p.add_argument('--histogram_match', action='store_true')
-    p.add_argument('--normalize_intensity', action='store_true')
-    p.add_argument('--sat_level', type=float, nargs='+', default=[0.25, 99.75])
-    p.add_argument('--verbose', action='store_true')
-    p.add_argument('--phase', default='test')
-    p.add_argument('--data_name', default=None)
-    p.add_argument('--dataroot_gt', default=None, help='directory with the ground-truth volume: enables the PSNR report')
-    p.add_argument('--save_volume', action='store_true')
-    p.add_argument('--save_projections', action='store_true')
-    p.add_argument('--save_slices', action='store_true')
-    opt = p.parse_args(argv)
+    opt = build_parser().parse_args(argv)
     opt.gpu_ids = [int(g) for g in opt.gpu_ids.split(',') if int(g) >= 0]
     opt.isTrain, opt.continue_train, opt.preprocess = False, False, 'addColorChannel'
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -504,30 +469,13 @@ def main(argv=None):
         init_process_group(torch.device('cuda', opt.gpu_ids[0]))
     model = models.create_model(opt)
     model.setup(opt)
-    from .data.diceImage_dataset import _load_volume
-    names = sorted(f for f in os.listdir(opt.dataroot) if f.endswith(('.npy', '.tif', '.tiff')))
-    vol = _load_volume(os.path.join(opt.dataroot, names[0]))
-    gt = None
-    if opt.dataroot_gt is not None:
-        gnames = sorted(f for f in os.listdir(opt.dataroot_gt) if f.endswith(('.npy', '.tif', '.tiff')))
-        gt = _load_volume(os.path.join(opt.dataroot_gt, gnames[0]))
+    vol, gt = load_first(opt.dataroot), load_first(opt.dataroot_gt)
     want_real = not opt.skip_real
     res = diced_inference(model.netG, vol, opt, rank, world, with_real=want_real)
-    metrics = {}
-    if rank == 0:
-        out, real = res if want_real else (res, None)
-        print('Image volume re-assembled.')
-        print('re-merged image shape: {}'.format(out.shape))
-        # web_dir as at test_dice.py:80-88
-        base = opt.name if opt.data_name is None else opt.data_name + '_by_' + opt.name
-        web_dir = os.path.join(opt.results_dir, base, '{}_{}'.format(opt.phase, opt.epoch))
-        if opt.load_iter > 0:
-            web_dir = '{:s}_iter{:d}'.format(web_dir, opt.load_iter)
-        os.makedirs(os.path.join(web_dir, 'volumes'), exist_ok=True)
-        np.save(os.path.join(web_dir, 'volumes', 'output_volume.npy'), out)
-        metrics = write_outputs(opt, web_dir, out, real, gt)
-        print('----Test done----')
-    return metrics
+    if rank != 0:
+        return {}
+    out, real = res if want_real else (res, None)
+    return save_results(opt, out, real, gt)
 
 
 if __name__ == '__main__':

@@ -1,4 +1,5 @@
-"""Assemble_Dice on the device (reference: util/assemble_dice.py:11-213).
+"""Assemble_Dice on the device (reference: util/assemble_dice.py:11-213), and Assemble_Base, which it shares with
+util/assemble_dice2d.py.
 
 Same interface -- Assemble_Dice(opt), addToStack(visuals), assemble_all(), getDict() -- but the cubes never leave HBM:
 addToStack crops the border and overlap-adds cube/8 into a padded fp32 accumulator right away (nc_assemble_scatter_add,
@@ -34,22 +35,31 @@ def match_histograms(source, template):
     return out
 
 
-def match_cube(fake, real, roi_size, border_cut, device):
-    """util/assemble_dice.py:149-151: the border-cropped fake cube matched to the border-cropped real cube; returns the
-    (R+2b)^3 fake cube with its interior replaced (the border is dropped by add_cube anyway)."""
+def match_interior(fake, real, roi_size, border_cut, device, axes):
+    """util/assemble_dice.py:149-151: the border-cropped fake piece matched to the border-cropped real piece; returns the
+    (R+2b)^axes fake piece with its interior replaced (the border is dropped by the overlap-add anyway)."""
     E, b = roi_size + 2 * border_cut, border_cut
-    fake = fake.reshape(E, E, E).to(device, torch.float32)
-    real = real.reshape(E, E, E).to(device, torch.float32)
+    fake = fake.reshape((E,) * axes).to(device, torch.float32)
+    real = real.reshape((E,) * axes).to(device, torch.float32)
+    inner = (slice(b, -b),) * axes
     out = fake.clone()
-    out[b:-b, b:-b, b:-b] = match_histograms(fake[b:-b, b:-b, b:-b], real[b:-b, b:-b, b:-b])
+    out[inner] = match_histograms(fake[inner], real[inner])
     return out
 
 
-class Assemble_Dice:
-    def __init__(self, opt, image_size_original=None, slab=None):
-        """image_size_original: (z, y, x) of the un-padded volume; when omitted it is taken from opt.volume_shape.
-        slab = (za, zb): the accumulators hold only the padded planes [za, zb) (sharded inference, test_dice.py assemble='slab':
-        a rank's cubes touch two or three z-layers); add_cube then accepts only cubes inside that range."""
+def match_cube(fake, real, roi_size, border_cut, device):
+    return match_interior(fake, real, roi_size, border_cut, device, 3)
+
+
+class Assemble_Base:
+    """What Assemble_Dice and Assemble_Dice2D share: the option checks, the padded fp32 accumulators, the addToStack loop, the host
+    conversion and getDict.  The last `axes` axes of the (L0, L1, L2) image are diced; a subclass adds its geometry, `_add_one` (one
+    piece of addToStack) and `_finalize(acc, out)`."""
+    axes, pieces = 3, 'cubes'
+
+    def __init__(self, opt, image_size_original=None, acc_planes=None):
+        """image_size_original: (L0, L1, L2), un-padded; when omitted it is taken from opt.volume_shape.
+        acc_planes: the accumulators hold that many planes of axis 0 only."""
         if image_size_original is None:
             image_size_original = opt.volume_shape
         self.image_size_original = tuple(int(s) for s in image_size_original)
@@ -62,12 +72,11 @@ class Assemble_Dice:
             raise ValueError('overlap must be >= 1: the reference assembler adds nothing for overlap 0 '
                              '(util/assemble_dice.py:170) and returns an all-zero volume')
         self.histogram_match = bool(getattr(opt, 'histogram_match', False))
-        self.normalize_intensity = bool(getattr(opt, 'normalize_intensity', False))
-        self.p1, self.p99 = getattr(opt, 'sat_level', [0.25, 99.75])  # options/test_options.py:25
         self.step = self.roi_size - self.overlap
-        self.image_size = util.padded_shape(self.image_size_original, self.roi_size, self.overlap)
-        self.z_steps, self.y_steps, self.x_steps = util.grid_steps(self.image_size, self.roi_size, self.overlap)
-        self.len_cube_queue = self.z_steps * self.y_steps * self.x_steps
+        k = 3 - self.axes  # the leading axes are neither diced nor padded: one piece per plane
+        self.image_size = self.image_size_original[:k] + util.padded_shape(self.image_size_original[k:], self.roi_size, self.overlap)
+        self.z_steps, self.y_steps, self.x_steps = self.image_size[:k] + util.grid_steps(self.image_size[k:], self.roi_size, self.overlap)
+        self.len_queue = self.z_steps * self.y_steps * self.x_steps
         self.visual_names = ['real', 'fake']
         self.imtype = opt.data_type
         if self.imtype not in ('uint8', 'uint16'):
@@ -77,8 +86,7 @@ class Assemble_Dice:
         self.acc = OrderedDict()
         self.count = OrderedDict()
         self.visual_ret = OrderedDict()
-        self.slab = None if slab is None else (int(slab[0]), int(slab[1]))
-        shape = self.image_size if self.slab is None else (self.slab[1] - self.slab[0],) + tuple(self.image_size[1:])
+        shape = self.image_size if acc_planes is None else (acc_planes,) + tuple(self.image_size[1:])
         for name in self.visual_names:
             if self.skip_real and name == 'real':
                 continue
@@ -91,7 +99,46 @@ class Assemble_Dice:
 
     def indexToCoordinates(self, index):
         z, y, x = self.indexTo3DIndex(index)
-        return z * self.step, y * self.step, x * self.step
+        return z * (self.step if self.axes == 3 else 1), y * self.step, x * self.step
+
+    def addToStack(self, piece):
+        """piece: OrderedDict {'real': [1,1,E,..,E], 'fake': ...} as returned by model.get_current_visuals(): one piece per call, in
+        index order."""
+        if self.histogram_match:
+            piece = OrderedDict(piece)
+            piece['fake'] = match_interior(piece['fake'], piece['real'], self.roi_size, self.border_cut, self.device, self.axes)
+        for name in self.acc:
+            self._add_one(name, piece[name], self.count[name])
+
+    def _empty_out(self, shape):
+        return torch.empty(shape, dtype=torch.int16 if self.imtype == 'uint16' else torch.uint8, device=self.device)
+
+    def _to_host(self, out):
+        host = out.cpu().numpy()  # torch has no uint16 arithmetic: the kernels wrote uint16 bits into an int16 tensor
+        return host.view(np.uint16) if self.imtype == 'uint16' else host
+
+    def assemble_all(self):
+        for name, acc in self.acc.items():
+            if self.count[name] != self.len_queue:
+                raise Exception('expected %d %s for %s, got %d' % (self.len_queue, self.pieces, name, self.count[name]))
+            out = self._empty_out(self.image_size_original)
+            self._finalize(acc, out)
+            self.visual_ret[name] = self._to_host(out)
+
+    def getDict(self):
+        return self.visual_ret
+
+
+class Assemble_Dice(Assemble_Base):
+    def __init__(self, opt, image_size_original=None, slab=None):
+        """image_size_original: (z, y, x) of the un-padded volume; when omitted it is taken from opt.volume_shape.
+        slab = (za, zb): the accumulators hold only the padded planes [za, zb) (sharded inference, test_dice.py assemble='slab':
+        a rank's cubes touch two or three z-layers); add_cube then accepts only cubes inside that range."""
+        self.slab = None if slab is None else (int(slab[0]), int(slab[1]))
+        super().__init__(opt, image_size_original, None if slab is None else self.slab[1] - self.slab[0])
+        self.normalize_intensity = bool(getattr(opt, 'normalize_intensity', False))
+        self.p1, self.p99 = getattr(opt, 'sat_level', [0.25, 99.75])  # options/test_options.py:25
+        self.len_cube_queue = self.len_queue
 
     def add_cube(self, name, cube, index):
         """Overlap-add one (R+2b)^3 network output at cube position `index`."""
@@ -113,19 +160,9 @@ class Assemble_Dice:
                                             self.roi_size, self.overlap, self.border_cut, int(index),
                                             P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_scatter_add')
 
-    def match_cube(self, fake, real):
-        return match_cube(fake, real, self.roi_size, self.border_cut, self.device)
-
-    def addToStack(self, cube):
-        """cube: OrderedDict {'real': [1,1,E,E,E], 'fake': ...} as returned by model.get_current_visuals()."""
-        if self.histogram_match:
-            cube = OrderedDict(cube)
-            cube['fake'] = self.match_cube(cube['fake'], cube['real'])
-        for name in self.visual_names:
-            if self.skip_real and name == 'real':
-                continue
-            self.add_cube(name, cube[name], self.count[name])
-            self.count[name] += 1
+    def _add_one(self, name, cube, index):
+        self.add_cube(name, cube, index)
+        self.count[name] += 1
 
     def finalize_slab(self, own_acc, za, zb):
         """(acc / count) * 8 * scale and the truncating cast for the padded planes [za, zb) held in own_acc (already complete: every
@@ -133,10 +170,9 @@ class Assemble_Dice:
         L0, L1, L2 = self.image_size_original
         P0, P1, P2 = self.image_size
         z0, z1 = min(za, L0), min(zb, L0)
-        u16 = self.imtype == 'uint16'
-        out = torch.empty((z1 - z0, L1, L2), dtype=torch.int16 if u16 else torch.uint8, device=self.device)
+        out = self._empty_out((z1 - z0, L1, L2))
         if z1 > z0:
-            check(lib().nc_assemble_finalize_slab(P(own_acc.data_ptr()), P(out.data_ptr()), 1 if u16 else 0, P0, P1, P2, L0,
+            check(lib().nc_assemble_finalize_slab(P(own_acc.data_ptr()), P(out.data_ptr()), int(self.imtype == 'uint16'), P0, P1, P2, L0,
                                                   L1, L2, self.roi_size, self.overlap, z0, z1 - z0, za,
                                                   P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_finalize_slab')
         return out
@@ -144,23 +180,16 @@ class Assemble_Dice:
     def assemble_all(self):
         if self.slab is not None:
             raise Exception('a slab accumulator is finalised by its owner ranks (finalize_slab), not by assemble_all')
+        super().assemble_all()
+
+    def _finalize(self, acc, out):
+        if self.normalize_intensity:
+            return self._finalize_normalized(acc, out, self.imtype == 'uint16')
         L0, L1, L2 = self.image_size_original
         P0, P1, P2 = self.image_size
-        for name, acc in self.acc.items():
-            if self.count[name] != self.len_cube_queue:
-                raise Exception('expected %d cubes for %s, got %d' % (self.len_cube_queue, name, self.count[name]))
-            u16 = self.imtype == 'uint16'
-            out = torch.empty((L0, L1, L2), dtype=torch.int16 if u16 else torch.uint8, device=self.device)
-            if self.normalize_intensity:
-                self._finalize_normalized(acc, out, u16)
-                host = out.cpu().numpy()
-                self.visual_ret[name] = host.view(np.uint16) if u16 else host
-                continue
-            check(lib().nc_assemble_finalize(P(acc.data_ptr()), P(out.data_ptr()), 1 if u16 else 0, P0, P1,
-                                             P2, L0, L1, L2, self.roi_size, self.overlap,
-                                             P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_finalize')
-            host = out.cpu().numpy()
-            self.visual_ret[name] = host.view(np.uint16) if u16 else host
+        check(lib().nc_assemble_finalize(P(acc.data_ptr()), P(out.data_ptr()), int(self.imtype == 'uint16'), P0, P1,
+                                         P2, L0, L1, L2, self.roi_size, self.overlap,
+                                         P(torch.cuda.current_stream().cuda_stream)), 'nc_assemble_finalize')
 
     def _finalize_normalized(self, acc, out, u16):
         """util/assemble_dice.py:184-203 with --normalize_intensity: percentiles over the merged PADDED volume."""
@@ -178,6 +207,3 @@ class Assemble_Dice:
                                                  L1, L2, self.roi_size, self.overlap,
                                                  np.float32(p_lo), np.float32(p_hi), np.float32(p_hi - p_lo),
                                                  stream), 'nc_assemble_rescale_finalize')
-
-    def getDict(self):
-        return self.visual_ret

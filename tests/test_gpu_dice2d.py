@@ -278,6 +278,33 @@ def test_classes_mirror_the_3d_ones():
     assert list(asm.getDict()) == ['fake'] and np.array_equal(asm.getDict()['fake'], back)
 
 
+def test_both_datasets_load_their_input_alike():
+    """One loader behind both classes (data/diceImage_dataset.load_resident): a torch tensor that is neither uint8, int16 nor uint16 is refused
+    -- the 3-D class used to read it as uint8 --, a read-only numpy array is copied, and int16 / uint16 tensors carry uint16 bits."""
+    from neuroclear_amd.data.diceImage2d_dataset import DiceImage2DDataSet
+    from neuroclear_amd.data.diceImage_dataset import DiceImageDataSet
+    g, stack, tiles, *_ = reference(0, 'uint16')
+    assert not stack.flags.writeable
+    opt = make_opt()
+    signed = torch.from_numpy(stack.view(np.int16).copy())
+    for cls in (DiceImageDataSet, DiceImage2DDataSet):
+        for dt in (torch.float32, torch.int32, torch.int8, torch.float16):
+            with pytest.raises(TypeError, match='must be uint8 or uint16'):
+                cls(opt, signed.to(dt))
+        with pytest.raises(TypeError, match='must be uint8 or uint16'):
+            cls(opt, stack.astype(np.int16))
+        resident = [cls(opt, stack), cls(opt, signed), cls(opt, signed.to(DEV))]
+        assert all(d.is_u16 and d.size_original() == g.L for d in resident)
+        assert not cls(opt, stack.astype(np.uint8)).is_u16 and not cls(opt, signed.to(torch.uint8)).is_u16
+        first = [d[0]['A'].cpu().numpy() for d in resident]
+        assert np.array_equal(first[0], first[1]) and np.array_equal(first[0], first[2])
+    # the 2-D set's first tile is the restatement's; the 3-D set's first cube holds the same pixels where the two overlap (plane 0, no reflection)
+    assert np.array_equal(first[0][0].view(np.int32), tiles[0].view(np.int32))
+    cube = DiceImageDataSet(opt, stack)[0]['A'][0].cpu().numpy()
+    b = g.border
+    assert np.array_equal(cube[b, b:, b:].view(np.int32), tiles[0][b:, b:].view(np.int32))
+
+
 @pytest.mark.parametrize('ndim', [2, 3])
 def test_main_with_image_dimension_2(tmp_path, ndim):
     """A seeded checkpoint saved under the reference's file name; the 2-D entry script (neuroclear_amd.infer_dice2d.main, test_dice.py's command
