@@ -22,6 +22,10 @@ inline int check_launch(const char* what) {
 }
 
 inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }  // bytes of a workspace region
+inline size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }        // floats of a workspace region: 256 bytes
+// a whole-network call is a chain of launches: leave at the first that fails
+#define NC_TRY(expr) do { int e_ = (expr); if (e_) return e_; } while (0)
 
 // Kernels with more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised once per (kernel, DEVICE): the
 // attribute belongs to the code object loaded on that device, so a process that drives several GPUs (the reference's nn.DataParallel
@@ -350,6 +354,7 @@ int act_split2h_pool(const float* x, const float* mean, const float* rstd, float
 int conv_s3x(const void* xs, const float* w, const float* bias, float* y, int N, int Cin, int D, int H, int W, int Kout, int KS, long so,
              long si, int flip, void* wp_ws, hipStream_t s, const unsigned* guard = nullptr);
 bool conv_keep_supported(int N, int C, int D, int H, int W, int K, int ks);
+bool conv_fwd_on_split(int N, int C, int D, int H, int W, int K, int ks);  // api.hip: nc_conv_fwd takes the layer to the split-operand kernels
 // stats_part (nullable; two-term 3^3 layers only -- conv_layer_h2): the convolution leaves the partial InstanceNorm sums of its output there
 // (s3x_stats_bytes; s3x_stats_finalize turns them into mean / rstd)
 int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K, int ks, void* ws,

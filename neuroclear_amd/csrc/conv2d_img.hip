@@ -438,8 +438,6 @@ bool sconv_layer_ok(const ConvDims& d) {
          (long)d.N * d.C * d.H * d.W < (1L << 31) && (long)d.N * d.K * d.Ho * d.Wo < (1L << 31);
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ---- weight gradient of the same layers: dw[k][c][ty][tx] = sum over (image, u, v) of dy[k][u][v] * x[c][u*s-1+ty][v*s-1+tx]
 // as a GEMM D[k][(c, tap)] whose REDUCTION axis is the flat column axis j = (image, u, v).  A workgroup (4 waves, 2 x 2) owns
 // 128 dy channels x NCW = 4 * NTW input channels (x 16 taps) and one chunk of columns, walked in stages of 64 columns:

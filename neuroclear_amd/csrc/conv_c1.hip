@@ -368,10 +368,9 @@ int conv_fwd_to1_k3(const float* x, const float* w, float* y, int N, int C, int 
   const int zc = (D + nz - 1) / nz;
   nz = (D + zc - 1) / zc;
   const dim3 grid((unsigned)(ntx * nty * nz), (unsigned)N);
-  static const bool dma = true;
   if (W % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0) {
     const float* zeros = nc_zero_page();
-    if (dma && zeros) {
+    if (zeros) {
       // channel groups (partial volumes, added in a fixed order): four times the workgroups without reading anything twice -- y has ONE channel
       static const int gwant = 4;
       int G = gwant;

@@ -539,7 +539,6 @@ size_t packed_bytes(int Cin, int Kout, int KS) {
   const int ksteps = KS == 5 ? (KS * KS + 1) / 2 * 2 : KS * KS;  // taps per plane incl. the zero tap of the 5^3 pairing
   return (size_t)Cin * Kout * KS * ksteps * 2;
 }
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <int DT, int KZ, int KY, int KX, bool PAIR, int VB, int NA>
 int launch_h(const HParams& p, int lds, hipStream_t s) {

@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(256) k_split3(const float* __restrict__ x, uin
 
 // InstanceNorm normalisation + (Leaky)ReLU (norm_act.hip k_in_act_fwd: the same arithmetic, operation for operation) writing the
 // S3 form of the result -- and the fp32 tensor too when y != NULL: a layer whose only consumer is a split-operand convolution
-// never exists in fp32 (whole-network forward, api.hip).
+// never exists in fp32 (whole-network forward, unet_fwd.hip).
 __global__ void __launch_bounds__(256) k_act_split3(const float* __restrict__ x, const float* __restrict__ mean,
                                                     const float* __restrict__ rstd, float slope, float* __restrict__ y, long ystride,
                                                     uint4* __restrict__ out, long S, int cblocks, int oblocks, int ob0) {
@@ -479,7 +479,6 @@ bool s_shape_ok(const ConvDims& d, int Cin, int Kout) {
 size_t s_packed_bytes(int Cin, int Kout, int KS) {
   return (size_t)(Kout / 64) * (Cin / 8) * KS * ((KS * KS + 1) / 2) * kPairPieces * 1024;
 }
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <int KS, int VB>
 int launch_s3(const SParams& p, int lds, hipStream_t s) {

@@ -430,7 +430,6 @@ __global__ void k_chan_sum_final(const double* __restrict__ part, int N, int C, 
   out[c] = (float)a;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 int wgrad_splits(int C, int K) {
   int s = 2048 / ((C / 32) * (K / 32));
   return s < 1 ? 1 : s;
@@ -514,9 +513,8 @@ int convT_wgrad_h(const void* x, const void* dy, int dctot, int dc0, float* dw, 
   p.x = (const unsigned short*)x; p.dy = (const unsigned short*)dy; p.part = part;
   p.N = N; p.C = C; p.K = K; p.Dc = D; p.Hc = H; p.Wc = W; p.dctot8 = dctot / 8; p.dc08 = dc0 / 8; p.splits = splits;
   p.Sc = (long)D * H * W;
-  static const bool shared_dy = true;  // A/B switch
   const int NW = C / 32;
-  if (shared_dy && (NW == 1 || NW == 2 || NW == 4 || NW == 8)) {
+  if (NW == 1 || NW == 2 || NW == 4 || NW == 8) {
     static const int vs = 1;  // (2 = 32 voxels per barrier: measured 40 % slower)
     if (vs == 2) {
       const size_t lds = (size_t)(NW * 4 * 36 + 2 * 8 * 4 * 36) * 16;

@@ -13,14 +13,11 @@
 
 
 #include "common.hpp"
+#include "unet_desc.hpp"
 
 using namespace nc;
 
-#define NC_TRY(expr) do { int e_ = (expr); if (e_) return e_; } while (0)
-
 namespace {
-
-size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 // Which S3 (three-term) copies of convolution inputs a training forward left in its `saved` buffer is a bit mask (bit i = layer i) that
 // the forward RETURNS to the caller (`kept`, a host word) and the caller hands to the backward of the same `saved` buffer: the
@@ -28,7 +25,6 @@ size_t up64(size_t n) { return (n + 63) & ~(size_t)63; }
 // gives that tensor to the weight gradient instead of converting x again.  The decision (library switch, shape coverage) is host
 // state, so the mask is host data; it travels with the autograd context that owns `saved`, not with a table keyed by its address.
 size_t s3_floats(size_t elems) { return up64((elems * 6 + 3) / 4); }
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- Unet_deconv ---------------------------------------------------------------------------------------------------
 // The LEAN forms of the two-term training step (nc_set_unet_lean, default on): fp32 tensors that only a fallback path reads are not written.
@@ -46,10 +42,6 @@ int lean_index(int consumer) {
   for (int j = 0; j < 5; ++j) if (kLeanBlocks[j] == consumer) return j;
   return -1;
 }
-
-struct UBlock { int C, K, lvl; };  // 3^3 conv + InstanceNorm + ReLU; lvl 0 = full resolution, 1 = half, 2 = quarter
-const UBlock kUB[10] = {{1, 64, 0},    {64, 64, 0},    {64, 128, 1},  {128, 128, 1}, {128, 256, 2},
-                        {256, 256, 2}, {256, 256, 2}, {256, 128, 1}, {128, 128, 1}, {128, 64, 0}};
 
 // PREPARED WEIGHTS of the two-term training step (nc_set_unet_wprep, default on; w_prep.hip): the forward computes the weight cells and the packed
 // weights of blocks 1 .. 9, forward AND data-gradient form, in one batched pass at its start and keeps them in `saved` (UPlan::wprep); every
@@ -89,13 +81,10 @@ struct UPlan {
 };
 
 bool u_plan(UPlan& p, int N, int S0, int S1, int S2) {
-  if (N < 1 || S0 < 4 || S1 < 4 || S2 < 4 || (S0 & 3) || (S1 & 3) || (S2 & 3)) return false;
+  if (N < 1 || !u_edges_ok(S0, S1, S2)) return false;
   p = UPlan{};
   p.N = N;
-  for (int l = 0; l < 3; ++l) {
-    p.d[l][0] = S0 >> l; p.d[l][1] = S1 >> l; p.d[l][2] = S2 >> l;
-    p.S[l] = (long)p.d[l][0] * p.d[l][1] * p.d[l][2];
-  }
+  u_level_dims(S0, S1, S2, p.d, p.S);
   const size_t n = (size_t)N, S = (size_t)p.S[0], Sh = (size_t)p.S[1], Sq = (size_t)p.S[2];
   size_t off = 0;
   auto take = [&](size_t k) { size_t r = off; off += up64(k); return r; };
@@ -139,25 +128,6 @@ bool u_plan(UPlan& p, int N, int S0, int S1, int S2) {
   const size_t c2 = nc_convT_ws_bytes(N, 128, p.d[1][0], p.d[1][1], p.d[1][2], 64);
   if (c2 > p.convT_ws) p.convT_ws = c2;
   return true;
-}
-
-// offsets (floats) of the 28 tensors inside the packed blob, state-dict order:
-// dc1.0 dc1.3 dc2.0 dc2.3 bot.0 bot.3 bot.6 t_conv2 ex2.0 ex2.3 t_conv1 ex1.0 1x1 1x1_2
-struct UOff { size_t w[14], b[14], total; };  // ids 0..9 = blocks, 10 = t_conv2, 11 = t_conv1, 12 = one_by_one, 13 = one_by_one_2
-UOff u_offsets() {
-  struct L { int id; size_t wn, bn; };
-  const L order[14] = {{0, 64 * 1 * 27, 64},     {1, 64 * 64 * 27, 64},    {2, 128 * 64 * 27, 128},  {3, 128 * 128 * 27, 128},
-                       {4, 256 * 128 * 27, 256}, {5, 256 * 256 * 27, 256}, {6, 256 * 256 * 27, 256}, {10, 256 * 128 * 8, 128},
-                       {7, 128 * 256 * 27, 128}, {8, 128 * 128 * 27, 128}, {11, 128 * 64 * 8, 64},   {9, 64 * 128 * 27, 64},
-                       {12, 64, 1},              {13, 1, 1}};
-  UOff o{};
-  size_t off = 0;
-  for (const L& l : order) {
-    o.w[l.id] = off; off += l.wn;
-    o.b[l.id] = off; off += l.bn;
-  }
-  o.total = off;
-  return o;
 }
 
 // dst[n][0..C) <- src[n][c0..c0+C) of a [N][Ctot][S] tensor (dense result); N == 1 needs no copy

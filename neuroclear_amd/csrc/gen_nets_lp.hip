@@ -15,6 +15,7 @@
 // (one output channel => rank 1).  The tail is evaluated in that form (k_lin_tail_*): no 32- / 16-channel tensors exist.
 
 #include "common.hpp"
+#include "unet_desc.hpp"
 
 namespace nc {
 // c8_ops.hip
@@ -38,32 +39,7 @@ int convT_wgrad_h(const void* x, const void* dy, int dctot, int dc0, float* dw, 
 
 using namespace nc;
 
-#define NC_TRY(expr) do { int e_ = (expr); if (e_) return e_; } while (0)
-
 namespace {
-
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct UBlock { int C, K, lvl; };
-const UBlock kUB[10] = {{1, 64, 0},    {64, 64, 0},    {64, 128, 1},  {128, 128, 1}, {128, 256, 2},
-                        {256, 256, 2}, {256, 256, 2}, {256, 128, 1}, {128, 128, 1}, {128, 64, 0}};
-
-struct UOff { size_t w[14], b[14], total; };
-UOff u_offsets() {
-  struct L { int id; size_t wn, bn; };
-  const L order[14] = {{0, 64 * 1 * 27, 64},     {1, 64 * 64 * 27, 64},    {2, 128 * 64 * 27, 128},  {3, 128 * 128 * 27, 128},
-                       {4, 256 * 128 * 27, 256}, {5, 256 * 256 * 27, 256}, {6, 256 * 256 * 27, 256}, {10, 256 * 128 * 8, 128},
-                       {7, 128 * 256 * 27, 128}, {8, 128 * 128 * 27, 128}, {11, 128 * 64 * 8, 64},   {9, 64 * 128 * 27, 64},
-                       {12, 64, 1},              {13, 1, 1}};
-  UOff o{};
-  size_t off = 0;
-  for (const L& l : order) {
-    o.w[l.id] = off; off += l.wn;
-    o.b[l.id] = off; off += l.bn;
-  }
-  o.total = off;
-  return o;
-}
 
 // byte offsets into `saved` / the backward scratch
 struct ULp {
@@ -77,15 +53,12 @@ struct ULp {
 
 bool ulp_plan(ULp& p, int N, int S0, int S1, int S2) {
   p = ULp{};
-  if (N < 1 || S0 < 4 || S1 < 4 || S2 < 4 || (S0 & 3) || (S1 & 3) || (S2 & 3)) return false;
+  if (N < 1 || !u_edges_ok(S0, S1, S2)) return false;
   p.N = N;
-  for (int l = 0; l < 3; ++l) {
-    p.d[l][0] = S0 >> l; p.d[l][1] = S1 >> l; p.d[l][2] = S2 >> l;
-    p.S[l] = (long)p.d[l][0] * p.d[l][1] * p.d[l][2];
-  }
+  u_level_dims(S0, S1, S2, p.d, p.S);
   const size_t n = (size_t)N, S = (size_t)p.S[0], Sh = (size_t)p.S[1], Sq = (size_t)p.S[2];
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes); return r; };
+  auto take = [&](size_t bytes) { size_t r = off; off += align256(bytes); return r; };
   p.c1 = c1_h_supported(S0, S1, S2, 3);
   p.raw0 = take(n * 64 * S * (p.c1 ? 2 : 4));
   p.a1 = take(n * 64 * S * 2); p.cat1 = take(n * 128 * S * 2); p.p1 = take(n * 64 * Sh * 2); p.a2 = take(n * 128 * Sh * 2);
@@ -127,7 +100,7 @@ bool ulp_plan(ULp& p, int N, int S0, int S1, int S2) {
 }
 
 size_t ulp_ws_bytes(const ULp& p, bool bwd) {
-  return al(p.conv_ws) + al(p.f32conv_ws) + al(p.in_ws) + al(p.c8_ws) + al(p.convT_ws) + al(p.o64_ws) + al(p.c1_ws) +
+  return align256(p.conv_ws) + align256(p.f32conv_ws) + align256(p.in_ws) + align256(p.c8_ws) + align256(p.convT_ws) + align256(p.o64_ws) + align256(p.c1_ws) +
          (bwd ? p.grads : 0) + 256;
 }
 
@@ -135,13 +108,13 @@ struct UWs { void *cws, *fws, *iws, *c8ws, *tws, *ows, *c1ws; char* G; };
 UWs ulp_ws(const ULp& p, void* ws) {
   UWs u;
   char* b = (char*)ws;
-  u.cws = b; b += al(p.conv_ws);
-  u.fws = b; b += al(p.f32conv_ws);
-  u.iws = b; b += al(p.in_ws);
-  u.c8ws = b; b += al(p.c8_ws);
-  u.tws = b; b += al(p.convT_ws);
-  u.ows = b; b += al(p.o64_ws);
-  u.c1ws = b; b += al(p.c1_ws);
+  u.cws = b; b += align256(p.conv_ws);
+  u.fws = b; b += align256(p.f32conv_ws);
+  u.iws = b; b += align256(p.in_ws);
+  u.c8ws = b; b += align256(p.c8_ws);
+  u.tws = b; b += align256(p.convT_ws);
+  u.ows = b; b += align256(p.o64_ws);
+  u.c1ws = b; b += align256(p.c1_ws);
   u.G = b;
   return u;
 }
@@ -405,7 +378,7 @@ bool llp_plan(LLp& p, int N, int S0, int S1, int S2) {
   for (int i = 0; i < 6; ++i) { p.w[i] = off; off += (size_t)K[i] * C[i] * ks[i] * ks[i] * ks[i]; }
   const size_t n = (size_t)N, S = (size_t)p.S;
   off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off += al(bytes); return r; };
+  auto take = [&](size_t bytes) { size_t r = off; off += align256(bytes); return r; };
   p.f1h = take(n * 64 * S * 2); p.f2h = take(n * 64 * S * 2); p.f3h = take(n * 64 * S * 2); p.weff = take(64 * 4); p.u1 = take(32 * 4);
   p.saved = off;
   off = 0;
@@ -437,7 +410,7 @@ bool llp_rank_ok(const LLp& p, ConvDims& dsh) {
          c8x_wgrad_part_bytes(dsh) <= p.conv_ws && h_fwd_supported(dsh) && h_ws_bytes(dsh) <= p.conv_ws;
 }
 
-size_t llp_ws_bytes(const LLp& p) { return al(p.conv_ws) + al(p.f32conv_ws) + al(p.o64_ws) + al(p.c1_ws) + p.grads + 256; }
+size_t llp_ws_bytes(const LLp& p) { return align256(p.conv_ws) + align256(p.f32conv_ws) + align256(p.o64_ws) + align256(p.c1_ws) + p.grads + 256; }
 
 }  // namespace
 
@@ -472,9 +445,9 @@ int nc_deep_linear_lp_fwd(const float* params, const float* x, float* y, void* s
   const WeightDiffusion wd_;  // the bias-free, norm-free stack rounds its weights tap-diffused (conv_h.hip)
   hipStream_t hs = (hipStream_t)stream;
   char* cws = (char*)ws;
-  char* fws = cws + al(p.conv_ws);
-  char* c1ws = fws + al(p.f32conv_ws) + al(p.o64_ws);
-  char* G = c1ws + al(p.c1_ws);
+  char* fws = cws + align256(p.conv_ws);
+  char* c1ws = fws + align256(p.f32conv_ws) + align256(p.o64_ws);
+  char* G = c1ws + align256(p.c1_ws);
   char* V = (char*)saved;
   float* Ff = (float*)(G + p.F);
   if (p.c1) {
@@ -528,10 +501,10 @@ int nc_deep_linear_lp_bwd(const float* params, const float* x, const void* saved
   const WeightDiffusion wd_;  // the bias-free, norm-free stack rounds its weights tap-diffused (conv_h.hip)
   hipStream_t hs = (hipStream_t)stream;
   char* cws = (char*)ws;
-  char* fws = cws + al(p.conv_ws);
-  char* ows = fws + al(p.f32conv_ws);
-  char* c1ws = ows + al(p.o64_ws);
-  char* G = c1ws + al(p.c1_ws);
+  char* fws = cws + align256(p.conv_ws);
+  char* ows = fws + align256(p.f32conv_ws);
+  char* c1ws = ows + align256(p.o64_ws);
+  char* G = c1ws + align256(p.c1_ws);
   const char* V = (const char*)saved;
   float* q = (float*)(G + p.q);
   ConvDims c5, c3;

@@ -15,14 +15,6 @@
 
 using namespace nc;
 
-namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-}  // namespace
-
-#define NC_TRY(expr) do { int e_ = (expr); if (e_) return e_; } while (0)
-
 extern "C" {
 
 size_t nc_patchgan_param_floats(int n_layers, int ndf, int nd) {

@@ -365,8 +365,7 @@ __global__ __launch_bounds__(256) void k_in_bwd_rows(const float* __restrict__ d
 }
 
 static inline bool rows_path(long S) {
-  static const bool on = true;  // A/B switch (timing experiments)
-  return on && S <= kRowsMaxS;
+  return S <= kRowsMaxS;
 }
 
 template <int MODE>

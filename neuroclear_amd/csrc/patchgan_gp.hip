@@ -223,8 +223,6 @@ int plane_launch(K k64, K k256, long planes, long S, hipStream_t s, const char* 
 
 using namespace nc;
 
-#define NC_TRY(expr) do { int e_ = (expr); if (e_) return e_; } while (0)
-
 extern "C" {
 
 size_t nc_patchgan_gp_saved_floats(int B, int D, int H, int W, int n_layers, int ndf, int nd) {

@@ -78,7 +78,7 @@ int set(Id id, int v);  // applies the row's clamp, returns the previous (raw) v
 
 // RAII: the frozen switches as THIS call sees them (NetworkScope opens one; the per-layer entry points with more than one phase open their own)
 struct SwitchScope { SwitchScope(); ~SwitchScope(); };
-// RAII mark of a whole-network call (gen_nets.hip, api.hip): inside one, guard mode 1 COUNTS a flagged measured tensor instead of launching the
+// RAII mark of a whole-network call (gen_nets.hip, unet_fwd.hip): inside one, guard mode 1 COUNTS a flagged measured tensor instead of launching the
 // three-term kernels beside the two-term ones (h2_guard_can_flip) -- ~65 near-empty launches per training step otherwise
 struct NetworkScope { NetworkScope(); ~NetworkScope(); };
 // RAII: this thread sees nc_set_split_terms(2) while it lives (kernels that exist in the two-term form only and convert their fp32 operands

@@ -41,7 +41,6 @@ constexpr int kNU = 4;     // units (tap, 16-channel block) per wave: 16 taps x 
 
 __device__ __forceinline__ unsigned fdiv(unsigned n, unsigned m) { return __umulhi(n, m); }
 unsigned magic(unsigned d) { return (unsigned)(((1ull << 32) + d - 1) / d); }
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct QParams {
   const uint4* xs;   // S3 of the padded input  [C/8][3][TOTx], unit (b * PPx + yp * Wp + xp); planes b >= B are zeros
