@@ -459,10 +459,19 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
  *   2  (default, round 6) layers 1 .. 5 as ONE position-typed 7^3 convolution 64 -> 1 of act0 (csrc/dl_typed.hip): the zero padding of
  *      act1 only matters ON the faces, where it removes the taps of the 3^3 kernel that point outside -- 27 composed kernels, one per position
  *      type; the interior one runs everywhere on the two-term matrix kernels, the voxels on a face are recomputed / corrected with their own.  The
- *      5^3 convolution is not executed at all.  Where the shape does not admit it (an extent below 8, W % 4 != 0, nc_set_split_terms(3)): as 1.
+ *      5^3 convolution is not executed at all.  Where the shape does not admit it (an extent below 8, H above 192, W % 4 != 0, W below 16
+ *      or above 176 -- the one-channel 7^3 weight gradient kernel's range --, nc_set_split_terms(3)): as 1.
  * Exact algebra in every level (weight-space products in fp64; tests/test_collapse_algebra.py in fp64 against autograd), the same outputs and
  * gradients to fp32 rounding, each level closer to an fp64 evaluation than the one before.  nc_deep_linear_lp_* follows the switch as 0 / non-zero.
- * Both pairs carry the forward's choice in `kept`, so the switch may move between a forward and its backward. */
+ * Both pairs carry the forward's choice in `kept`, so the switch may move between a forward and its backward.
+ * nc_deep_linear_fwd's `kept`: bits 0 .. 5 and 16 .. 21 as above (the kept copy of layer i's input and its form); the three top bits say which of
+ * the forms ran (csrc/gen_nets.hip: kKeptCollapsed, kKeptNoAct1, kKeptTyped; tests read them to assert the form):
+ *   bit 31  a collapsed form: act2 .. act4 were not written, the backward takes layers 2 .. 5 from dy, act1 and the weights (level 1 or 2);
+ *   bit 30  ... and act1 was not written either ("the forward without act1", or the typed form);
+ *   bit 29  ... because layers 1 .. 5 ran as the ONE position-typed 7^3 kernel of level 2: `saved` holds act0 alone.  Set only by a training
+ *           forward (saved != NULL) under level 2 in the two-term arithmetic at a shape every kernel of the form admits; the inference form
+ *           (saved == NULL) never takes it: under levels 1 and 2 it runs layers 2 .. 5 as the one 64 -> 1 convolution (bit 31 alone).
+ * All three clear: the layered evaluation.  Bit 30 implies bit 31, bit 29 implies both. */
 void nc_set_dl_collapse(int on);
 int nc_get_dl_collapse(void);
 int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, const float* dy, float* dx, float* dparams,

@@ -629,6 +629,10 @@ def test_deep_linear_collapsed_tail_equals_the_layered_chain(shape, want_dx, ter
             p.grad = None
         x = x0.clone().requires_grad_(want_dx)
         y = net(x)
+        # which form ran: the forward's own word (include/nc_hip.h, nc_deep_linear_fwd: bit 29 = layers 1 .. 5 as one position-typed kernel).  Set
+        # under mode 2 in the two-term arithmetic for the shapes csrc/dl_typed.hip's dl_typed_supported admits, clear everywhere else
+        typed = bool(y.grad_fn.kept & (1 << 29))
+        assert typed == (collapse == 2 and terms == 2 and shape != (2, 1, 9, 14, 21)), (collapse, terms, shape, hex(y.grad_fn.kept))
         (y * r).sum().backward()
         with torch.no_grad():
             yi = net(x0)  # the inference form (saved == NULL)
