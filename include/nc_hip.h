@@ -398,7 +398,18 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
 /* The lean forms of the two-term training step (default on; NC_UNET_LEAN=0 at load time): the forward does not write fp32 activations whose only
  * regular reader is a two-term convolution that has its own H2 copy, and the backward (one sample) never expands the rank-one data gradient
  * behind one_by_one -- block 9's InstanceNorm backward forms w12[c] * s2[v] itself.  Outputs and gradients are bit for bit what the full forms
- * give.  With nc_set_split_terms(3) or the split kernels off: no effect. */
+ * give.  With nc_set_split_terms(3) or the split kernels off: no effect.
+ * Three more full-resolution fp32 tensors stay unwritten, each recorded in `kept` (the backward decides from the bits, not from the switch):
+ *   bit 27       e1, block 9's output: one_by_one's forward and weight gradient take raw / mean / rstd and normalise the operand as they read it
+ *                -- only where the two flat 1 x 1 kernels take the layer (>= 16384 voxels, nc_set_force_direct off); else e1 is written.
+ *   bits 28, 29  the fp32 upper half of cat1 / cat2: the transposed convolution writes the H2 half of block 9 / 7's operand alone.
+ *   bits 30, 31  TOGETHER WITH bit 26, the fp32 lower half of cat1 / cat2: blocks 1 / 3 write the H2 half, the fp32 POOLED tensor and the pool's
+ *                winner bytes in one pass and the max-pool is not launched -- only when the forward writes winner bytes (nc_set_in_bwd_fold on
+ *                at that call: bit 26, the one bit that switch moves; bits 30 / 31 say that the block is in the form otherwise).
+ * A backward that reads one of them after all (block 9 / 7 without the kept H2 copy or with nc_set_h2_guard(2), a pool backward outside the norm
+ * backward, one_by_one off the flat kernels) first writes it again with the bits the full forward stores: the concat halves into their own
+ * slots of `saved` (which the backward therefore WRITES in these cases), e1 into its workspace.  The layout of `saved`,
+ * nc_unet_deconv_saved_floats and the workspace sizes are unchanged. */
 void nc_set_unet_lean(int on);
 int nc_get_unet_lean(void);
 /* Prepared weights of the two-term training step (default on; NC_UNET_WPREP=0 at load time; process-wide, sampled once per call):
@@ -690,6 +701,17 @@ int nc_instnorm_act_bwd_dbias_h2_pool_debug(const float* dy, long dy_stride, con
                                             const float* rstd, float slope, void* dxs, float* dbias, int N, int C, int D, int H, int W, void* ws,
                                             size_t ws_bytes, unsigned* guard, void* stream);
 int nc_maxpool2_fwd_arg_debug(const float* x, float* y, unsigned char* arg, int NC, int D, int H, int W, void* stream);
+/* Test exports of the lean training forms (tests/test_gpu_unet_lean2.py).  nc_act_split2h_pool_arg_debug: act_split2h_pool_arg -- act_split2h's
+ * H2 part and, of the same activations, MaxPool3d(2) as fp32 into `pooled` with the winner bytes into `arg` (both dense [N][C][D/2 H/2 W/2]); no
+ * fp32 activation.  nc_conv_fwd_norm_1x1_debug / nc_conv_wgrad_norm_1x1_debug: nc_conv_fwd / nc_conv_wgrad (dbias nullable) of a 1 x 1 layer
+ * whose input is InstanceNorm + (Leaky)ReLU of `raw` (mean, rstd: [N][C]), normalised inside the kernel; NC_ERR_SHAPE where the two flat 1 x 1
+ * kernels do not take the layer (C % 16, fewer than 16384 voxels, nc_set_force_direct). */
+int nc_act_split2h_pool_arg_debug(const float* x, const float* mean, const float* rstd, float slope, void* ys, float* pooled, unsigned char* arg, int N,
+                                  int C, int D, int H, int W, int ctot, int c0, float bound, unsigned* cell, void* stream);
+int nc_conv_fwd_norm_1x1_debug(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* bias, float* y, int N,
+                               int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
+int nc_conv_wgrad_norm_1x1_debug(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, float* dbias, int N,
+                                 int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
 size_t nc_convT_k2s2_split_h2_ws_bytes(int N, int C, int D, int H, int W, int K);
 int nc_convT_k2s2_fwd_split_h2_debug(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C,
                                      int D, int H, int W, int K, unsigned* out_cell, void* ws, size_t ws_bytes, void* stream);

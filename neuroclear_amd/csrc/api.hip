@@ -532,6 +532,34 @@ bool conv_fwd_on_split(int N, int C, int D, int H, int W, int K, int ks) {
   return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && fwd_path(d) == 9;
 }
 
+// The 1 x 1 layer behind an InstanceNorm + (Leaky)ReLU without the stored activation (conv_1x1.hip, the NORM forms): taken only where nc_conv_fwd
+// AND nc_conv_wgrad would put the layer on the two flat kernels now, whose products and order the forms keep.
+bool norm_1x1_taken(int N, int C, int D, int H, int W, int K) {
+  ConvDims d;
+  return make_dims(d, N, C, D, H, W, K, 1, 1, 1, 1, 0) && fwd_path(d) == 3 && wgrad_path(d) == 3 && norm_1x1_supported(d);
+}
+int conv_fwd_norm_1x1(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* bias, float* y, int N, int C,
+                      int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream) {
+  ConvDims d;
+  if (int e = conv_args("conv_fwd_norm_1x1", d, raw, w, y, N, C, D, H, W, K, 1, 1, 1, 1, 0)) return e;
+  if (!mean || !rstd) { set_error("conv_fwd_norm_1x1: null pointer"); return NC_ERR_ARG; }
+  ProfScope ps(0, 3, d, 0, (hipStream_t)stream);
+  return conv_fwd_1x1_norm(raw, mean, rstd, slope, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream);
+}
+int conv_wgrad_norm_1x1(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, float* dbias, int N, int C,
+                        int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream) {
+  ConvDims d;
+  if (int e = conv_args("conv_wgrad_norm_1x1", d, raw, dy, dw, N, C, D, H, W, K, 1, 1, 1, 1, 0)) return e;
+  if (!mean || !rstd) { set_error("conv_wgrad_norm_1x1: null pointer"); return NC_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(2, 3, d, 0, s);
+    if (int e = conv_wgrad_1x1_norm(raw, mean, rstd, slope, dy, dw, d, ws, ws_bytes, s)) return e;
+  }
+  if (dbias) return bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s);  // (as nc_conv_wgrad)
+  return NC_OK;
+}
+
 // forward of such a layer whose input already exists in S3 form (written by the producer: act_split3 / split3_into)
 int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, int N, int C, int D, int H, int W, int K, int ks, void* ws,
                  size_t ws_bytes, void* stream, float* stats_part, const S3xPrepared* prep) {
@@ -588,3 +616,18 @@ int conv_bwd_keep(const float* x, const void* xs, const float* dy, const float* 
   return nc_conv_bwd(x, dy, w, dx, dw, nullptr, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2, ws, ws_bytes, stream);
 }
 }  // namespace nc
+
+// Test exports of the 1 x 1 layer that normalises its operand as it reads it (conv_1x1.hip, the NORM forms; tests/test_gpu_unet_lean2.py): the
+// calls the U-Net training step issues for one_by_one, refused (NC_ERR_SHAPE) where the step would not take them.
+extern "C" {
+int nc_conv_fwd_norm_1x1_debug(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* bias, float* y, int N,
+                               int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream) {
+  if (!norm_1x1_taken(N, C, D, H, W, K)) { set_error("conv_fwd_norm_1x1_debug: the flat 1 x 1 kernels do not take this layer"); return NC_ERR_SHAPE; }
+  return conv_fwd_norm_1x1(raw, mean, rstd, slope, w, bias, y, N, C, D, H, W, K, ws, ws_bytes, stream);
+}
+int nc_conv_wgrad_norm_1x1_debug(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, float* dbias, int N,
+                                 int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream) {
+  if (!norm_1x1_taken(N, C, D, H, W, K)) { set_error("conv_wgrad_norm_1x1_debug: the flat 1 x 1 kernels do not take this layer"); return NC_ERR_SHAPE; }
+  return conv_wgrad_norm_1x1(raw, mean, rstd, slope, dy, dw, dbias, N, C, D, H, W, K, ws, ws_bytes, stream);
+}
+}  // extern "C"

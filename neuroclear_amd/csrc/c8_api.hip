@@ -220,11 +220,13 @@ int nc_convT_k2s2_fwd_split(const float* x, const void* xs, const float* w, cons
 
 namespace nc {
 // ... in the two-term form, for the training forward (gen_nets.hip): x fp32 (an InstanceNorm + ReLU output: bound sqrt(S)) is converted into
-// the workspace, y (fp32) and ys (channels [c0, c0 + K) of an H2 tensor whose cell `out_cell` the caller set with convT_h2_bound) are written
+// the workspace, y (fp32) and ys (channels [c0, c0 + K) of an H2 tensor whose cell `out_cell` the caller set with convT_h2_bound) are written.
+// Either of y and ys may be NULL: the lean training forward writes ys alone, and a backward that needs the fp32 half after all y alone -- the
+// same kernel on the same operands, so the bits the full forward stores (the switch was the forward's to ask: convT_s3x_shape here).
 int convT_fwd_split_h2(const float* x, const float* w, const float* bias, float* y, void* ys, int ys_ctot, int ys_c0, int N, int C, int D, int H,
                        int W, int K, const unsigned* out_cell, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!x || !w || !ys || !out_cell || !ws) { set_error("convT_fwd_split_h2: null pointer"); return NC_ERR_ARG; }
-  if (!convT_s3x_supported(N, C, D, H, W, K)) { set_error("convT_fwd_split_h2: shape not covered"); return NC_ERR_SHAPE; }
+  if (!x || !w || (!y && !ys) || (ys && !out_cell) || !ws) { set_error("convT_fwd_split_h2: null pointer"); return NC_ERR_ARG; }
+  if (!convT_s3x_shape(N, C, D, H, W, K)) { set_error("convT_fwd_split_h2: shape not covered"); return NC_ERR_SHAPE; }
   const size_t wb = al256(convT_s3x_ws_bytes(C, K));
   const long S = (long)D * H * W;
   const size_t ex = (size_t)N * C * S;

@@ -181,6 +181,20 @@ int conv_fwd_1x1(const float* x, const float* w, const float* b, float* y, const
                  hipStream_t s);
 int conv_dgrad_1x1(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb,
                    hipStream_t s);
+// The same forward and weight gradient of a layer whose input is InstanceNorm + (Leaky)ReLU of `raw`: the kernels normalise the operand as they
+// read it from LDS, so the activation is never stored (C % 16 == 0).  Products and their order are those of the plain kernels on the activation.
+bool norm_1x1_supported(const ConvDims& d);
+int conv_fwd_1x1_norm(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* b, float* y,
+                      const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
+int conv_wgrad_1x1_norm(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, const ConvDims& d,
+                        void* ws, size_t wsb, hipStream_t s);
+// api.hip: the two calls above in the place of nc_conv_fwd / nc_conv_wgrad (profiling scope, bias gradient); norm_1x1_taken: BOTH flat kernels
+// take the layer now (shape, nc_set_force_direct)
+bool norm_1x1_taken(int N, int C, int D, int H, int W, int K);
+int conv_fwd_norm_1x1(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* bias, float* y, int N, int C,
+                      int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
+int conv_wgrad_norm_1x1(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, float* dbias, int N, int C,
+                        int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
 
 // ---- many-channels -> one channel, 7^3 (VALU), conv_c1.hip
 size_t conv_fwd_to1_k3_ws_bytes(int N, int D, int H, int W);
@@ -316,6 +330,21 @@ __device__ __forceinline__ bool guard_skip(const unsigned* guard, int want) {  /
 __device__ bool guard_skip(const unsigned* guard, int want);
 #endif
 #if defined(__HIPCC__)
+// InstanceNorm normalisation + (Leaky)ReLU of one element, ONE definition for k_in_act_fwd (norm_act.hip) and the 1 x 1 kernels that apply it to
+// their operand as they read it (conv_1x1.hip): a negative v at slope 0 gives -0, as the stored activation has it.
+__device__ __forceinline__ float in_act(float x, float m, float r, float slope) {
+  const float v = (x - m) * r;
+  return v > 0.f ? v : v * slope;
+}
+// One step of the scan over a max-pool window, ONE definition for pool_winner (norm_act.hip) and the pass that normalises, converts and pools at
+// once (h2.hip k_act_split2h_pool<true>): an element takes over when it is greater than every one before it, a NaN from anything.  best starts
+// at -INFINITY, idx runs in (z, y, x) order.
+__device__ __forceinline__ void pool_winner_step(float v, int idx, float& best, int& arg) {
+  if (v > best || v != v) {
+    best = v;
+    arg = idx;
+  }
+}
 // The guard's decision (k_h2_guard_decide's comment in h2.hip has the arguments), for ONE thread: shared by that kernel and by the launch of the
 // norm backward that takes the decision beside its bias sums (norm_act.hip k_in_dbias_final_decide)
 __device__ __forceinline__ void h2_guard_decide_one(unsigned* ga, unsigned* gb, unsigned* prior, unsigned* flag, int can_flip,
@@ -351,6 +380,10 @@ int act_split2h(const float* x, const float* mean, const float* rstd, float slop
                 int c0, float bound, unsigned* cell, unsigned* cell2, hipStream_t s);
 int act_split2h_pool(const float* x, const float* mean, const float* rstd, float slope, void* ys, void* pooled, int N, int C, int D, int H, int W,
                      int ctot, int c0, float bound, unsigned* cell, hipStream_t s);
+// the TRAINING form: the pooled tensor is fp32 (dense [N][C][D/2 H/2 W/2], the values nc_maxpool2_fwd gives on the fp32 activation) and `arg`
+// receives maxpool2_fwd_arg's winner bytes; no full-resolution fp32 tensor is written
+int act_split2h_pool_arg(const float* x, const float* mean, const float* rstd, float slope, void* ys, float* pooled, unsigned char* arg, int N, int C,
+                         int D, int H, int W, int ctot, int c0, float bound, unsigned* cell, hipStream_t s);
 int conv_s3x(const void* xs, const float* w, const float* bias, float* y, int N, int Cin, int D, int H, int W, int Kout, int KS, long so,
              long si, int flip, void* wp_ws, hipStream_t s, const unsigned* guard = nullptr);
 bool conv_keep_supported(int N, int C, int D, int H, int W, int K, int ks);
@@ -382,6 +415,7 @@ bool c8x_supported(int N, int Cin, int D, int H, int W, int Kout, int KS, bool f
 int conv_c8x(const void* xh, const float* w, const float* bias, float* y, void* yh, int ctot, int c0, int N, int Cin, int D, int H, int W,
              int Kout, int KS, long so, long si, int flip, int diffuse, int dt, void* wp_ws, hipStream_t s);
 bool convT_s3x_supported(int N, int C, int D, int H, int W, int K);
+bool convT_s3x_shape(int N, int C, int D, int H, int W, int K);  // ... the shape alone, without the A/B switch
 size_t convT_s3x_ws_bytes(int C, int K);
 int convT_fwd_s3x(const void* xs, const float* w, const float* bias, float* y, void* ys, int ctot, int c0, int N, int C, int D, int H, int W,
                   int K, void* ws, size_t wsb, hipStream_t s, const unsigned* h2cell = nullptr, const unsigned* xcell = nullptr);

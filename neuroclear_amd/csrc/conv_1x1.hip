@@ -34,8 +34,16 @@ struct W1Params {
   int npd, npx;        // 256-float pieces of the dY / X region of one buffer
   long nchunks;        // N * ceil(S / 128)
   long cps;            // chunks per sample
+  const float* mean;   // NORM: X = InstanceNorm + (Leaky)ReLU of x, statistics [N][C]
+  const float* rstd;
+  float slope;
 };
 
+// NORM: x is the RAW tensor in front of an InstanceNorm + (Leaky)ReLU and the X operand is normalised as it leaves LDS (in_act, the stored
+// activation's bits): a lane's X rows are fixed -- channel nb * 16 + l15 of its two blocks -- so their statistics sit in registers per sample.
+// Zero-page columns (voxels past the end of the volume) become in_act(0) instead of 0; the dY columns they meet are zero-page zeros, the
+// statistics are finite, so the products are +-0 as before.  C % 16 == 0 (no zero-page X rows).
+template <bool NORM>
 __global__ __launch_bounds__(512) void k_wgrad_1x1(W1Params p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -78,15 +86,18 @@ __global__ __launch_bounds__(512) void k_wgrad_1x1(W1Params p) {
   };
 
   f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  int aoff[2], boff[2];
+  int aoff[2], boff[2], xch[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int b = wave + 8 * t;
     const int mb = b < nblk ? b / NB : 0, nb = b < nblk ? b % NB : 0;
     aoff[t] = (mb * 16 + l15) * kPitch + 4 * kq;
     boff[t] = p.npd * 256 + (nb * 16 + l15) * kPitch + 4 * kq;
+    xch[t] = nb * 16 + l15;
   }
 
+  float xm[2] = {0.f, 0.f}, xr[2] = {0.f, 0.f};
+  long ncur = -1;
   if (c0 < c1) issue(c0, lds);
   for (long c = c0; c < c1; ++c) {
     const int par = (int)((c - c0) & 1);
@@ -94,13 +105,22 @@ __global__ __launch_bounds__(512) void k_wgrad_1x1(W1Params p) {
     __syncthreads();  // the chunk has landed for every wave, and the previous chunk's MFMAs are done
     if (c + 1 < c1) issue(c + 1, lds + (par ^ 1) * bufsz);
     const float* buf = lds + par * bufsz;
+    if (NORM && c / p.cps != ncur) {  // (a new sample: its statistics)
+      ncur = c / p.cps;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) { xm[t] = p.mean[ncur * p.C + xch[t]]; xr[t] = p.rstd[ncur * p.C + xch[t]]; }
+    }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (wave + 8 * t < nblk) {
 #pragma unroll
         for (int q = 0; q < kVC; q += 16) {
           const f32x4 a = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(buf + aoff[t] + q, 16));
-          const f32x4 b = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(buf + boff[t] + q, 16));
+          f32x4 b = *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(buf + boff[t] + q, 16));
+          if (NORM) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) b[m] = in_act(b[m], xm[t], xr[t], p.slope);
+          }
 #pragma unroll
           for (int m = 0; m < 4; ++m) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m], b[m], acc[t], 0, 0, 0);
         }
@@ -155,7 +175,8 @@ size_t wgrad_1x1_ws_bytes(const ConvDims& d) {
   return (size_t)wg1_nwg(d) * Kp * Cp * sizeof(float) + 256;
 }
 
-int conv_wgrad_1x1(const float* x, const float* dy, float* dw, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
+static int launch_wgrad(const float* x, const float* mean, const float* rstd, float slope, const float* dy, float* dw, const ConvDims& d, void* ws,
+                        size_t wsb, hipStream_t s) {
   const size_t need = wgrad_1x1_ws_bytes(d);
   if (!need) {
     set_error("wgrad_1x1: unsupported shape");
@@ -177,12 +198,28 @@ int conv_wgrad_1x1(const float* x, const float* dy, float* dw, const ConvDims& d
   p.nchunks = (long)d.N * p.cps;
   const int nwg = wg1_nwg(d);
   const int lds_bytes = 2 * (p.npd + p.npx) * 256 * (int)sizeof(float);
-  if (int e = raise_dyn_lds(k_wgrad_1x1, 160 * 1024, "wgrad_1x1")) return e;
-  hipLaunchKernelGGL(k_wgrad_1x1, dim3(nwg), dim3(512), lds_bytes, s, p);
+  p.mean = mean; p.rstd = rstd; p.slope = slope;
+  if (mean) {
+    if (int e = raise_dyn_lds(k_wgrad_1x1<true>, 160 * 1024, "wgrad_1x1")) return e;
+    hipLaunchKernelGGL(k_wgrad_1x1<true>, dim3(nwg), dim3(512), lds_bytes, s, p);
+  } else {
+    if (int e = raise_dyn_lds(k_wgrad_1x1<false>, 160 * 1024, "wgrad_1x1")) return e;
+    hipLaunchKernelGGL(k_wgrad_1x1<false>, dim3(nwg), dim3(512), lds_bytes, s, p);
+  }
   if (int e = check_launch("wgrad_1x1")) return e;
   hipLaunchKernelGGL(k_wgrad_1x1_reduce, dim3((d.K * d.C + 3) / 4), dim3(256), 0, s, (const float*)ws, dw, nwg, d.K,
                      d.C, p.Kp, p.Cp);
   return check_launch("wgrad_1x1_reduce");
+}
+
+int conv_wgrad_1x1(const float* x, const float* dy, float* dw, const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
+  return launch_wgrad(x, nullptr, nullptr, 0.f, dy, dw, d, ws, wsb, s);
+}
+bool norm_1x1_supported(const ConvDims& d) { return wgrad_1x1_supported(d) && flat_1x1_supported(d) && d.C % 16 == 0; }
+int conv_wgrad_1x1_norm(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, const ConvDims& d,
+                        void* ws, size_t wsb, hipStream_t s) {
+  if (!mean || !rstd || !norm_1x1_supported(d)) { set_error("wgrad_1x1_norm: unsupported call"); return NC_ERR_SHAPE; }
+  return launch_wgrad(raw, mean, rstd, slope, dy, dw, d, ws, wsb, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -205,8 +242,15 @@ struct F1Params {
   int Rp;       // R rounded up to 4
   int npi;      // 256-float pieces of one input buffer
   long nchunks, cps;
+  const float* mean;  // NORM: the input is InstanceNorm + (Leaky)ReLU of `in`, statistics [N][R]
+  const float* rstd;
+  float slope;
 };
 
+// NORM: `in` is the RAW tensor in front of an InstanceNorm + (Leaky)ReLU and the B operand is normalised as it leaves LDS (in_act, the stored
+// activation's bits): a lane's input row of k-step ks is 4 * ks + kq, so the 16 pairs of statistics sit in registers per sample.  Zero-page
+// columns (voxels past the end of the volume) become in_act(0) instead of 0: those output columns are never stored.  R % 4 == 0.
+template <bool NORM>
 __global__ __launch_bounds__(512) void k_flat_1x1(F1Params p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -254,6 +298,8 @@ __global__ __launch_bounds__(512) void k_flat_1x1(F1Params p) {
   }
   const int nks = p.Rp / 4;
   const int b_off = kq * kPitchF + l15;
+  float xm[16] = {}, xr[16] = {};
+  long ncur = -1;
 
   if (c0 < c1) issue(c0, lds);
   for (long c = c0; c < c1; ++c) {
@@ -263,11 +309,23 @@ __global__ __launch_bounds__(512) void k_flat_1x1(F1Params p) {
     if (c + 1 < c1) issue(c + 1, lds + (par ^ 1) * bufsz);
     const float* buf = lds + par * bufsz + b_off;
     if (mb_on) {
+      if (NORM && c / p.cps != ncur) {  // (a new sample: its statistics)
+        ncur = c / p.cps;
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {
+          xm[ks] = ks < nks ? p.mean[ncur * p.R + 4 * ks + kq] : 0.f;
+          xr[ks] = ks < nks ? p.rstd[ncur * p.R + 4 * ks + kq] : 0.f;
+        }
+      }
       for (int nb = wave % wpm; nb < 8; nb += wpm) {
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks)
-          if (ks < nks) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[ks], buf[4 * ks * kPitchF + nb * 16], acc, 0, 0, 0);
+          if (ks < nks) {
+            float bv = buf[4 * ks * kPitchF + nb * 16];
+            if (NORM) bv = in_act(bv, xm[ks], xr[ks], p.slope);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(aw[ks], bv, acc, 0, 0, 0);
+          }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) ost[(mb * 16 + 4 * kq + rr) * kPitchO + nb * 16 + l15] = acc[rr];
       }
@@ -300,7 +358,8 @@ static bool flat_1x1_shape(const ConvDims& d) {
 bool flat_1x1_supported(const ConvDims& d) { return flat_1x1_shape(d); }
 
 static int launch_flat(const float* in, const float* w, const float* bias, float* out, int M, int R, int sm, int sr,
-                       const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
+                       const ConvDims& d, void* ws, size_t wsb, hipStream_t s, const float* mean = nullptr, const float* rstd = nullptr,
+                       float slope = 0.f) {
   if (!ws || wsb < 256) {
     set_error("flat_1x1: workspace too small");
     return NC_ERR_WS;
@@ -317,14 +376,25 @@ static int launch_flat(const float* in, const float* w, const float* bias, float
   const int nwg = (int)(p.nchunks < 512 ? p.nchunks : 512);
   const int MB = (M + 15) / 16;
   const int lds_bytes = (2 * p.npi * 256 + MB * 16 * kPitchO) * (int)sizeof(float);
-  if (int e = raise_dyn_lds(k_flat_1x1, 160 * 1024, "flat_1x1")) return e;
-  hipLaunchKernelGGL(k_flat_1x1, dim3(nwg), dim3(512), lds_bytes, s, p);
+  p.mean = mean; p.rstd = rstd; p.slope = slope;
+  if (mean) {
+    if (int e = raise_dyn_lds(k_flat_1x1<true>, 160 * 1024, "flat_1x1")) return e;
+    hipLaunchKernelGGL(k_flat_1x1<true>, dim3(nwg), dim3(512), lds_bytes, s, p);
+  } else {
+    if (int e = raise_dyn_lds(k_flat_1x1<false>, 160 * 1024, "flat_1x1")) return e;
+    hipLaunchKernelGGL(k_flat_1x1<false>, dim3(nwg), dim3(512), lds_bytes, s, p);
+  }
   return check_launch("flat_1x1");
 }
 
 int conv_fwd_1x1(const float* x, const float* w, const float* b, float* y, const ConvDims& d, void* ws, size_t wsb,
                  hipStream_t s) {
   return launch_flat(x, w, b, y, d.K, d.C, d.C, 1, d, ws, wsb, s);
+}
+int conv_fwd_1x1_norm(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* b, float* y,
+                      const ConvDims& d, void* ws, size_t wsb, hipStream_t s) {
+  if (!mean || !rstd || !norm_1x1_supported(d)) { set_error("flat_1x1_norm: unsupported call"); return NC_ERR_SHAPE; }
+  return launch_flat(raw, w, b, y, d.K, d.C, d.C, 1, d, ws, wsb, s, mean, rstd, slope);
 }
 int conv_dgrad_1x1(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb,
                    hipStream_t s) {

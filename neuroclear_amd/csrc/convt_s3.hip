@@ -216,12 +216,16 @@ int qn_for(int C) { return (C / 32) * 8 * 3 * 1024 <= 128 * 1024 ? 8 : 4; }
 
 }  // namespace
 
-bool convT_s3x_supported(int N, int C, int D, int H, int W, int K) {
-  const bool on = sw::raw(sw::CONVT_S3X) != 0;  // A/B switch: the fp32 kernels of convt.hip
+// the shapes the kernel covers, whatever the switch says: a training backward that runs a forward of its own call's forward AGAIN (gen_nets.hip, the
+// lean fallbacks) must get the same kernel even if the switch moved in between
+bool convT_s3x_shape(int N, int C, int D, int H, int W, int K) {
   const long S = (long)D * H * W;
-  if (!on || C % 32 || K % 16 || C > 256 || N < 1) return false;
+  if (C % 32 || K % 16 || C > 256 || N < 1) return false;
   if ((C / 32) * qn_for(C) * 3 * 1024 > 128 * 1024) return false;
   return (long)N * K * 8 * S < (1L << 40) && S * 16 * 3 * (C / 8) < (1L << 40);
+}
+bool convT_s3x_supported(int N, int C, int D, int H, int W, int K) {
+  return sw::raw(sw::CONVT_S3X) != 0 && convT_s3x_shape(N, C, D, H, W, K);  // A/B switch: the fp32 kernels of convt.hip
 }
 size_t convT_s3x_ws_bytes(int C, int K) { return (size_t)C * K * 8 * 3 * 2 + 256; }
 
@@ -237,7 +241,7 @@ int convT_h2_bound(const float* w, const float* bias, int C, int K, float in_bou
 int convT_fwd_s3x(const void* xs, const float* w, const float* bias, float* y, void* ys, int ctot, int c0, int N, int C, int D, int H, int W,
                   int K, void* ws, size_t wsb, hipStream_t s, const unsigned* h2cell, const unsigned* xcell) {
   if (!xs || !w || (!y && !ys) || !ws) { set_error("convT_fwd_s3x: null pointer"); return NC_ERR_ARG; }
-  if (!convT_s3x_supported(N, C, D, H, W, K) || ctot % 8 || c0 % 8) { set_error("convT_fwd_s3x: shape not covered"); return NC_ERR_SHAPE; }
+  if (!convT_s3x_shape(N, C, D, H, W, K) || ctot % 8 || c0 % 8) { set_error("convT_fwd_s3x: shape not covered"); return NC_ERR_SHAPE; }
   if (wsb < convT_s3x_ws_bytes(C, K)) { set_error("convT_fwd_s3x: workspace too small"); return NC_ERR_WS; }
   const int QN = qn_for(C);
   const int NT = xcell ? 2 : 3;

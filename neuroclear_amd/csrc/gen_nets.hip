@@ -32,10 +32,25 @@ size_t s3_floats(size_t elems) { return up64((elems * 6 + 3) / 4); }
 //             them; `kept` bit 10 + j records that tensor j of that list was not written.  A backward that cannot use the kept H2 copy (the
 //             terms switch moved, the shape left the split kernels) or whose range guard may switch to the three-term kernels inside the call
 //             (nc_set_h2_guard(2)) first writes the tensor again from raw / mean / rstd into its own scratch.
+//             e1 (block 9's output) is not written when one_by_one runs on the two flat 1 x 1 kernels (conv_1x1.hip): they take raw[9] / mean /
+//             rstd and normalise the operand as they read it, in the forward and in the weight gradient (`kept` bit 27).
+//             The two halves of cat1 and cat2 exist only as the H2 operand of block 9 / 7: the transposed convolutions write no fp32 output
+//             (bits 28, 29), and blocks 1 and 3 normalise, convert and POOL in one pass (h2.hip k_act_split2h_pool<true>) that leaves p1 / p2 and
+//             the winner bytes but no full-resolution fp32 (bits 30, 31 TOGETHER WITH bit 26: only when the forward writes winner bytes,
+//             nc_set_in_bwd_fold -- that switch moves bit 26 alone).
+//             A backward that needs one of these tensors after all -- block 9 / 7 without the kept H2 copy or under a range guard that may
+//             switch, a pool whose backward is not folded into the norm backward, one_by_one off the flat kernels -- writes it again first, with
+//             the bits the full forward stores: the lower half of a concat buffer by nc_instnorm_act_fwd, the upper half by the transposed
+//             convolution's forward with its fp32 output alone (both into the tensor's own slot of `saved`), e1 into scratch.
 //   backward  the gradient at block 9's output is w12[c] * s2[v]: the InstanceNorm backward forms it from the one-channel s2 (norm_act.hip,
 //             the rank-one form) -- no 64-channel data gradient of one_by_one is written or read.
 // Every lean form applies to a block in the two-term form only; with three terms, the split kernels off or NC_S3_TRAIN_FUSE=0 the calls launch
-// what they launched before.
+// what they launched before.  The backward decides from the `kept` bits, not from the switch.
+constexpr unsigned kLeanE1 = 1u << 27;            // e1 was not written
+constexpr unsigned kLeanUp1 = 1u << 28, kLeanUp2 = 1u << 29;  // the fp32 upper half of cat1 / cat2 (the transposed convolution's output) was not written
+// bits 30, 31: block 1 / 3 is in the form that pools in its normalisation pass -- the fp32 lower half of cat1 / cat2 was not written IF the winner
+// bytes exist too (bit 26, the only bit nc_set_in_bwd_fold moves: the pass is taken when the forward writes winner bytes, and only then)
+constexpr unsigned kLeanLo1 = 1u << 30, kLeanLo2 = 1u << 31;
 constexpr int kLeanBit0 = 10;                     // kept bits 10 .. 14
 constexpr int kLeanBlocks[5] = {1, 3, 5, 6, 8};   // the blocks whose fp32 input the lean forward leaves out (a1, a2, b1, b2, e2a)
 int lean_index(int consumer) {
@@ -238,6 +253,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   unsigned* cell7 = h2_cells_of(V + p.xs3[7], (size_t)N * 256 * Sh) + 1;
   unsigned* cell9 = h2_cells_of(V + p.xs3[9], (size_t)N * 128 * S) + 1;
   unsigned kept_mask = 0;
+  const bool pool_arg = sw::get(sw::IN_BWD_FOLD) != 0;  // (the pools also leave their winner bytes, see kKeptPoolArg)
   // the prepared weights (see kKeptWPrep): every two-term block's cells and packs, both forms, before the first convolution
   S3xPrepared prep[18] = {};
   bool bound7 = false, bound9 = false;  // the pass set cell7 / cell9
@@ -276,7 +292,8 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   // conv (3^3, pad 1) -> raw; statistics; normalise + ReLU into `out`, where sample n's K planes start at
   // out + n * out_stride (out_stride = K * S for a dense tensor, Ctot * S for a half of a concat buffer).
   // to >= 0: block `to` consumes this output as channels [0, K) of its `to_ctot`-channel input
-  auto block = [&](int i, const float* in, float* out, size_t out_stride, int to, int to_ctot) -> int {
+  auto block = [&](int i, const float* in, float* out, size_t out_stride, int to, int to_ctot, float* pooled = nullptr,
+                   unsigned char* parg = nullptr) -> int {
     const UBlock& b = kUB[i];
     const int* d = p.d[b.lvl];
     const long S = p.S[b.lvl];
@@ -298,6 +315,13 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     }
     if (epi) NC_TRY(s3x_stats_finalize((const float*)iws, P + o.b[i], N, d[0], d[1], d[2], b.K, 3, 1e-5f, V + p.mean[i], V + p.rstd[i], hs));
     else NC_TRY(nc_instnorm_stats(V + p.raw[i], N * b.K, S, 1e-5f, V + p.mean[i], V + p.rstd[i], iws, p.in_ws, stream));
+    // lean, blocks 1 and 3 (the lower half of a concat input, and a max-pool behind them): the H2 half, the fp32 POOLED tensor and the winner bytes in
+    // one pass -- no full-resolution fp32, and no pool launch (`pooled` / `parg` non-null: the caller's pool)
+    if (to >= 0 && lean && h2l[to] && to_ctot == 2 * b.K && pooled) kept_mask |= i == 1 ? kLeanLo1 : kLeanLo2;
+    if (pool_arg && (kept_mask & (i == 1 ? kLeanLo1 : kLeanLo2)) && pooled) {
+      return act_split2h_pool_arg(V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, V + p.xs3[to], pooled, parg, N, b.K, d[0], d[1], d[2], to_ctot, 0,
+                                  sqrtf((float)S), h2_cells_of(V + p.xs3[to], (size_t)N * to_ctot * S), hs);  // (act_operand's cell and bound)
+    }
     if (to >= 0 && use[to]) {  // fp32 (the backward of the pool / the fallback paths read it) AND the consumer's S3 operand in one pass
       // lean: a tensor whose only regular reader is the two-term block behind it stays unwritten (the backward takes the H2 copy)
       const int lj = lean && h2l[to] && to_ctot == b.K ? lean_index(to) : -1;
@@ -306,6 +330,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
       if (to_ctot == b.K) pre[to] = true;  // (a concat input is complete once its second half has been converted, below)
       return NC_OK;
     }
+    if (to == -2) return NC_OK;  // (the consumer normalises for itself: the lean tail)
     if (out_stride == (size_t)b.K * S || N == 1)
       return nc_instnorm_act_fwd(V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, out, N * b.K, S, stream);
     for (int n = 0; n < N; ++n)
@@ -314,10 +339,9 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     return NC_OK;
   };
   NC_TRY(block(0, x, V + p.a1, (size_t)64 * S, 1, 64));
-  NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128));
-  const bool pool_arg = sw::get(sw::IN_BWD_FOLD) != 0;  // (the pools also leave their winner bytes, see kKeptPoolArg)
+  NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128, V + p.p1, (unsigned char*)(V + p.parg[0])));
   if (pool_arg) kept_mask |= kKeptPoolArg;
-  for (int n = 0; n < N; ++n) {
+  for (int n = 0; n < N && !(pool_arg && (kept_mask & kLeanLo1)); ++n) {
     if (pool_arg)
       NC_TRY(maxpool2_fwd_arg(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, (unsigned char*)(V + p.parg[0]) + (size_t)n * 64 * Sh, 64,
                               d0[0], d0[1], d0[2], hs));
@@ -325,8 +349,8 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
       NC_TRY(nc_maxpool2_fwd(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, 64, d0[0], d0[1], d0[2], stream));
   }
   NC_TRY(block(2, V + p.p1, V + p.a2, (size_t)128 * Sh, 3, 128));
-  NC_TRY(block(3, V + p.a2, V + p.cat2, (size_t)256 * Sh, 7, 256));
-  for (int n = 0; n < N; ++n) {
+  NC_TRY(block(3, V + p.a2, V + p.cat2, (size_t)256 * Sh, 7, 256, V + p.p2, (unsigned char*)(V + p.parg[1])));
+  for (int n = 0; n < N && !(pool_arg && (kept_mask & kLeanLo2)); ++n) {
     if (pool_arg)
       NC_TRY(maxpool2_fwd_arg(V + p.cat2 + (size_t)n * 256 * Sh, V + p.p2 + (size_t)n * 128 * Sq, (unsigned char*)(V + p.parg[1]) + (size_t)n * 128 * Sq,
                               128, d1[0], d1[1], d1[2], hs));
@@ -340,9 +364,12 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     NC_TRY(h2_zero_cells(cell7, 1, hs));
     NC_TRY(convT_h2_bound(P + o.w[10], P + o.b[10], 256, 128, sqrtf((float)Sq), cell7, hs));
   }
+  // lean: the H2 half is all block 7 / 9 read of a transposed convolution's output (ct2h / ct1h: the consumer is two-term) -- no fp32 half
+  if (lean && ct2h) kept_mask |= kLeanUp2;
+  if (lean && ct1h) kept_mask |= kLeanUp1;
   for (int n = 0; n < N; ++n) {  // t_conv2 writes the second half of cat2
     if (ct2h)
-      NC_TRY(convT_fwd_split_h2(V + p.b3 + (size_t)n * 256 * Sq, P + o.w[10], P + o.b[10], V + p.cat2 + ((size_t)n * 256 + 128) * Sh,
+      NC_TRY(convT_fwd_split_h2(V + p.b3 + (size_t)n * 256 * Sq, P + o.w[10], P + o.b[10], lean ? nullptr : V + p.cat2 + ((size_t)n * 256 + 128) * Sh,
                                 (char*)(V + p.xs3[7]) + (size_t)n * 256 * Sh * 4, 256, 128, 1, 256, d2[0], d2[1], d2[2], 128, cell7, cws, p.conv_ws, hs));
     else if (ct2)
       NC_TRY(nc_convT_k2s2_fwd_split(V + p.b3 + (size_t)n * 256 * Sq, nullptr, P + o.w[10], P + o.b[10], V + p.cat2 + ((size_t)n * 256 + 128) * Sh,
@@ -366,7 +393,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   }
   for (int n = 0; n < N; ++n) {  // t_conv1 writes the second half of cat1
     if (ct1h)
-      NC_TRY(convT_fwd_split_h2(V + p.e2b + (size_t)n * 128 * Sh, P + o.w[11], P + o.b[11], V + p.cat1 + ((size_t)n * 128 + 64) * S,
+      NC_TRY(convT_fwd_split_h2(V + p.e2b + (size_t)n * 128 * Sh, P + o.w[11], P + o.b[11], lean ? nullptr : V + p.cat1 + ((size_t)n * 128 + 64) * S,
                                 (char*)(V + p.xs3[9]) + (size_t)n * 128 * S * 4, 128, 64, 1, 128, d1[0], d1[1], d1[2], 64, cell9, cws, p.conv_ws, hs));
     else if (ct1)
       NC_TRY(nc_convT_k2s2_fwd_split(V + p.e2b + (size_t)n * 128 * Sh, nullptr, P + o.w[11], P + o.b[11], V + p.cat1 + ((size_t)n * 128 + 64) * S,
@@ -383,9 +410,16 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     if (!ct_s3 && !ct1h) NC_TRY(operand_into(cd[9], V + p.cat1 + (size_t)64 * S, (long)128 * S, V + p.xs3[9], N, 64, S, 128, 64, hs));
     pre[9] = true;
   }
-  NC_TRY(block(9, V + p.cat1, V + p.e1, (size_t)64 * S, -1, 0));
-  // the 1x1 tail
-  NC_TRY(nc_conv_fwd(V + p.e1, P + o.w[12], P + o.b[12], V + p.t1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  // the 1x1 tail.  lean, one_by_one on the flat kernels: no e1 -- block 9 stops at its statistics and the kernel normalises raw[9] as it reads it
+  if (lean && norm_1x1_taken(N, 64, d0[0], d0[1], d0[2], 1)) {
+    kept_mask |= kLeanE1;
+    NC_TRY(block(9, V + p.cat1, nullptr, (size_t)64 * S, -2, 0));
+    NC_TRY(conv_fwd_norm_1x1(V + p.raw[9], V + p.mean[9], V + p.rstd[9], 0.f, P + o.w[12], P + o.b[12], V + p.t1, N, 64, d0[0], d0[1], d0[2], 1, cws,
+                             p.conv_ws, stream));
+  } else {
+    NC_TRY(block(9, V + p.cat1, V + p.e1, (size_t)64 * S, -1, 0));
+    NC_TRY(nc_conv_fwd(V + p.e1, P + o.w[12], P + o.b[12], V + p.t1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  }
   // one_by_one_2 + sigmoid: y doubles as the buffer of the pre-sigmoid value (the sigmoid kernel is elementwise in place)
   NC_TRY(nc_conv_fwd(V + p.t1, P + o.w[13], P + o.b[13], y, N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
   if (kept) *kept = kept_mask;
@@ -426,6 +460,17 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
       off += s3x_packed_bytes(sg[k].Cin, sg[k].Kout, 3, 2);
     }
   }
+  // Does block i's backward leave its fp32 input alone?  Only with the kept copy in the form of now AND the split weight gradient AND a range guard
+  // that cannot switch inside this call: a flagged call builds its three-term x operand from the fp32 tensor (conv_split.hip run_ws_h2, "the
+  // flagged call").  A tensor the lean forward left out is written again in every other case.
+  auto input_unread = [&](int i, bool want_dx) -> bool {
+    const UBlock& b = kUB[i];
+    const int* d = p.d[b.lvl];
+    ConvDims cdk;
+    const bool now_h2 = make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk);
+    const bool have = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2;
+    return have && !h2_guard_can_flip() && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, want_dx, p.conv_ws);
+  };
   // backward of block i: g = gradient at the block's (post-ReLU) output, dense [N][K][S]; `in` = the block's input.
   // draw <- InstanceNorm/ReLU backward (+ the conv's bias gradient); dW <- wgrad; gin (nullable) <- dgrad
   // pool (block_bwd, blocks 1 and 3 under pool_folds): g is the skip half of the concat gradient (sample stride 2 K Sl), pool the dense pooled
@@ -439,13 +484,10 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
     const void* xs = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2 ? (const void*)(V + p.xs3[i]) : nullptr;
     // the data-gradient pack the forward prepared, under the same test (see kKeptWPrep); nc_set_unet_wprep(0) now: the per-layer launches
     const S3xPrepared* pd = i >= 1 && gin && now_h2 && (kept_mask & kKeptWPrep) && ((kept_mask >> (16 + i)) & 1) && wprep_now ? &prepd[i] : nullptr;
-    // a lean forward did not write this block's fp32 input.  The paths below leave `in` alone only when they have the kept copy AND the split
-    // weight gradient AND the range guard cannot switch inside this call: a flagged call builds its three-term x operand from the fp32 tensor
-    // (conv_split.hip run_ws_h2, "the flagged call").  In every other case the tensor is written again (the block in front's normalisation +
-    // ReLU: the bits the full forward stores) into scratch no block's backward uses.
+    // a lean forward did not write this block's fp32 input.  Unless the paths below leave `in` alone (input_unread) the tensor is written again
+    // (the block in front's normalisation + ReLU: the bits the full forward stores) into scratch no block's backward uses.
     const int lj = lean_index(i);
-    if (lj >= 0 && ((kept_mask >> (kLeanBit0 + lj)) & 1) &&
-        !(xs && !h2_guard_can_flip() && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, gin != nullptr, p.conv_ws))) {
+    if (lj >= 0 && ((kept_mask >> (kLeanBit0 + lj)) & 1) && !input_unread(i, gin != nullptr)) {
       NC_TRY(nc_instnorm_act_fwd(V + p.raw[i - 1], V + p.mean[i - 1], V + p.rstd[i - 1], 0.f, G + p.T, N * b.C, Sl, stream));
       in = G + p.T;
     }
@@ -492,6 +534,26 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
     *out = G + p.T;
     return NC_OK;
   };
+  // The halves of the concat buffers a lean forward left out (kept bits 28 .. 31), where this backward reads them after all: block 9 / 7's weight
+  // gradient without the kept H2 copy (both halves), a pool's backward outside the norm backward (the lower half, its source).  Written into
+  // their own slots of `saved` with the bits the full forward stores -- the lower half is block 1 / 3's normalisation + ReLU, the upper half the
+  // transposed convolution's forward again with its fp32 output alone -- before anything of this call lives in the convolution workspace.
+  {
+    float* Vw = const_cast<float*>(saved);
+    auto rebuild = [&](int lo_blk, size_t cat, int C, long Sl, bool lower, bool upper, const float* tin, int tw, const int* td) -> int {
+      for (int n = 0; n < N && lower; ++n)
+        NC_TRY(nc_instnorm_act_fwd(V + p.raw[lo_blk] + (size_t)n * C * Sl, V + p.mean[lo_blk] + n * C, V + p.rstd[lo_blk] + n * C, 0.f,
+                                   Vw + cat + (size_t)n * 2 * C * Sl, C, Sl, stream));
+      for (int n = 0; n < N && upper; ++n)
+        NC_TRY(convT_fwd_split_h2(tin + (size_t)n * 2 * C * (Sl / 8), P + o.w[tw], P + o.b[tw], Vw + cat + ((size_t)n * 2 + 1) * C * Sl, nullptr, 2 * C, C, 1,
+                                  2 * C, td[0], td[1], td[2], C, nullptr, cws, p.conv_ws, hs));
+      return NC_OK;
+    };
+    const bool in9 = !input_unread(9, true), in7 = !input_unread(7, true);
+    const bool lo1 = (kept_mask & kLeanLo1) && (kept_mask & kKeptPoolArg), lo2 = (kept_mask & kLeanLo2) && (kept_mask & kKeptPoolArg);
+    NC_TRY(rebuild(1, p.cat1, 64, S, lo1 && (in9 || !pool_folds(1)), (kept_mask & kLeanUp1) && in9, V + p.e2b, 11, d1));
+    NC_TRY(rebuild(3, p.cat2, 128, Sh, lo2 && (in7 || !pool_folds(3)), (kept_mask & kLeanUp2) && in7, V + p.b3, 10, d2));
+  }
   // 1x1 tail
   NC_TRY(nc_sigmoid_bwd(dy, y, G + p.s1, (long)N * S, stream));
   NC_TRY(nc_conv_wgrad(V + p.t1, G + p.s1, DP + o.w[13], DP + o.b[13], N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
@@ -503,7 +565,19 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   const bool r1 = sw::raw(sw::UNET_LEAN) != 0 && N == 1 && fuse_bwd &&
                   make_dims(cd9, N, 128, d0[0], d0[1], d0[2], 64, 3, 3, 3, 1, 1) && conv_layer_h2(cd9) &&
                   conv_bwd_pre_supported(N, 128, d0[0], d0[1], d0[2], 64, 3, true, p.conv_ws) && instnorm_bwd_s3_supported(N, 64, S);
-  NC_TRY(nc_conv_wgrad(V + p.e1, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  // a lean forward did not write e1 (kLeanE1): the weight gradient normalises raw[9] as it reads it -- or, off the flat kernels now, takes e1
+  // written again into scratch (block 9's normalisation + ReLU; T is free until block 9's backward)
+  if ((kept_mask & kLeanE1) && norm_1x1_taken(N, 64, d0[0], d0[1], d0[2], 1)) {
+    NC_TRY(conv_wgrad_norm_1x1(V + p.raw[9], V + p.mean[9], V + p.rstd[9], 0.f, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, cws,
+                               p.conv_ws, stream));
+  } else {
+    const float* e1 = V + p.e1;
+    if (kept_mask & kLeanE1) {
+      NC_TRY(nc_instnorm_act_fwd(V + p.raw[9], V + p.mean[9], V + p.rstd[9], 0.f, G + p.T, N * 64, S, stream));
+      e1 = G + p.T;
+    }
+    NC_TRY(nc_conv_wgrad(e1, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
+  }
   if (!r1) {
     NC_TRY(nc_conv_dgrad(G + p.s2, P + o.w[12], G + p.G1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
   }

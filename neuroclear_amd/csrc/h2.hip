@@ -184,9 +184,14 @@ __global__ void __launch_bounds__(256) k_act_split2h(const float* __restrict__ x
 // k_act_split2h and k_maxpool2_h2 (below) in one pass: one thread per (8-channel block, POOLED voxel) normalises its 2 x 2 x 2 voxels, writes their
 // eight H2 units and the unit of the winner (first maximum of a0 + a1 in scan order: k_maxpool2_h2's rule on the same terms) -- the inference
 // forward's pooled blocks no longer read the full-resolution H2 tensor back (0.2 ms of an 11 ms cube).  Even extents; x read as float2.
+// ARG, the TRAINING form (the lean forward of blocks 1 and 3, gen_nets.hip): the pooled tensor is fp32 -- the winner of the fp32 activations by
+// pool_winner's rule, the value k_maxpool2_fwd stores -- into pf, dense [N][C][So], with the winner's index as a byte into parg (k_maxpool2_fwd<true>'s);
+// the full-resolution activation leaves only as H2 units.
+template <bool ARG>
 __global__ void __launch_bounds__(256) k_act_split2h_pool(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                          float slope, uint4* __restrict__ out, uint4* __restrict__ pooled, int D, int H, int W,
-                                                          int cblocks, int oblocks, int ob0, unsigned bound_bits, unsigned* __restrict__ cell) {
+                                                          float slope, uint4* __restrict__ out, uint4* __restrict__ pooled, float* __restrict__ pf,
+                                                          unsigned char* __restrict__ parg, int D, int H, int W, int cblocks, int oblocks, int ob0,
+                                                          unsigned bound_bits, unsigned* __restrict__ cell) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && cell) *cell = bound_bits;
   const int Do = D / 2, Ho = H / 2, Wo = W / 2;
   const long So = (long)Do * Ho * Wo, S = (long)D * H * W;
@@ -202,6 +207,11 @@ __global__ void __launch_bounds__(256) k_act_split2h_pool(const float* __restric
   for (int j = 0; j < 8; ++j) { m[j] = mean[c0 + j]; r[j] = rstd[c0 + j]; }
   float best[8];
   unsigned short w0[8], w1[8];
+  int win[8];
+  if (ARG) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; win[j] = 0; }
+  }
 #pragma unroll
   for (int kp = 0; kp < 4; ++kp) {  // (z, y) of the pair; the pair itself is two consecutive x
     const long u = ((long)(2 * zo + (kp >> 1)) * H + (2 * yo + (kp & 1))) * W + 2 * xo;
@@ -213,6 +223,10 @@ __global__ void __launch_bounds__(256) k_act_split2h_pool(const float* __restric
       t0 = t0 > 0.f ? t0 : t0 * slope;
       t1 = t1 > 0.f ? t1 : t1 * slope;
       asm("" : "+v"(t0), "+v"(t1));  // the scaling must see the ROUNDED activation (as k_act_split2h)
+      if (ARG) {  // (z, y, x) order: the pair's index is kp * 2 + h
+        pool_winner_step(t0, kp * 2, best[j], win[j]);
+        pool_winner_step(t1, kp * 2 + 1, best[j], win[j]);
+      }
       h2_split(t0 * sc, e[0][j]);
       h2_split(t1 * sc, e[1][j]);
     }
@@ -220,6 +234,7 @@ __global__ void __launch_bounds__(256) k_act_split2h_pool(const float* __restric
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) out[(ob * 2 + t) * S + u + h] = s3_unit(e[h], t);
+      if (ARG) continue;
       const int k = (kp >> 1) * 4 + (kp & 1) * 2 + h;  // k_maxpool2_h2's scan order: z, y, x
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -227,6 +242,14 @@ __global__ void __launch_bounds__(256) k_act_split2h_pool(const float* __restric
         if (val > best[j] || k == 0) { best[j] = val; w0[j] = e[h][j][0]; w1[j] = e[h][j][1]; }
       }
     }
+  }
+  if (ARG) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      pf[(c0 + j) * So + v] = best[j];
+      parg[(c0 + j) * So + v] = (unsigned char)win[j];
+    }
+    return;
   }
   uint4 o0, o1;
   o0.x = w0[0] | ((unsigned)w0[1] << 16); o0.y = w0[2] | ((unsigned)w0[3] << 16); o0.z = w0[4] | ((unsigned)w0[5] << 16); o0.w = w0[6] | ((unsigned)w0[7] << 16);
@@ -378,9 +401,26 @@ int act_split2h_pool(const float* x, const float* mean, const float* rstd, float
   unsigned bits;
   __builtin_memcpy(&bits, &bound, 4);
   const long So = (long)(D / 2) * (H / 2) * (W / 2);
-  hipLaunchKernelGGL(k_act_split2h_pool, dim3((unsigned)cdiv(So, 256), (unsigned)(N * C / 8)), dim3(256), 0, s, x, mean, rstd, slope, (uint4*)ys,
-                     (uint4*)pooled, D, H, W, C / 8, ctot / 8, c0 / 8, bits, cell);
+  hipLaunchKernelGGL(k_act_split2h_pool<false>, dim3((unsigned)cdiv(So, 256), (unsigned)(N * C / 8)), dim3(256), 0, s, x, mean, rstd, slope, (uint4*)ys,
+                     (uint4*)pooled, (float*)nullptr, (unsigned char*)nullptr, D, H, W, C / 8, ctot / 8, c0 / 8, bits, cell);
   return check_launch("act_split2h_pool");
+}
+
+// the training form (k_act_split2h_pool<true>): pooled fp32 and the winner bytes, dense [N][C][So]
+int act_split2h_pool_arg(const float* x, const float* mean, const float* rstd, float slope, void* ys, float* pooled, unsigned char* arg, int N, int C,
+                         int D, int H, int W, int ctot, int c0, float bound, unsigned* cell, hipStream_t s) {
+  if (!x || !mean || !rstd || !ys || !pooled || !arg) { set_error("act_split2h_pool_arg: null pointer"); return NC_ERR_ARG; }
+  if (N < 1 || C < 8 || C % 8 || ctot % 8 || c0 % 8 || c0 < 0 || c0 + C > ctot || D < 2 || H < 2 || W < 2 || ((D | H | W) & 1) || (long)N * C / 8 > 65535) {
+    set_error("act_split2h_pool_arg: channels % 8, even extents");
+    return NC_ERR_SHAPE;
+  }
+  if ((((uintptr_t)x) & 7) != 0) { set_error("act_split2h_pool_arg: input not 8-byte aligned"); return NC_ERR_ARG; }
+  unsigned bits;
+  __builtin_memcpy(&bits, &bound, 4);
+  const long So = (long)(D / 2) * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(k_act_split2h_pool<true>, dim3((unsigned)cdiv(So, 256), (unsigned)(N * C / 8)), dim3(256), 0, s, x, mean, rstd, slope, (uint4*)ys,
+                     (uint4*)nullptr, pooled, arg, D, H, W, C / 8, ctot / 8, c0 / 8, bits, cell);
+  return check_launch("act_split2h_pool_arg");
 }
 
 }  // namespace nc

@@ -50,6 +50,13 @@ int nc_act_split2h_pool_debug(const float* x, const float* mean, const float* rs
   return act_split2h_pool(x, mean, rstd, slope, ys, pooled, N, C, D, H, W, ctot, c0, bound, cell, (hipStream_t)stream);
 }
 
+// the training form (h2.hip k_act_split2h_pool<true>): pooled fp32 and the winner bytes; pointers and shape are checked by the internal function
+int nc_act_split2h_pool_arg_debug(const float* x, const float* mean, const float* rstd, float slope, void* ys, float* pooled, unsigned char* arg, int N,
+                                  int C, int D, int H, int W, int ctot, int c0, float bound, unsigned* cell, void* stream) {
+  if (!(bound > 0.f)) { set_error("act_split2h_pool_arg_debug: bad shape"); return NC_ERR_SHAPE; }
+  return act_split2h_pool_arg(x, mean, rstd, slope, ys, pooled, arg, N, C, D, H, W, ctot, c0, bound, cell, (hipStream_t)stream);
+}
+
 int nc_maxpool2_h2_debug(const void* in, void* out, int N, int C, int ctot, int D, int H, int W, void* stream) {
   if (!in || !out) { set_error("maxpool2_h2_debug: null pointer"); return NC_ERR_ARG; }
   if (D < 2 || H < 2 || W < 2 || !h2_part_ok(N, C, (long)D * H * W, ctot, 0)) { set_error("maxpool2_h2_debug: bad shape"); return NC_ERR_SHAPE; }

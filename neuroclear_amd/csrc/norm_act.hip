@@ -99,16 +99,11 @@ __global__ __launch_bounds__(256) void k_in_act_fwd(const float* __restrict__ x,
     float4* o4 = reinterpret_cast<float4*>(o);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < S / 4; i += (long)gridDim.x * 256) {
       float4 v = p4[i];
-      v.x = (v.x - m) * r; v.y = (v.y - m) * r; v.z = (v.z - m) * r; v.w = (v.w - m) * r;
-      v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope;
-      v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
+      v.x = in_act(v.x, m, r, slope); v.y = in_act(v.y, m, r, slope); v.z = in_act(v.z, m, r, slope); v.w = in_act(v.w, m, r, slope);
       o4[i] = v;
     }
   } else {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < S; i += (long)gridDim.x * 256) {
-      const float v = (p[i] - m) * r;
-      o[i] = v > 0.f ? v : v * slope;
-    }
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < S; i += (long)gridDim.x * 256) o[i] = in_act(p[i], m, r, slope);
   }
 }
 
@@ -866,13 +861,7 @@ __device__ __forceinline__ int pool_winner(const float* __restrict__ p, int od, 
   int arg = 0;
   for (int a = 0; a < wd; ++a)
     for (int b = 0; b < 2; ++b)
-      for (int c = 0; c < 2; ++c) {
-        const float v = p[((long)(od * wd + a) * H + (oh * 2 + b)) * W + ow * 2 + c];
-        if (v > best || v != v) {
-          best = v;
-          arg = (a * 2 + b) * 2 + c;
-        }
-      }
+      for (int c = 0; c < 2; ++c) pool_winner_step(p[((long)(od * wd + a) * H + (oh * 2 + b)) * W + ow * 2 + c], (a * 2 + b) * 2 + c, best, arg);
   return arg;
 }
 
