@@ -646,6 +646,21 @@ int nc_conv_dgrad_split(const float* dy, const void* dys, const float* w, float*
                         void* ws, size_t ws_bytes, void* stream);
 int nc_conv_wgrad_split(const float* x, const void* xs, const float* dy, const void* dys, float* dw, int N, int C, int D, int H, int W,
                         int K, int ks, void* ws, size_t ws_bytes, void* stream); /* nc_conv_wgrad (weights only) */
+/* Test exports of the two kernels that add up FIXED-ORDER partial sums (tests/test_gpu_partial_sums.py); each runs exactly the launch the
+ * library's own paths make.
+ * nc_wgrad_s3_reduce_debug: k_wgrad_s3_reduce (csrc/conv_split.hip) behind the 3^3 / 5^3 weight-gradient kernels.  T3 = 27 or 125, TW = 27 / 25
+ *   taps per workgroup, ndg = T3 / TW dz groups, npairs = (K / 64) * (C / 32) * ndg (<= 256), pair = ((k / 64) * (C / 32) + c / 32) * ndg + dz;
+ *   part: fp32 [nwp][npairs][NF][TW][64 k][32 c], 16-byte aligned -- workgroup w of a pair, accumulator flush f -- i.e.
+ *   npairs * nwp * NF * TW * 64 * 32 floats.  dw[k][c][dz * TW + tap] = the nslots = nwp * NF slots sl = w * NF + f of (pair, tap, k % 64, c % 32)
+ *   added as eight segments of per = ceil(nslots / 8) consecutive slots, each from 0.f in slot order (an empty segment is 0.f), the segments
+ *   as ((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7; with xcells / ycell (device words, both or neither; then C % 64 == 0) the sum r becomes
+ *   r * f.x * f.y, f the two powers of two that undo the cells xcells[c >= C / 2] and *ycell of the two-term operands.  guard (nullable, 8 device
+ *   words): the launch leaves dw alone unless word [2] says it is this form's turn (set: the form without cells; zero: the one with).
+ * nc_gemm_split_reduce_debug: k_gemm_split_reduce (csrc/conv_gemm.hip) behind every split gather GEMM: slab fp32 [splits][n],
+ *   out[i] = ((bias[(i / inner) % K] + slab[0][i]) + slab[1][i]) + ... (bias nullable: 0.f; inner, K are read only with a bias). */
+int nc_wgrad_s3_reduce_debug(const float* part, float* dw, int K, int C, int T3, int nwp, int NF, const unsigned* xcells, const unsigned* ycell,
+                             const unsigned* guard, void* stream);
+int nc_gemm_split_reduce_debug(const float* slab, float* out, long n, int splits, const float* bias, long inner, int K, void* stream);
 
 /* ConvTranspose3d(kernel 2, stride 2) forward -- nn.ConvTranspose3d at networks.py:471-478 -- on the same arithmetic (csrc/convt_s3.hip):
  * C % 32 == 0 (<= 256), K % 16 == 0.  xs: the input in S3 form, or NULL (x is converted into the workspace); y (nullable): fp32 output

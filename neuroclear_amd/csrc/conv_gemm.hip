@@ -315,12 +315,49 @@ __global__ __launch_bounds__(256 * KG) void k_conv_gemm(GemmParams p) {
 }
 
 // out[i] = bias[(i / inner) % K] + sum_k slab[k][i]   (fixed order: deterministic)
+// The order ((bias + slab[0][i]) + slab[1][i]) + ... is the contract (tests/test_gpu_partial_sums.py).  A thread's loads are issued eight slabs
+// at a time, before their adds (one add behind every load made the kernel `splits` memory latencies long whatever its size).
+// V = 4: four consecutive elements per thread through 16-byte accesses, n % 4 == 0 and both pointers 16-byte aligned (the launcher checks);
+// V = 1: everything else.  T: float4 / float.
+__device__ __forceinline__ void gsr_add(float& s, float v) { s += v; }
+__device__ __forceinline__ void gsr_add(float4& s, const float4& v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+template <int V, typename T>
 __global__ void k_gemm_split_reduce(const float* __restrict__ slab, float* __restrict__ out, long n, int splits,
                                     const float* __restrict__ bias, long inner, int K) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float s = bias ? bias[(i / inner) % K] : 0.f;
-    for (int k = 0; k < splits; ++k) s += slab[(long)k * n + i];
-    out[i] = s;
+  const long nv = n / V;
+  for (long iv = (long)blockIdx.x * blockDim.x + threadIdx.x; iv < nv; iv += (long)gridDim.x * blockDim.x) {
+    const long i = iv * V;
+    float b[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) b[e] = 0.f;
+    if (bias) {  // the channel per ELEMENT: with inner % 4 != 0 a thread's four span channels
+      long r = i % inner;
+      int ch = (int)((i / inner) % K);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        b[e] = bias[ch];
+        if (++r == inner) { r = 0; if (++ch == K) ch = 0; }
+      }
+    }
+    T s;
+    if constexpr (V == 4) s = make_float4(b[0], b[1], b[2], b[3]); else s = b[0];
+    const T* p = reinterpret_cast<const T*>(slab + i);
+    int k = 0;
+    for (; k + 8 <= splits; k += 8) {
+      T v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = p[(long)(k + j) * nv];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) gsr_add(s, v[j]);
+    }
+    if (k < splits) {  // the last 1 .. 7 slabs, again all loads first (splits is uniform: scalar branches)
+      T v[7];
+#pragma unroll
+      for (int j = 0; j < 7; ++j) if (k + j < splits) v[j] = p[(long)(k + j) * nv];
+#pragma unroll
+      for (int j = 0; j < 7; ++j) if (k + j < splits) gsr_add(s, v[j]);
+    }
+    *reinterpret_cast<T*>(out + i) = s;
   }
 }
 
@@ -472,13 +509,21 @@ static int split_setup(GemmParams& p, int splits, float* out, void* ws, size_t w
   }
   return NC_OK;
 }
+// Workgroups of 64 threads until there are 1024 of them (a small n still reaches every CU), of 256 beyond; at most 8192 workgroups
+static int gemm_split_reduce(const float* slab, float* out, long n, int splits, const float* bias, long inner, int K, hipStream_t s) {
+  const bool v4 = n % 4 == 0 && !(((uintptr_t)slab | (uintptr_t)out) & 15);
+  const long nt = v4 ? n / 4 : n;
+  const int bs = nt < 64 * 1024 ? 64 : 256;
+  const long nb = cdiv(nt, bs);
+  const dim3 grid((unsigned)(nb > 8192 ? 8192 : nb));
+  if (v4) hipLaunchKernelGGL((k_gemm_split_reduce<4, float4>), grid, dim3(bs), 0, s, slab, out, n, splits, bias, inner, K);
+  else hipLaunchKernelGGL((k_gemm_split_reduce<1, float>), grid, dim3(bs), 0, s, slab, out, n, splits, bias, inner, K);
+  return check_launch("gemm_split_reduce");
+}
 static int split_reduce(const GemmParams& p, float* out, long n, const float* bias, long inner, int K,
                         hipStream_t s) {
   if (p.splits == 1) return NC_OK;
-  const long nb = cdiv(n, 256);
-  hipLaunchKernelGGL(k_gemm_split_reduce, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, s,
-                     (const float*)p.out, out, n, p.splits, bias, inner, K);
-  return check_launch("gemm_split_reduce");
+  return gemm_split_reduce((const float*)p.out, out, n, p.splits, bias, inner, K, s);
 }
 
 int conv_fwd_gemm(const float* x, const float* w, const float* b, float* y, const ConvDims& d, void* ws, size_t wsb,
@@ -553,3 +598,11 @@ int conv_wgrad_gemm(const float* x, const float* dy, float* dw, const ConvDims& 
 }
 
 }  // namespace nc
+
+// Test export (tests/test_gpu_partial_sums.py): the launch split_reduce makes, on slabs the caller wrote ([splits][n] fp32)
+extern "C" int nc_gemm_split_reduce_debug(const float* slab, float* out, long n, int splits, const float* bias, long inner, int K, void* stream) {
+  using namespace nc;
+  if (!slab || !out) { set_error("gemm_split_reduce_debug: null pointer"); return NC_ERR_ARG; }
+  if (n < 1 || splits < 1 || (bias && (inner < 1 || K < 1))) { set_error("gemm_split_reduce_debug: bad shape"); return NC_ERR_SHAPE; }
+  return gemm_split_reduce(slab, out, n, splits, bias, bias ? inner : 1, bias ? K : 1, (hipStream_t)stream);
+}

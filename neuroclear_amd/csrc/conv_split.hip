@@ -1113,44 +1113,98 @@ __global__ void __launch_bounds__(kThreads, 1) k_wgrad_s3x(const WsParams p) {
   for (++nflush; nflush < p.NF; ++nflush) write_partial(false);
 }
 
-// dw[k][c][tap] = sum of the nwp * NF partial slots of pair (k/64, c/32, tap / TW).  A workgroup handles 32 consecutive outputs (one
-// 128-byte run of c); its 8 lane groups each add a contiguous eighth of the slots in slot order, and the eight sums are added in group
-// order: a fixed order (deterministic), with eight loads in flight per output instead of one dependent chain of several hundred
-// (the one-thread-per-output form ran at ~1 TB/s: 0.85 ms of the 108^3 step).
+// dw[k][c][tap] = sum of the nwp * NF partial slots of pair (k/64, c/32, tap / TW), in a fixed order (deterministic).
 // xcells != NULL (H2 operands): the sums are scaled back by 2^-(kx + ky), kx per half of the input channels (h2.hip)
-__global__ void __launch_bounds__(256) k_wgrad_s3_reduce(const float* __restrict__ part, float* __restrict__ dw, int C, int T3, int TW,
-                                                         int nct, int npairs, int nwp, int NF, long total,
-                                                         const unsigned* __restrict__ xcells = nullptr, const unsigned* __restrict__ ycell = nullptr,
-                                                         const unsigned* __restrict__ guard = nullptr) {
-  __shared__ float red[8][32];
-  if (guard_skip(guard, xcells ? 0 : 1)) return;
-  const int o = threadIdx.x & 31, seg = threadIdx.x >> 5;
-  const long i = (long)blockIdx.x * 32 + o;  // (k, tap, c): c fastest -> coalesced partial reads
-  float sacc = 0.f;
-  int c = 0, t = 0, k = 0;
-  if (i < total) {
-    c = (int)(i % C);
-    t = (int)((i / C) % T3);
-    k = (int)(i / ((long)C * T3));
-    const int ndg = T3 / TW;
-    const int pair = ((k / 64) * nct + c / 32) * ndg + t / TW;
-    const long off = ((long)(t % TW) * 64 + (k & 63)) * 32 + (c & 31);
-    const int nslots = nwp * NF, per = (nslots + 7) / 8;
-    const int s0 = seg * per, s1 = s0 + per < nslots ? s0 + per : nslots;
-    for (int sl = s0; sl < s1; ++sl) {
-      const int w = sl / NF, f = sl - w * NF;
-      sacc += part[(((long)(w * npairs + pair) * NF + f) * TW) * 64 * 32 + off];
-    }
-  }
-  red[seg][o] = sacc;
-  __syncthreads();
-  if (seg == 0 && i < total) {
-    float r = red[0][o];
+//
+// The ORDER is the contract (tests/test_gpu_partial_sums.py restates it in numpy, bit for bit): nslots = nwp * NF slots, slot sl = w * NF + f;
+// eight segments of per = ceil(nslots / 8) consecutive slots, each summed from 0.f in slot order (an empty segment stays 0.f); then
+// ((((((s0 + s1) + s2) + s3) + s4) + s5) + s6) + s7; then, with cells, r * f.x * f.y.
+// The SHAPE: one workgroup per (k, 32 channels, dz group); thread = (tap, four consecutive c) with all eight segment sums in registers, so a
+// step t issues the eight segments' 16-byte loads together, and U steps at once: 8 U independent loads in flight per thread, no LDS, no barrier
+// in the sums (the first form -- one 4-byte load per thread and step, each add behind its load -- ran at 1.2 TB/s).  The TW x 32 results cross
+// LDS once and leave as consecutive floats of dw (3^3: one run of 32 x 27; 5^3: 32 runs of 25) instead of 4-byte stores T3 floats apart.
+// U follows per (ws_reduce; U = 1, 2: per == U, one step without a loop; U = 4: any per).  Many slots come with few workgroups (K C / 32 of them:
+// 128 .. 512 at 256 slots), which need U = 4 to keep enough bytes in flight; few slots come with thousands of workgroups of one or two steps,
+// which need the registers of U = 1 / 2 (48 / 80) so that all of them are resident at once (at U = 4's 199 registers the 2048 workgroups of a
+// 256 -> 256 layer ran in four rounds: 26-38 us instead of 12).
+template <int U, bool ALL>  // ALL: every slot of these steps exists (no predicates: the waits are counted, adds start as loads land)
+__device__ __forceinline__ void ws_reduce_steps(const float* __restrict__ base, unsigned toff, float4 (&acc)[8], int t, int per, int nslots, int NF,
+                                                long wstride, long slot) {  // base: the workgroup's (uniform), toff: the thread's bytes behind it
+  float4 v[U][8];
 #pragma unroll
-    for (int g = 1; g < 8; ++g) r += red[g][o];
-    if (xcells) { const float2 f = h2_unscale2(xcells[c >= C / 2 ? 1 : 0], *ycell); r = r * f.x * f.y; }
-    dw[((long)k * C + c) * T3 + t] = r;
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int sl = j * per + t + u;  // (uniform over the workgroup: the predicate is a scalar branch)
+      if (ALL || sl < nslots) {
+        const int w = NF == 1 ? sl : sl / NF, f = sl - w * NF;
+        v[u][j] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(base + ((long)w * wstride + (long)f * slot)) + toff);
+      }
+    }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (ALL || j * per + t + u < nslots) {
+        acc[j].x += v[u][j].x; acc[j].y += v[u][j].y; acc[j].z += v[u][j].z; acc[j].w += v[u][j].w;
+      }
+}
+
+template <int U>  // (second bound: the waves per SIMD the registers must allow -- at least 8 / 4 / 2 workgroups a CU)
+__global__ void __launch_bounds__(256, U == 1 ? 8 : U == 2 ? 4 : 2)
+k_wgrad_s3_reduce(const float* __restrict__ part, float* __restrict__ dw, int C, int T3, int TW, int nct, int npairs, int nwp, int NF,
+                  const unsigned* __restrict__ xcells, const unsigned* __restrict__ ycell, const unsigned* __restrict__ guard) {
+  __shared__ float out[32 * 27];  // [c][tap], TW <= 27
+  if (guard_skip(guard, xcells ? 0 : 1)) return;
+  const int kk = blockIdx.x & 63, pair = blockIdx.x >> 6;  // pair = ((k / 64) * nct + c / 32) * ndg + dz group, as the writers number them
+  const int ndg = T3 / TW;
+  const int dzg = pair % ndg, ct = (pair / ndg) % nct, k = (pair / ndg / nct) * 64 + kk, c0 = ct * 32;
+  const int tap = threadIdx.x >> 3, j4 = (threadIdx.x & 7) * 4;
+  if (tap < TW) {
+    const long slot = (long)TW * 64 * 32;  // floats of one partial slot
+    const float* base = part + (long)pair * NF * slot + kk * 32;
+    const unsigned toff = (unsigned)(tap * 64 * 32 + j4) * 4u;
+    const long wstride = (long)npairs * NF * slot;
+    const int nslots = nwp * NF, per = (nslots + 7) / 8;
+    float4 acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (U < 4) {  // per == U: one step, no loop -- the sums never occupy registers beside the loads
+      if (nslots == 8 * U) ws_reduce_steps<U, true>(base, toff, acc, 0, U, nslots, NF, wstride, slot);
+      else ws_reduce_steps<U, false>(base, toff, acc, 0, U, nslots, NF, wstride, slot);
+    } else {
+      int t = 0;
+      for (; t + U <= per && 7 * per + t + U <= nslots; t += U) ws_reduce_steps<U, true>(base, toff, acc, t, per, nslots, NF, wstride, slot);
+      for (; t + U <= per; t += U) ws_reduce_steps<U, false>(base, toff, acc, t, per, nslots, NF, wstride, slot);
+      for (; t < per; ++t) ws_reduce_steps<1, false>(base, toff, acc, t, per, nslots, NF, wstride, slot);
+    }
+    float4 r = acc[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) { r.x += acc[j].x; r.y += acc[j].y; r.z += acc[j].z; r.w += acc[j].w; }
+    if (xcells) {  // (C % 64 == 0 with cells: the four c of a thread lie in one half)
+      const float2 f = h2_unscale2(xcells[c0 + j4 >= C / 2 ? 1 : 0], *ycell);
+      r.x = r.x * f.x * f.y; r.y = r.y * f.x * f.y; r.z = r.z * f.x * f.y; r.w = r.w * f.x * f.y;
+    }
+    out[(j4 + 0) * TW + tap] = r.x; out[(j4 + 1) * TW + tap] = r.y; out[(j4 + 2) * TW + tap] = r.z; out[(j4 + 3) * TW + tap] = r.w;
   }
+  __syncthreads();
+  float* o = dw + ((long)k * C + c0) * T3 + dzg * TW;
+  for (int e = threadIdx.x; e < 32 * TW; e += 256) {
+    const int c = e / TW;
+    o[(long)c * T3 + (e - c * TW)] = out[e];
+  }
+}
+
+// The one launch of k_wgrad_s3_reduce: npairs = (K / 64) * (C / 32) * (T3 / TW) pairs of nwp * NF slots each, 64 workgroups (one per k) a pair
+int ws_reduce(const float* part, float* dw, int C, int T3, int npairs, int nwp, int NF, const unsigned* xc, const unsigned* yc, const unsigned* guard,
+              hipStream_t s, const char* what) {
+  if ((uintptr_t)part & 15) { set_error("%s: partial sums not 16-byte aligned", what); return NC_ERR_ARG; }
+  const int TW = T3 == 27 ? 27 : 25, per = (nwp * NF + 7) / 8;
+  const dim3 grid((unsigned)npairs * 64);
+  if (per >= 3) hipLaunchKernelGGL(k_wgrad_s3_reduce<4>, grid, dim3(256), 0, s, part, dw, C, T3, TW, C / 32, npairs, nwp, NF, xc, yc, guard);
+  else if (per == 2) hipLaunchKernelGGL(k_wgrad_s3_reduce<2>, grid, dim3(256), 0, s, part, dw, C, T3, TW, C / 32, npairs, nwp, NF, xc, yc, guard);
+  else hipLaunchKernelGGL(k_wgrad_s3_reduce<1>, grid, dim3(256), 0, s, part, dw, C, T3, TW, C / 32, npairs, nwp, NF, xc, yc, guard);
+  return check_launch(what);
 }
 
 struct WsPlan {
@@ -1272,16 +1326,13 @@ int ws_core(int NT, const void* xs, const void* dys, const unsigned* xc, const u
   p.F = F; p.NF = NF;
   p.mTx = magic(pl.Tx); p.mXp = magic(pl.Xp); p.mXUp = magic(pl.XUp); p.mPTp = magic(pl.PTp);
   const int lds = NS * pl.xslot + 2 * pl.dybuf;
-  const long total = (long)d.K * d.C * T3;
   if (NT == 2) {
     if (int e = raise_dyn_lds((k_wgrad_s3x<3, 2, NC_DT_F16>), kLdsMax, "wgrad_h2")) return e;
     if (int e = raise_dyn_lds((k_wgrad_s3x<5, 2, NC_DT_F16>), kLdsMax, "wgrad_h2")) return e;
     if (KS == 3) hipLaunchKernelGGL((k_wgrad_s3x<3, 2, NC_DT_F16>), dim3(npairs * nwp), dim3(kThreads), lds, s, p);
     else hipLaunchKernelGGL((k_wgrad_s3x<5, 2, NC_DT_F16>), dim3(npairs * nwp), dim3(kThreads), lds, s, p);
     if (int e = check_launch("wgrad_h2")) return e;
-    hipLaunchKernelGGL(k_wgrad_s3_reduce, dim3((unsigned)cdiv(total, 32)), dim3(256), 0, s, (const float*)part, dw, d.C, T3, TW, d.C / 32, npairs, nwp,
-                       NF, total, xc, yc, guard);
-    return check_launch("wgrad_h2_reduce");
+    return ws_reduce(part, dw, d.C, T3, npairs, nwp, NF, xc, yc, guard, s, "wgrad_h2_reduce");
   }
   if (int e = raise_dyn_lds(k_wgrad_s3<3>, kLdsMax, "wgrad_s3")) return e;
   if (int e = raise_dyn_lds(k_wgrad_s3<5>, kLdsMax, "wgrad_s3")) return e;
@@ -1293,9 +1344,7 @@ int ws_core(int NT, const void* xs, const void* dys, const unsigned* xc, const u
   } else if (KS == 3) hipLaunchKernelGGL(k_wgrad_s3<3>, dim3(npairs * nwp), dim3(kThreads), lds, s, p);
   else hipLaunchKernelGGL(k_wgrad_s3<5>, dim3(npairs * nwp), dim3(kThreads), lds, s, p);
   if (int e = check_launch("wgrad_s3")) return e;
-  hipLaunchKernelGGL(k_wgrad_s3_reduce, dim3((unsigned)cdiv(total, 32)), dim3(256), 0, s, (const float*)part, dw, d.C, T3, TW, d.C / 32, npairs, nwp,
-                     NF, total, (const unsigned*)nullptr, (const unsigned*)nullptr, guard);
-  return check_launch("wgrad_s3_reduce");
+  return ws_reduce(part, dw, d.C, T3, npairs, nwp, NF, nullptr, nullptr, guard, s, "wgrad_s3_reduce");
 }
 
 // The weight gradient on H2 operands (two fp16 terms, three products): k_wgrad_s3x<KS, 2, f16>; xs_pre / dys_pre: H2 tensors with their cells, or
@@ -1413,10 +1462,7 @@ int run_wsx(const void* xh, const void* dyh, float* dw, const ConvDims& d, void*
   if (KS == 3) hipLaunchKernelGGL((k_wgrad_s3x<3, 1, DT>), dim3(npairs * nwp), dim3(kThreads), lds, s, p);
   else hipLaunchKernelGGL((k_wgrad_s3x<5, 1, DT>), dim3(npairs * nwp), dim3(kThreads), lds, s, p);
   if (int e = check_launch("wgrad_c8x")) return e;
-  const long total = (long)d.K * d.C * T3;
-  hipLaunchKernelGGL(k_wgrad_s3_reduce, dim3((unsigned)cdiv(total, 32)), dim3(256), 0, s, (const float*)ws, dw, d.C, T3, TW, d.C / 32, npairs, nwp, 1,
-                     total);
-  return check_launch("wgrad_c8x_reduce");
+  return ws_reduce((const float*)ws, dw, d.C, T3, npairs, nwp, 1, nullptr, nullptr, nullptr, s, "wgrad_c8x_reduce");
 }
 
 }  // namespace
@@ -1610,3 +1656,17 @@ int conv_dgrad_s3(const float* dy, const void* dys, const float* w, float* dx, c
 }
 
 }  // namespace nc
+
+// Test export (tests/test_gpu_partial_sums.py): the launch ws_core / run_wsx make, on partial sums the caller wrote (layout: nc_hip.h)
+extern "C" int nc_wgrad_s3_reduce_debug(const float* part, float* dw, int K, int C, int T3, int nwp, int NF, const unsigned* xcells,
+                                        const unsigned* ycell, const unsigned* guard, void* stream) {
+  using namespace nc;
+  if (!part || !dw || !xcells != !ycell) { set_error("wgrad_s3_reduce_debug: null pointer"); return NC_ERR_ARG; }
+  const int TW = T3 == 27 ? 27 : 25;
+  if ((T3 != 27 && T3 != 125) || K < 64 || K % 64 || C < 32 || C % (xcells ? 64 : 32) || nwp < 1 || NF < 1 ||
+      (long)(K / 64) * (C / 32) * (T3 / TW) > 256 || (long)nwp * NF > (1 << 20)) {
+    set_error("wgrad_s3_reduce_debug: bad shape");
+    return NC_ERR_SHAPE;
+  }
+  return ws_reduce(part, dw, C, T3, (K / 64) * (C / 32) * (T3 / TW), nwp, NF, xcells, ycell, guard, (hipStream_t)stream, "wgrad_s3_reduce");
+}
