@@ -42,6 +42,13 @@ int nc_version(void);
  * gradient (3^3 / 7^3, W % 4 == 0).  The query assumes a 256^2 plane for pointwise kernels, a 32^3 volume otherwise. */
 int nc_conv_fwd_path(int C, int K, int kd, int kh, int kw, int stride, int pad);
 int nc_conv_wgrad_path(int C, int K, int kd, int kh, int kw, int stride, int pad);
+/* Test query (tests/test_gpu_conv_fp32.py): which variant of the fp32 brick kernels (csrc/conv_mfma_fwd.hip, conv_mfma_wgrad.hip) a k^3, stride 1,
+ * padding k / 2 layer takes; launches nothing.  out: 8 ints (host).  what = 0 forward, 1 data gradient: cfg (0 .. 4: waves along M x waves along
+ * N x position blocks 8x1x4, 8x1x2, 4x2x2, 2x4x2, 2x4x1), CK, Tz, Ty, 1 for the TAIL kernels (W % 4 != 0), nchunks, units (stream-K: tiles x
+ * nchunks over 256 workgroups), tiles.  what = 2 weight gradient: kernel (0 k_wgrad_rows<3>, 1 k_wgrad_dma<KS, AB>, 2 k_wgrad_mfma<KS, AB>), KS,
+ * AB (kernel 0: rows per step), column blocks (kernel 1), parts, G, 0, 0.  NC_ERR_SHAPE where the brick kernels do not take the layer (a data
+ * gradient with K = 1 among them: the single-channel mode is forward only). */
+int nc_conv_mfma_plan_debug(int what, int N, int C, int D, int H, int W, int K, int k, int* out);
 /* Live launch profiler (bench.py's `roofline`): between nc_prof_begin and nc_prof_end every convolution entry point of
  * >= min_flop algorithmic FLOP is bracketed by HIP events on the stream it is launched on.  nc_prof_end returns the number
  * of recorded calls and fills the first `max`: cls = op (0 fwd, 1 dgrad, 2 wgrad) | path << 4 | kernel edge << 8 |

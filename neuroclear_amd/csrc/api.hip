@@ -222,6 +222,15 @@ int nc_conv_wgrad_path(int C, int K, int kd, int kh, int kw, int stride, int pad
                                                                          : gemm_wgrad_supported(d) ? 2 : 0;
 }
 
+int nc_conv_mfma_plan_debug(int what, int N, int C, int D, int H, int W, int K, int k, int* out) {
+  ConvDims d;
+  if (!out) { set_error("conv_mfma_plan_debug: null pointer"); return NC_ERR_ARG; }
+  if (what < 0 || what > 2 || !make_dims(d, N, C, D, H, W, K, k, k, k, 1, k / 2)) { set_error("conv_mfma_plan_debug: bad arguments"); return NC_ERR_SHAPE; }
+  if (what == 2 ? mfma_wgrad_plan_debug(d, out) : mfma_fwd_plan_debug(d, what, out)) return NC_OK;
+  set_error("conv_mfma_plan_debug: the brick kernels do not take this layer");
+  return NC_ERR_SHAPE;
+}
+
 size_t nc_conv_ws_bytes(int N, int C, int D, int H, int W, int K, int kd, int kh, int kw, int stride, int pad) {
   ConvDims d;
   if (!make_dims(d, N, C, D, H, W, K, kd, kh, kw, stride, pad)) return 0;

@@ -115,6 +115,9 @@ int conv_dgrad_mfma(const float* dy, const float* w, float* dx, const ConvDims& 
                     hipStream_t s);
 int conv_wgrad_mfma(const float* x, const float* dy, float* dw, const ConvDims& d, void* ws, size_t wsb,
                     hipStream_t s);
+// nc_conv_mfma_plan_debug: what run() / conv_wgrad_mfma would choose for this layer, 8 ints each; false where they take no such layer
+bool mfma_fwd_plan_debug(const ConvDims& d, int dgrad, int* out);
+bool mfma_wgrad_plan_debug(const ConvDims& d, int* out);
 
 // ---- generic gather-GEMM MFMA kernels, conv_gemm.hip
 bool gemm_fwd_supported(const ConvDims& d);

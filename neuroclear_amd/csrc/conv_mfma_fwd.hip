@@ -568,9 +568,12 @@ bool mfma_fwd_supported(const ConvDims& d) {
   FwdPlan pl;
   return shape_ok(d, d.C, d.K) && plan_fwd(d.kd, d.C, d.K, d.N, d.D, d.H, d.W, pl);
 }
+// The single-channel mode is forward only: k_pack_w_c1 has no flipped form, and the workspace below is sized for the forward roles.  A K = 1
+// data gradient (its Cin would be 1) goes down api.hip's ladder to the gather GEMM.
+static bool dgrad_shape_ok(const ConvDims& d) { return d.K != 1 && shape_ok(d, d.K, d.C); }
 bool mfma_dgrad_supported(const ConvDims& d) {
   FwdPlan pl;
-  return shape_ok(d, d.K, d.C) && plan_fwd(d.kd, d.K, d.C, d.N, d.D, d.H, d.W, pl);
+  return dgrad_shape_ok(d) && plan_fwd(d.kd, d.K, d.C, d.N, d.D, d.H, d.W, pl);
 }
 
 // bytes of workspace the fwd / dgrad MFMA kernels need for this shape: packed weights + prefetch slack + partial slots
@@ -580,7 +583,7 @@ size_t mfma_fwd_ws_bytes(const ConvDims& d) {
   const size_t pack = (packed_floats(d.kd, d.C, d.K) * sizeof(float) + kPackSlackBytes + 255) & ~(size_t)255;
   if (shape_ok(d, d.C, d.K) && plan_fwd(d.kd, d.C, d.K, d.N, d.D, d.H, d.W, pl))
     need = pack + part_bytes(kCfgs[pl.cfg]);
-  if (shape_ok(d, d.K, d.C) && plan_fwd(d.kd, d.K, d.C, d.N, d.D, d.H, d.W, pl)) {
+  if (dgrad_shape_ok(d) && plan_fwd(d.kd, d.K, d.C, d.N, d.D, d.H, d.W, pl)) {
     const size_t b = pack + part_bytes(kCfgs[pl.cfg]);
     if (b > need) need = b;
   }
@@ -640,6 +643,20 @@ int conv_fwd_mfma(const float* x, const float* w, const float* b, float* y, cons
 int conv_dgrad_mfma(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb,
                     hipStream_t s) {
   return run(dy, w, nullptr, dx, d.K, d.C, d, 1, ws, wsb, s);
+}
+
+// The plan run() takes for the forward (dgrad = 0) or the data gradient (dgrad = 1) of this layer: cfg (row of kCfgs), CK, Tz, Ty, the TAIL
+// flag, nchunks, units (as run() computes them), tiles.  Nothing is launched.
+bool mfma_fwd_plan_debug(const ConvDims& d, int dgrad, int* out) {
+  const int Cin = dgrad ? d.K : d.C, Cout = dgrad ? d.C : d.K;
+  FwdPlan pl;
+  if (!(dgrad ? dgrad_shape_ok(d) : shape_ok(d, Cin, Cout)) || !plan_fwd(d.kd, Cin, Cout, d.N, d.D, d.H, d.W, pl)) return false;
+  const long tiles = (long)d.N * (Cout / (kCfgs[pl.cfg].WN * 64)) * pl.ntz * pl.nty;
+  const int nchunks = Cin / pl.CK;
+  if (tiles * nchunks >= (1L << 31)) return false;
+  out[0] = pl.cfg; out[1] = pl.CK; out[2] = pl.Tz; out[3] = pl.Ty; out[4] = (d.W & 3) ? 1 : 0;
+  out[5] = nchunks; out[6] = (int)(tiles * nchunks); out[7] = (int)tiles;
+  return true;
 }
 
 }  // namespace nc

@@ -875,4 +875,19 @@ int conv_wgrad_mfma(const float* x, const float* dy, float* dw, const ConvDims& 
   return check_launch("wgrad_reduce");
 }
 
+// The kernel conv_wgrad_mfma takes for this layer, in its order of preference: out[0] = 0 k_wgrad_rows<3> (out[2] = rows per step R),
+// 1 k_wgrad_dma<KS, AB> (out[3] = column blocks NXB), 2 k_wgrad_mfma<KS, AB>; out[1] = KS, out[2] = AB (kernels 1, 2), out[4] = parts,
+// out[5] = G (grid = parts x G).  Nothing is launched.
+bool mfma_wgrad_plan_debug(const ConvDims& d, int* out) {
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  out[1] = d.kd;
+  WrPlan pr;
+  if (plan_wgrad_rows(d, pr)) { out[0] = 0; out[2] = pr.R; out[4] = pr.parts; out[5] = pr.G; return true; }
+  WdPlan pd;
+  if (plan_wgrad_dma(d, pd)) { out[0] = 1; out[2] = pd.AB; out[3] = pd.NXB; out[4] = pd.parts; out[5] = pd.G; return true; }
+  WgPlan pl;
+  if (plan_wgrad(d, pl)) { out[0] = 2; out[2] = pl.AB; out[4] = pl.parts; out[5] = pl.G; return true; }
+  return false;
+}
+
 }  // namespace nc

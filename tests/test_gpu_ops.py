@@ -30,43 +30,48 @@ def T(seed, shape, scale=1.0, shift=0.0):
     return ((torch.rand(shape, generator=g) - 0.5) * 2 * scale + shift).to(DEV)
 
 
+# What the `auto` arm of a case reaches at default switches -- forward / data gradient / weight gradient, read from the library's profiler.  The
+# `direct` arm is always the VALU kernels of conv_direct.hip (and bias_grad).  The fp32 kernels named here are held to float64 branch by branch in
+# tests/test_gpu_conv_fp32.py, the newer families in their own files:
+#   split = the split-operand kernels (conv_split.hip), h2 = Conv3d(1, 64, 7) in two-term pseudo-channel form (conv_s3x.hip), c1k3 = conv_c1k3.hip,
+#   gemm = the gather GEMM (conv_gemm.hip), flat = conv_1x1.hip, c1w / k1 = k_wgrad_c1 / the K = 1 reductions (conv_c1.hip), p2d = conv_p2d.hip /
+#   wgrad_p2d.hip, img = the image-staged kernels (conv2d_img.hip), pg1 = patchgan_edge.hip, valu = conv_direct.hip
 CONV_CASES = [
     # N, C, K, spatial, k, stride, pad
-    (1, 1, 64, (12, 12, 12), 3, 1, 1),
-    (1, 64, 64, (12, 14, 20), 3, 1, 1),      # MFMA
-    (2, 64, 128, (9, 10, 27), 3, 1, 1),      # MFMA, odd sizes, batch 2
-    (1, 128, 256, (7, 7, 7), 3, 1, 1),       # MFMA small
-    (1, 256, 128, (8, 12, 12), 3, 1, 1),     # MFMA
-    (1, 128, 64, (6, 20, 36), 3, 1, 1),      # MFMA (ex_conv1_1 shape class)
-    (1, 64, 64, (10, 12, 16), 5, 1, 2),      # MFMA 5^3
-    (1, 64, 64, (6, 7, 60), 5, 1, 2),        # 5^3, W > 56, W % 4 == 0: k_wgrad_dma<5,1>
-    (1, 64, 64, (5, 6, 72), 3, 1, 1),        # 3^3, W > 56, W % 4 == 0: k_wgrad_dma<3,2>, two column blocks
-    (1, 32, 64, (5, 6, 70), 3, 1, 1),        # 3^3, W > 56, W % 4 != 0: register-staged k_wgrad_mfma, TAIL fwd kernel
-    (2, 32, 64, (6, 5, 54), 3, 1, 1),        # W = 54: k_wgrad_rows with 2 rows per step, row tails
-    (1, 1, 64, (12, 12, 12), 7, 1, 3),
-    (1, 1, 64, (10, 9, 20), 7, 1, 3),        # tap-axis MFMA wgrad (W % 4 == 0), ragged D/H
-    (2, 1, 64, (7, 11, 36), 3, 1, 1),        # same, 3^3, batch 2
-    (2, 1, 64, (5, 30, 24), 7, 1, 3),        # MFMA 64 -> 1 data gradient: row ranges that split planes (halo rows)
-    (2, 1, 64, (9, 10, 70), 7, 1, 3),        # 7^3, ragged: exercises tile edges of the many->one dgrad kernel
-    (1, 1, 64, (8, 9, 148), 7, 1, 3),        # W > 112: the 64 -> 1 data gradient runs as two column segments
-    (1, 1, 64, (7, 8, 116), 7, 1, 3),        # same, narrowest two-segment case
-    (1, 64, 1, (10, 10, 10), 1, 1, 0),
-    (1, 1, 1, (8, 8, 8), 1, 1, 0),
-    (1, 64, 32, (6, 6, 6), 1, 1, 0),
-    (1, 64, 32, (28, 28, 24), 1, 1, 0),      # 1x1 wgrad on the flat-voxel MFMA kernel (18816 voxels, ragged last chunk)
-    (2, 16, 1, (26, 26, 28), 1, 1, 0),       # same, channel padding on both sides, batch 2
-    (1, 1, 1, (32, 32, 32), 1, 1, 0),
-    (3, 1, 64, (36, 36), 4, 2, 1),           # PatchGAN 2-D
-    (1, 64, 128, (18, 18), 4, 2, 1),
-    (1, 256, 512, (4, 4), 4, 1, 1),
-    (1, 512, 1, (3, 3), 4, 1, 1),
-    (32, 128, 256, (40, 40), 4, 1, 1),       # Athena-sized batch: 128-row gather-GEMM tiles (fwd, dgrad)
-    (32, 128, 256, (40, 40), 4, 2, 1),       # same, strided: parity-class dgrad on 128-row tiles
-    (24, 160, 192, (33, 35), 4, 1, 1),
-    (20, 512, 1, (12, 12), 4, 1, 1),         # PatchGAN head at a large batch: K = 1 reduction kernels (fwd, wgrad)
-    (3, 100, 1, (9, 10, 11), 4, 1, 1),       # same in 3-D, ragged channel groups
-       # 128-row tiles with a ragged last row tile (M = 192 / 160) and ragged N
-    (1, 1, 64, (12, 12, 12), 4, 2, 1),       # PatchGAN 3-D
+    (1, 1, 64, (12, 12, 12), 3, 1, 1),       # c1k3 / gemm / gemm (W < 16: not c1w)
+    (1, 64, 64, (12, 14, 20), 3, 1, 1),      # split / split / split
+    (2, 64, 128, (9, 10, 27), 3, 1, 1),      # split x 3, odd sizes, batch 2
+    (1, 128, 256, (7, 7, 7), 3, 1, 1),       # split x 3, small
+    (1, 256, 128, (8, 12, 12), 3, 1, 1),     # split x 3
+    (1, 128, 64, (6, 20, 36), 3, 1, 1),      # split x 3 (ex_conv1_1 shape class)
+    (1, 64, 64, (10, 12, 16), 5, 1, 2),      # split x 3, 5^3
+    (1, 64, 64, (6, 7, 60), 5, 1, 2),        # split x 3, 5^3, W > 56
+    (1, 64, 64, (5, 6, 72), 3, 1, 1),        # split x 3, W > 56
+    (1, 32, 64, (5, 6, 70), 3, 1, 1),        # split / gemm (C = 32 is no multiple of 64) / split, W % 4 != 0
+    (2, 32, 64, (6, 5, 54), 3, 1, 1),        # split / gemm / split, W = 54
+    (1, 1, 64, (12, 12, 12), 7, 1, 3),       # h2 / h2 / gemm (W < 16: not c1w)
+    (1, 1, 64, (10, 9, 20), 7, 1, 3),        # h2 / h2 / c1w (W % 4 == 0), ragged D/H
+    (2, 1, 64, (7, 11, 36), 3, 1, 1),        # c1k3 / gemm / c1w, 3^3, batch 2
+    (2, 1, 64, (5, 30, 24), 7, 1, 3),        # h2 / h2 / c1w
+    (2, 1, 64, (9, 10, 70), 7, 1, 3),        # h2 / h2 / gemm (W % 4 != 0), ragged
+    (1, 1, 64, (8, 9, 148), 7, 1, 3),        # h2 / h2 / c1w, W > 112
+    (1, 1, 64, (7, 8, 116), 7, 1, 3),        # h2 / h2 / c1w
+    (1, 64, 1, (10, 10, 10), 1, 1, 0),       # valu (one GEMM row, R < 256) / gemm / gemm
+    (1, 1, 1, (8, 8, 8), 1, 1, 0),           # valu / valu / gemm (one padded row, 512 positions)
+    (1, 64, 32, (6, 6, 6), 1, 1, 0),         # gemm x 3 (216 voxels: below the flat kernels' 16384)
+    (1, 64, 32, (28, 28, 24), 1, 1, 0),      # flat x 3 (18816 voxels, ragged last chunk)
+    (2, 16, 1, (26, 26, 28), 1, 1, 0),       # flat x 3, channel padding on both sides, batch 2
+    (1, 1, 1, (32, 32, 32), 1, 1, 0),        # flat x 3
+    (3, 1, 64, (36, 36), 4, 2, 1),           # pg1 x 3: PatchGAN 2-D, first layer
+    (1, 64, 128, (18, 18), 4, 2, 1),         # gemm x 3 (81 positions: too few for img / p2d), parity-class dgrad
+    (1, 256, 512, (4, 4), 4, 1, 1),          # gemm x 3, split reductions
+    (1, 512, 1, (3, 3), 4, 1, 1),            # gemm (one padded row) / gemm / valu (4 positions)
+    (32, 128, 256, (40, 40), 4, 1, 1),       # p2d x 3: Athena-sized batch
+    (32, 128, 256, (40, 40), 4, 2, 1),       # p2d / p2d / img, strided
+    (24, 160, 192, (33, 35), 4, 1, 1),       # img / gemm (the flipped forward on 128-row tiles: M = 160, ragged) / p2d
+    (20, 512, 1, (12, 12), 4, 1, 1),         # k1 / gemm / k1: PatchGAN head at a large batch
+    (3, 100, 1, (9, 10, 11), 4, 1, 1),       # k1 / gemm / k1, 3-D, ragged channel groups
+    (1, 1, 64, (12, 12, 12), 4, 2, 1),       # gemm x 3: PatchGAN 3-D, parity-class dgrad
 ]
 
 
