@@ -498,7 +498,8 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
 /* ---- The 16-bit END-TO-END path (BASELINE.json configs[3]): operators between which activations and gradients exist in
  *      HBM only as 16-bit "C8" tensors [N][C/8][S][8] (nc_to_c8's layout).  A tensor argument (ptr, ctot, c0) means
  *      channels [c0, c0 + C) of a ctot-channel C8 buffer -- halves of the skip concat buffers (networks.py:526,531) are
- *      read / written in place.  Gradient tensors are bf16.  Statistics: fp32 per-thread partials, fp64 reduction.
+ *      read / written in place.  Gradient tensors are bf16.  Statistics: fp32 per-thread partials of x - the instance's first voxel, fp64 reduction.
+ *      The nc_c8_* entries and nc_from_c8 refuse N * C / 8 > 65535 (the heads: N > 65535) with NC_ERR_SHAPE before their first launch.
  *      nc_conv_fwd_c8 / nc_conv_dgrad_c8: nc_conv_fwd_lp / nc_conv_dgrad_lp with a C8 result (rounded to dtype);
  *      nc_c8_instnorm_*: InstanceNorm3d(affine=False) + ReLU / LeakyReLU (networks.py:33-34,422-423) and its backward
  *      (g = gradient at the activation output, xh = raw convolution output; dbias nullable = sum of dx per channel);
@@ -543,6 +544,13 @@ int nc_convT_k2s2_dgrad_c8(const void* dyh, int dy_ctot, int dy_c0, const float*
                            void* ws, size_t ws_bytes, void* stream);
 int nc_convT_k2s2_wgrad_c8(const void* xh, const void* dyh, int dy_ctot, int dy_c0, float* dw, float* dbias /* or NULL */, int N,
                            int C, int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream);
+/* Test exports of the 64 -> 1 pointwise heads of both generators on this path (csrc/c8_ops.hip; tests/test_gpu_c8_ops.py): each validates
+ * its arguments and forwards.  nc_c8_dot64_debug: out fp32 [N][S] = bias (nullable) + sum_c w[c] xh[n][c][v], xh a dense 64-channel C8
+ * tensor.  nc_c8_outer64_debug: the backward, dxh (nullable; bf16 C8) = w (x) g, dw[64] = sum g x, db (nullable) = sum g; N <= 65535. */
+int nc_c8_dot64_debug(const void* xh, const float* w, const float* bias, float* out, int N, long S, int dtype, void* stream);
+size_t nc_c8_outer64_ws_bytes_debug(int N, long S);
+int nc_c8_outer64_debug(const float* g, const void* xh, const float* w, void* dxh, float* dw, float* db, int N, long S, int dtype, void* ws,
+                        size_t ws_bytes, void* stream);
 
 /* ---- Whole-network training passes of the generators on that path (dtype = NC_DT_BF16): same contract as
  *      nc_unet_deconv_train_fwd / _bwd and nc_deep_linear_fwd / _bwd, `saved` in bytes.  The one-channel first layers

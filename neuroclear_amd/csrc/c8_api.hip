@@ -10,6 +10,9 @@ int c8_instnorm_bwd(const void* g, int gctot, int gc0, const void* x, const floa
 int c8_maxpool_fwd(const void* x, int ctot, int c0, void* y, int N, int C, int D, int H, int W, int dt, hipStream_t s);
 int c8_maxpool_bwd_add(const void* dp, const void* x, int ctot, int c0, const void* skip, int sctot, int sc0, void* dx, int N, int C, int D, int H, int W, int dt, hipStream_t s);
 int c8_to_f32(const void* x, int ctot, int c0, float* y, int N, int C, long S, int dt, hipStream_t s);
+int c8_dot64(const void* x, const float* w, const float* bias, float* out, int N, long S, int dt, hipStream_t s);
+size_t c8_outer64_ws_bytes(int N, long S);
+int c8_outer64(const float* g, const void* x, const float* w, void* dx, float* dw, float* db, int N, long S, int dt, void* ws, size_t wsb, hipStream_t s);
 bool convT_h_supported(int C, int K);
 size_t convT_h_ws_bytes(int N, int C, int D, int H, int W, int K);
 int convT_fwd_h(const void* x, const float* w, const float* bias, void* out, int octot, int oc0, int N, int C, int D, int H, int W, int K, int dt, void* ws, size_t wsb, hipStream_t s);
@@ -111,6 +114,22 @@ int nc_from_c8(const void* xh, int x_ctot, int x_c0, float* y, int N, int C, lon
   if (!xh || !y) { set_error("from_c8: null pointer"); return NC_ERR_ARG; }
   if (!dt_ok(dtype) || N < 1 || S < 1) { set_error("from_c8: bad dtype / shape"); return NC_ERR_ARG; }
   return c8_to_f32(xh, x_ctot, x_c0, y, N, C, S, dtype, (hipStream_t)stream);
+}
+
+// test exports of the 64 -> 1 heads (tests/test_gpu_c8_ops.py)
+int nc_c8_dot64_debug(const void* xh, const float* w, const float* bias, float* out, int N, long S, int dtype, void* stream) {
+  if (!xh || !w || !out) { set_error("c8_dot64_debug: null pointer"); return NC_ERR_ARG; }
+  if (!dt_ok(dtype)) { set_error("c8_dot64_debug: bad dtype"); return NC_ERR_ARG; }
+  return c8_dot64(xh, w, bias, out, N, S, dtype, (hipStream_t)stream);
+}
+
+size_t nc_c8_outer64_ws_bytes_debug(int N, long S) { return (N < 1 || N > 65535 || S < 1) ? 0 : c8_outer64_ws_bytes(N, S); }
+
+int nc_c8_outer64_debug(const float* g, const void* xh, const float* w, void* dxh, float* dw, float* db, int N, long S, int dtype, void* ws,
+                        size_t ws_bytes, void* stream) {
+  if (!g || !xh || !w || !dw) { set_error("c8_outer64_debug: null pointer"); return NC_ERR_ARG; }
+  if (!dt_ok(dtype)) { set_error("c8_outer64_debug: bad dtype"); return NC_ERR_ARG; }
+  return c8_outer64(g, xh, w, dxh, dw, db, N, S, dtype, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t nc_convT_c8_ws_bytes(int N, int C, int D, int H, int W, int K) { return convT_h_supported(C, K) ? convT_h_ws_bytes(N, C, D, H, W, K) : 0; }

@@ -67,7 +67,11 @@ __device__ __forceinline__ void block_reduce(double* v, double* lds /* [4][NV] *
   if (threadIdx.x < NV) out[threadIdx.x] = lds[threadIdx.x] + lds[NV + threadIdx.x] + lds[2 * NV + threadIdx.x] + lds[3 * NV + threadIdx.x];
 }
 
-// ---- InstanceNorm statistics: part[(ncb * splits + split)][16] = 8 sums, 8 sums of squares ------------------------
+// ---- InstanceNorm statistics: part[(ncb * splits + split)][16] = 8 sums, 8 sums of squares of x - pivot ----------
+// The pivot is the instance's own first voxel (the same for every split of the instance): the variance does not depend on it, and the fp32
+// chains of squares stay of the size of the spread.  Unshifted, an instance with |mean| >> deviation loses the variance in them: fp16 data
+// of mean 100 and deviation 1 came out with rstd 7e-4 off (tests/test_gpu_c8_ops.py, the 'offset' case), more than half an fp16 ulp of
+// every normalised value.
 template <int DT>
 __global__ void __launch_bounds__(256) k_stats_c8(const uint4* __restrict__ x, long S, int splits, double* __restrict__ part) {
   __shared__ double lds[4 * 16];
@@ -75,12 +79,18 @@ __global__ void __launch_bounds__(256) k_stats_c8(const uint4* __restrict__ x, l
   const int split = blockIdx.x;
   const long lo = S * split / splits, hi = S * (split + 1) / splits;
   const uint4* xs = x + ncb * S;
+  float pv[8];
+  unpack8<DT>(xs[0], pv);
   float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (long v = lo + threadIdx.x; v < hi; v += 256) {
     float f[8];
     unpack8<DT>(xs[v], f);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] += f[j]; q[j] = fmaf(f[j], f[j], q[j]); }
+    for (int j = 0; j < 8; ++j) {
+      const float d = f[j] - pv[j];
+      s[j] += d;
+      q[j] = fmaf(d, d, q[j]);
+    }
   }
   double d[16];
 #pragma unroll
@@ -105,17 +115,19 @@ __device__ __forceinline__ void c8_final_sums(const double* __restrict__ part, i
   }
 }
 
-__global__ void __launch_bounds__(64) k_stats_final_c8(const double* __restrict__ part, int NC, int splits, long S, float eps,
-                                                       float* __restrict__ mean, float* __restrict__ rstd) {
+template <int DT>
+__global__ void __launch_bounds__(64) k_stats_final_c8(const double* __restrict__ part, const uint4* __restrict__ x, int NC, int splits,
+                                                       long S, float eps, float* __restrict__ mean, float* __restrict__ rstd) {
   const int ncb = blockIdx.x, lane = threadIdx.x;
   double s, q;
   c8_final_sums(part, ncb, splits, lane, s, q);
   const int i = ncb * 8 + lane;  // n * C + c
   if (lane < 8 && i < NC) {
+    const unsigned short* pv = reinterpret_cast<const unsigned short*>(x + (long)ncb * S);  // the pivot of k_stats_c8
     const double m = s / (double)S;
     double var = q / (double)S - m * m;
     if (var < 0) var = 0;
-    mean[i] = (float)m;
+    mean[i] = (float)((double)cvtf<DT>(pv[lane]) + m);
     rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
   }
 }
@@ -261,8 +273,6 @@ __global__ void __launch_bounds__(256) k_pool_c8(const uint4* __restrict__ x, in
   float best[8];
   unsigned short bh[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; bh[j] = 0; }
-#pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < 2; ++b)
@@ -275,7 +285,8 @@ __global__ void __launch_bounds__(256) k_pool_c8(const uint4* __restrict__ x, in
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float f = cvtf<DT>(hv[j]);
-          if (f > best[j] || f != f) { best[j] = f; bh[j] = hv[j]; }
+          // the first element starts the scan with its own bits: a window of eight -inf is -inf, as MaxPool3d has it
+          if ((a | b | c) == 0 || f > best[j] || f != f) { best[j] = f; bh[j] = hv[j]; }
         }
       }
   uint4 out;
@@ -419,6 +430,9 @@ __global__ void __launch_bounds__(256) k_outer64_final(const double* __restrict_
 }  // namespace
 
 // ---- host side (internal API, used by gen_nets_lp.hip and the extern "C" wrappers below) ------------------------------------
+// N * C / 8 (the heads: N) is gridDim.y of every launch here: past 65535 the runtime rejects the launch, and in a multi-launch call the
+// later kernels would then read a workspace nobody wrote -- so every launcher refuses it before its first launch
+static bool grid_y_ok(long n) { return n >= 1 && n <= 65535; }
 size_t c8_stats_ws_bytes(int N, int C, long S) {
   const size_t a = (size_t)N * (C / 8) * splits_for(S) * 16 * sizeof(double);
   const long nbx = cdiv(S, 256 * 8);
@@ -428,20 +442,23 @@ size_t c8_stats_ws_bytes(int N, int C, long S) {
 
 int c8_instnorm_stats(const void* x, int N, int C, long S, float eps, float* mean, float* rstd, int dt, void* ws, size_t wsb,
                       hipStream_t s) {
-  if (C % 8 || N < 1 || S < 1) { set_error("c8_instnorm_stats: bad shape"); return NC_ERR_SHAPE; }
+  if (C % 8 || N < 1 || S < 1 || !grid_y_ok((long)N * (C / 8))) { set_error("c8_instnorm_stats: bad shape (C % 8, N * C / 8 <= 65535)"); return NC_ERR_SHAPE; }
   if (!ws || wsb < c8_stats_ws_bytes(N, C, S)) { set_error("c8_instnorm_stats: workspace too small"); return NC_ERR_WS; }
   const int sp = splits_for(S);
   double* part = (double*)ws;
 #define CALL(D) hipLaunchKernelGGL((k_stats_c8<D>), dim3(sp, N * C / 8), dim3(256), 0, s, (const uint4*)x, S, sp, part)
   DISPATCH_DT(dt, CALL);
 #undef CALL
-  hipLaunchKernelGGL(k_stats_final_c8, dim3((unsigned)(N * C / 8)), dim3(64), 0, s, part, N * C, sp, S, eps, mean, rstd);
+#define CALL(D) hipLaunchKernelGGL((k_stats_final_c8<D>), dim3((unsigned)(N * C / 8)), dim3(64), 0, s, part, (const uint4*)x, N * C, sp, S, eps, mean, rstd)
+  DISPATCH_DT(dt, CALL);
+#undef CALL
   return check_launch("c8_instnorm_stats");
 }
 
 int c8_instnorm_apply(const void* x, const float* mean, const float* rstd, float slope, void* y, int ctot, int c0, int N, int C,
                       long S, int dt, hipStream_t s) {
-  if (C % 8 || ctot % 8 || c0 % 8 || c0 + C > ctot) { set_error("c8_instnorm_apply: bad channel range"); return NC_ERR_SHAPE; }
+  if (C % 8 || ctot % 8 || c0 % 8 || c0 < 0 || c0 + C > ctot) { set_error("c8_instnorm_apply: bad channel range"); return NC_ERR_SHAPE; }
+  if (N < 1 || S < 1 || !grid_y_ok((long)N * (C / 8))) { set_error("c8_instnorm_apply: bad shape (N * C / 8 <= 65535)"); return NC_ERR_SHAPE; }
 #define CALL(D) hipLaunchKernelGGL((k_apply_c8<D>), dim3((unsigned)cdiv(S, 256), N * C / 8), dim3(256), 0, s, (const uint4*)x, mean, rstd, slope, (uint4*)y, C / 8, S, ctot / 8, c0 / 8)
   DISPATCH_DT(dt, CALL);
 #undef CALL
@@ -451,7 +468,8 @@ int c8_instnorm_apply(const void* x, const float* mean, const float* rstd, float
 // g: gradient (bf16) in channels [gc0, ..) of a gctot buffer; x: raw conv output (dt); dx: dense bf16; dbias nullable
 int c8_instnorm_bwd(const void* g, int gctot, int gc0, const void* x, const float* mean, const float* rstd, float slope, void* dx,
                     float* dbias, int N, int C, long S, int dt, void* ws, size_t wsb, hipStream_t s) {
-  if (C % 8 || gctot % 8 || gc0 % 8 || gc0 + C > gctot) { set_error("c8_instnorm_bwd: bad channel range"); return NC_ERR_SHAPE; }
+  if (C % 8 || gctot % 8 || gc0 % 8 || gc0 < 0 || gc0 + C > gctot) { set_error("c8_instnorm_bwd: bad channel range"); return NC_ERR_SHAPE; }
+  if (N < 1 || S < 1 || !grid_y_ok((long)N * (C / 8))) { set_error("c8_instnorm_bwd: bad shape (N * C / 8 <= 65535)"); return NC_ERR_SHAPE; }
   if (!ws || wsb < c8_stats_ws_bytes(N, C, S)) { set_error("c8_instnorm_bwd: workspace too small"); return NC_ERR_WS; }
   const int sp = splits_for(S);
   double* part = (double*)ws;
@@ -472,7 +490,10 @@ int c8_instnorm_bwd(const void* g, int gctot, int gc0, const void* x, const floa
 }
 
 int c8_maxpool_fwd(const void* x, int ctot, int c0, void* y, int N, int C, int D, int H, int W, int dt, hipStream_t s) {
-  if (C % 8 || ctot % 8 || c0 % 8 || c0 + C > ctot || (D & 1) || (H & 1) || (W & 1)) { set_error("c8_maxpool_fwd: bad shape"); return NC_ERR_SHAPE; }
+  if (C % 8 || ctot % 8 || c0 % 8 || c0 < 0 || c0 + C > ctot || D < 2 || H < 2 || W < 2 || (D & 1) || (H & 1) || (W & 1) || N < 1 || !grid_y_ok((long)N * (C / 8))) {
+    set_error("c8_maxpool_fwd: bad shape (C % 8, even dims, N * C / 8 <= 65535)");
+    return NC_ERR_SHAPE;
+  }
   const long So = (long)(D / 2) * (H / 2) * (W / 2);
 #define CALL(T) hipLaunchKernelGGL((k_pool_c8<T>), dim3((unsigned)cdiv(So, 256), N * C / 8), dim3(256), 0, s, (const uint4*)x, ctot / 8, c0 / 8, (uint4*)y, C / 8, D, H, W)
   DISPATCH_DT(dt, CALL);
@@ -482,8 +503,9 @@ int c8_maxpool_fwd(const void* x, int ctot, int c0, void* y, int N, int C, int D
 
 int c8_maxpool_bwd_add(const void* dp, const void* x, int ctot, int c0, const void* skip, int sctot, int sc0, void* dx, int N, int C,
                        int D, int H, int W, int dt, hipStream_t s) {
-  if (C % 8 || ctot % 8 || c0 % 8 || c0 + C > ctot || sctot % 8 || sc0 % 8 || sc0 + C > sctot || (D & 1) || (H & 1) || (W & 1)) {
-    set_error("c8_maxpool_bwd_add: bad shape");
+  if (C % 8 || ctot % 8 || c0 % 8 || c0 < 0 || c0 + C > ctot || sctot % 8 || sc0 % 8 || sc0 < 0 || sc0 + C > sctot || D < 2 || H < 2 || W < 2 || (D & 1) ||
+      (H & 1) || (W & 1) || N < 1 || !grid_y_ok((long)N * (C / 8))) {
+    set_error("c8_maxpool_bwd_add: bad shape (C % 8, even dims, N * C / 8 <= 65535)");
     return NC_ERR_SHAPE;
   }
   const long So = (long)(D / 2) * (H / 2) * (W / 2);
@@ -494,7 +516,8 @@ int c8_maxpool_bwd_add(const void* dp, const void* x, int ctot, int c0, const vo
 }
 
 int c8_to_f32(const void* x, int ctot, int c0, float* y, int N, int C, long S, int dt, hipStream_t s) {
-  if (C % 8 || ctot % 8 || c0 % 8 || c0 + C > ctot) { set_error("c8_to_f32: bad channel range"); return NC_ERR_SHAPE; }
+  if (C % 8 || ctot % 8 || c0 % 8 || c0 < 0 || c0 + C > ctot) { set_error("c8_to_f32: bad channel range"); return NC_ERR_SHAPE; }
+  if (N < 1 || S < 1 || !grid_y_ok((long)N * (C / 8))) { set_error("c8_to_f32: bad shape (N * C / 8 <= 65535)"); return NC_ERR_SHAPE; }
 #define CALL(T) hipLaunchKernelGGL((k_from_c8<T>), dim3((unsigned)cdiv(S, 256), N * C / 8), dim3(256), 0, s, (const uint4*)x, ctot / 8, c0 / 8, y, C / 8, S)
   DISPATCH_DT(dt, CALL);
 #undef CALL
@@ -502,6 +525,7 @@ int c8_to_f32(const void* x, int ctot, int c0, float* y, int N, int C, long S, i
 }
 
 int c8_dot64(const void* x, const float* w, const float* bias, float* out, int N, long S, int dt, hipStream_t s) {
+  if (S < 1 || !grid_y_ok(N)) { set_error("c8_dot64: bad shape (1 <= N <= 65535)"); return NC_ERR_SHAPE; }
 #define CALL(T) hipLaunchKernelGGL((k_dot64_c8<T>), dim3((unsigned)cdiv(S, 256), N), dim3(256), 0, s, (const uint4*)x, w, bias, out, S)
   DISPATCH_DT(dt, CALL);
 #undef CALL
@@ -513,6 +537,7 @@ size_t c8_outer64_ws_bytes(int N, long S) { return (size_t)N * cdiv(S, 256 * 16)
 // dx (nullable) = w (x) g in bf16 C8; dw[64] = sum g x; db (nullable) = sum g
 int c8_outer64(const float* g, const void* x, const float* w, void* dx, float* dw, float* db, int N, long S, int dt, void* ws,
                size_t wsb, hipStream_t s) {
+  if (S < 1 || !grid_y_ok(N)) { set_error("c8_outer64: bad shape (1 <= N <= 65535)"); return NC_ERR_SHAPE; }
   if (!ws || wsb < c8_outer64_ws_bytes(N, S)) { set_error("c8_outer64: workspace too small"); return NC_ERR_WS; }
   const long nbx = cdiv(S, 256 * 16);
   double* part = (double*)ws;

@@ -30,8 +30,8 @@ def test_one_prototype_per_declared_name():
     protos = _lib.prototypes()
     assert sorted(protos) == _lib.header_symbols()
     assert len(VOID) == 15 and {n for n, (ret, _) in protos.items() if ret is None} == VOID
-    # the rule the binding applied to the names before: sizes in bytes or floats, and one offset
-    by_name = {n for n in protos if n.endswith('_bytes') or n.endswith('_floats') or n == 'nc_h2_cells_offset'}
+    # the rule the binding applied to the names before: sizes in bytes or floats (a test export: ..._bytes_debug), and one offset
+    by_name = {n for n in protos if n.endswith('_bytes') or n.endswith('_bytes_debug') or n.endswith('_floats') or n == 'nc_h2_cells_offset'}
     assert {n for n, (ret, _) in protos.items() if ret is ctypes.c_size_t} == by_name
     assert [n for n, (ret, _) in protos.items() if ret is ctypes.c_char_p] == ['nc_last_error']
     assert all(ret in (ctypes.c_int, ctypes.c_size_t, ctypes.c_char_p, None) for ret, _ in protos.values())
