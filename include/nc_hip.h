@@ -755,6 +755,19 @@ int nc_convT_k2s2_fwd_s3_debug(const float* x, const float* w, const float* bias
  * channels and S voxels (more channels: NC_ERR_SHAPE); w2, b1, b2 point at one float each. */
 int nc_instnorm_relu_tail_sigmoid_debug(const float* x, const float* mean, const float* rstd, const float* w1, const float* b1, const float* w2,
                                         const float* b2, float* y, int C, long S, void* stream);
+/* Test exports of the boundary pieces of deep_linear_gen's position-typed path (csrc/dl_typed.hip and csrc/dl_bnd.hip, whose kernels do the
+ * same arithmetic in the same order; tests/test_gpu_dl_bnd.py compares the two bit by bit).  piece: 0 = the forward's boundary voxels (io = y
+ * [N][1][D][H][W]: boundary voxels overwritten, the others untouched; dy may be NULL), 1 = dL/dact0's boundary terms (io = g [N][64][D][H][W],
+ * added to), 2 = the boundary types' sums (io = Pq [64][32][125], overwritten; the interior's correlation dWsw taken as zero).  variant: 0 =
+ * dl_typed.hip's kernels, 1 = dl_bnd.hip's (NC_ERR_SHAPE where it has none for the piece and the shape), -1 = what the whole-network calls take:
+ * nc_dl_bnd_variant_debug's answer.  F: the 27 composed 5^3 kernels [27][64][125]; act0: [N][64][D][H][W]; dy: [N][1][D][H][W]; scratch:
+ * nc_dl_typed_scratch_bytes_debug bytes (0: the typed form does not take the shape), the layout of dl_typed.hip's dl_typed_plan.  The call runs
+ * the composition of the typed kernels, the transposed copies and the one piece on `stream`; a bad piece or variant, a null pointer
+ * (NC_ERR_ARG), an uncovered shape (NC_ERR_SHAPE) or a short scratch (NC_ERR_WS) is refused before anything is written. */
+size_t nc_dl_typed_scratch_bytes_debug(int N, int D, int H, int W);
+int nc_dl_bnd_variant_debug(int piece, int N, int D, int H, int W);
+int nc_dl_bnd_piece_debug(int piece, const float* F, const float* act0, const float* dy, float* io, void* scratch, size_t scratch_bytes, int N, int D,
+                          int H, int W, int variant, void* stream);
 
 /* ---- Learned-PSF generators (--netG_B linearkernel / linearkernel_double / linearkernel_LK31): LinearKernel and LinearKernel_double at
  *      models/networks.py:840-871, one bias-free Conv3d(1, 1, k, stride 1, padding (k - 1) / 2) -- applied twice with one weight in the

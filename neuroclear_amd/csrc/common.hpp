@@ -287,9 +287,15 @@ size_t dl_typed_bytes(int N, int D, int H, int W);
 const float* dl_typed_wp(const char* scratch, int N, int D, int H, int W);
 float* dl_typed_dwsw(char* scratch, int N, int D, int H, int W);
 int dl_typed_compose(const float* F, char* scratch, int N, int D, int H, int W, hipStream_t s);
+// variant (dL/dact0 and the type sums): 0 = dl_typed.hip's boundary kernels, 1 = dl_bnd.hip's (same arithmetic in the same order), -1 = dl_bnd.hip's where dl_bnd_variant says so
 int dl_typed_fwd_boundary(const float* act0, float* y, char* scratch, int N, int D, int H, int W, hipStream_t s);
-int dl_typed_dgrad_boundary(const float* act0, const float* dy, float* g, char* scratch, int N, int D, int H, int W, hipStream_t s);
-int dl_typed_p(const float* act0, const float* dy, float* Pq, char* scratch, int N, int D, int H, int W, hipStream_t s);
+int dl_typed_gather(const float* act0, const float* dy, char* scratch, int N, int D, int H, int W, hipStream_t s);
+int dl_typed_dgrad_boundary(const float* act0, const float* dy, float* g, char* scratch, int N, int D, int H, int W, hipStream_t s, int variant = -1);
+int dl_typed_p(const float* act0, const float* dy, float* Pq, char* scratch, int N, int D, int H, int W, hipStream_t s, int variant = -1);
+// dl_bnd.hip: piece 0 = forward, 1 = dL/dact0, 2 = type sums -> 1 where it has kernels for the piece and the shape, else 0
+int dl_bnd_variant(int piece, int N, int D, int H, int W);
+int dl_bnd_dgrad(const float* dy, const float* dyX, const float* Hd, float* g, int N, int D, int H, int W, hipStream_t s);
+int dl_bnd_wgrad_rows(const float* act0, const float* dy, float* partA, int N, int D, int H, int W, int nrows, hipStream_t s);
 int conv_c1k7_h2_dgrad(const float* dy, const float* w, float* dx, const ConvDims& d, void* ws, size_t wsb, hipStream_t s);
 // h2.hip: the H2 operand form (two fp16 terms of the tensor times a power of two taken from a cell)
 // an H2 tensor of `elems` elements = elems * 4 bytes of units + (at this byte offset) 256 bytes of cells: [0] the cell of the channels' first

@@ -497,25 +497,40 @@ int dl_typed_fwd_boundary(const float* act0, float* y, char* scratch, int N, int
 }
 // the backward's boundary pieces: g (= dL/dact0 from the interior kernel) += the boundary voxels' difference kernels, and Pq (the rank form's P,
 // k_dl_q_from_p's layout) from dWsw (the swapped-role 7^3 correlation of dy and act0, already in the scratch) and the boundary types' sums
-int dl_typed_dgrad_boundary(const float* act0, const float* dy, float* g, char* scratch, int N, int D, int H, int W, hipStream_t s) {
+// variant (here and in dl_typed_p): 0 = the kernels of this file, 1 = dl_bnd.hip's, -1 = dl_bnd.hip's where it has them
+int dl_typed_gather(const float* act0, const float* dy, char* scratch, int N, int D, int H, int W, hipStream_t s) {
   const DlTyped t = dl_typed_plan(N, D, H, W);
   float* AX = (float*)(scratch + t.AX);
   float* dyX = (float*)(scratch + t.dyX);
   hipLaunchKernelGGL(k_dl_gather_x, dim3((unsigned)D, kC, (unsigned)(N * 2)), dim3(128), 0, s, act0, AX, dy, dyX, D, H, W);  // (AX: for dl_typed_p below)
-  hipLaunchKernelGGL(k_dl_bnd_dgrad<false>, dim3((unsigned)(D * H), (unsigned)cdiv(W, 64), (unsigned)N), dim3(256), 0, s, dy, (const float*)(scratch + t.Hd), g, D, H, W, 1);
-  const int nseg = (int)cdiv(H, 64);
-  hipLaunchKernelGGL(k_dl_bnd_dgrad<true>, dim3((unsigned)D, 2, (unsigned)(N * nseg)), dim3(256), 0, s, (const float*)dyX, (const float*)(scratch + t.Hd), g, D, H, W, nseg);
+  return check_launch("deep_linear: typed path, transposed copies");
+}
+int dl_typed_dgrad_boundary(const float* act0, const float* dy, float* g, char* scratch, int N, int D, int H, int W, hipStream_t s, int variant) {
+  const DlTyped t = dl_typed_plan(N, D, H, W);
+  float* dyX = (float*)(scratch + t.dyX);
+  NC_TRY(dl_typed_gather(act0, dy, scratch, N, D, H, W, s));
+  if (variant < 0 ? dl_bnd_variant(1, N, D, H, W) == 1 : variant == 1) {
+    NC_TRY(dl_bnd_dgrad(dy, dyX, (const float*)(scratch + t.Hd), g, N, D, H, W, s));
+  } else {
+    hipLaunchKernelGGL(k_dl_bnd_dgrad<false>, dim3((unsigned)(D * H), (unsigned)cdiv(W, 64), (unsigned)N), dim3(256), 0, s, dy, (const float*)(scratch + t.Hd), g, D, H, W, 1);
+    const int nseg = (int)cdiv(H, 64);
+    hipLaunchKernelGGL(k_dl_bnd_dgrad<true>, dim3((unsigned)D, 2, (unsigned)(N * nseg)), dim3(256), 0, s, (const float*)dyX, (const float*)(scratch + t.Hd), g, D, H, W, nseg);
+  }
   hipLaunchKernelGGL(k_dl_bnd_dgrad_ends, dim3((unsigned)D, 4, (unsigned)N), dim3(256), 0, s, (const float*)dyX, (const float*)(scratch + t.Hd), g, D, H, W);
   return check_launch("deep_linear: typed data gradient, boundary");
 }
 // Pq (the rank form's P, k_dl_q_from_p's layout) from dWsw (the swapped-role 7^3 correlation of dy and act0, already in the scratch) and the boundary
 // types' sums (computed here: needs act0 and dy)
-int dl_typed_p(const float* act0, const float* dy, float* Pq, char* scratch, int N, int D, int H, int W, hipStream_t s) {  // (after dl_typed_dgrad_boundary: AX, dyX)
+int dl_typed_p(const float* act0, const float* dy, float* Pq, char* scratch, int N, int D, int H, int W, hipStream_t s, int variant) {  // (after dl_typed_dgrad_boundary: AX, dyX)
   const DlTyped t = dl_typed_plan(N, D, H, W);
   const float* AX = (const float*)(scratch + t.AX);
   const float* dyX = (const float*)(scratch + t.dyX);
   const size_t lds = (size_t)(64 * kPitch + 192) * 4;
-  hipLaunchKernelGGL(k_dl_bnd_wgrad<false>, dim3((unsigned)t.nrows, 7, (unsigned)N), dim3(448), lds, s, act0, dy, (float*)(scratch + t.partA), D, H, W, t.nrows);
+  if (variant < 0 ? dl_bnd_variant(2, N, D, H, W) == 1 : variant == 1) {
+    NC_TRY(dl_bnd_wgrad_rows(act0, dy, (float*)(scratch + t.partA), N, D, H, W, t.nrows, s));
+  } else {
+    hipLaunchKernelGGL(k_dl_bnd_wgrad<false>, dim3((unsigned)t.nrows, 7, (unsigned)N), dim3(448), lds, s, act0, dy, (float*)(scratch + t.partA), D, H, W, t.nrows);
+  }
   hipLaunchKernelGGL(k_dl_bnd_wgrad<true>, dim3((unsigned)(2 * D), 7, (unsigned)N), dim3(448), lds, s, AX, dyX, (float*)(scratch + t.partB), D, H, W, t.nrows);
   hipLaunchKernelGGL(k_dl_bnd_reduce, dim3((unsigned)cdiv((long)kD7 * kC, 256), kT), dim3(256), 0, s, (const float*)(scratch + t.partA), (const float*)(scratch + t.partB),
                      (float*)(scratch + t.dHb), N, D, H, W, t.nrows);
