@@ -391,6 +391,9 @@ int nc_unet_deconv_fwd(const float* params, const float* x, float* y, int N, int
 size_t nc_unet_deconv_param_floats(void);
 size_t nc_unet_deconv_saved_floats(int N, int S0, int S1, int S2);
 size_t nc_unet_deconv_train_ws_bytes(int N, int S0, int S1, int S2);
+/* The `kept` word nc_unet_deconv_train_fwd would return for this shape under the switches of now (the forward's plan, gen_nets.hip u_fwd_forms);
+ * launches nothing.  0: an edge is not a positive multiple of 4. */
+unsigned nc_unet_deconv_kept_expected(int N, int S0, int S1, int S2);
 /* `kept` (HOST word, out, may be NULL): bit i set = the forward left the three-term (S3) copy of layer i's input in `saved`; hand the
  * same word to the backward that reads this `saved` buffer (0 is always valid: the backward then converts the inputs again).  The
  * word travels with the caller's record of the forward (the autograd context), there is no library-side table.

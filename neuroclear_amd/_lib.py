@@ -23,7 +23,7 @@ L_ = ctypes.c_long
 F = ctypes.c_float
 Z = ctypes.c_size_t
 
-_RET = {'int': I, 'size_t': Z, 'void': None, 'const char*': ctypes.c_char_p}
+_RET = {'int': I, 'size_t': Z, 'unsigned': ctypes.c_uint, 'void': None, 'const char*': ctypes.c_char_p}
 _ARG = {'int': I, 'long': L_, 'size_t': Z, 'unsigned': ctypes.c_uint, 'float': F, 'double': ctypes.c_double}
 
 

@@ -19,60 +19,59 @@ using namespace nc;
 
 namespace {
 
-// Which S3 (three-term) copies of convolution inputs a training forward left in its `saved` buffer is a bit mask (bit i = layer i) that
-// the forward RETURNS to the caller (`kept`, a host word) and the caller hands to the backward of the same `saved` buffer: the
-// forward of a layer that runs on the split-operand kernels converts its input INTO the saved buffer (conv_fwd_keep) and the backward
-// gives that tensor to the weight gradient instead of converting x again.  The decision (library switch, shape coverage) is host
-// state, so the mask is host data; it travels with the autograd context that owns `saved`, not with a table keyed by its address.
-size_t s3_floats(size_t elems) { return up64((elems * 6 + 3) / 4); }
+// `kept`: what a training forward left in (or out of) its `saved` buffer.  A host word that the forward RETURNS and the caller hands to the backward
+// of the same buffer: every decision behind it (library switches, shape coverage) is host state, so the word travels with the autograd context
+// that owns `saved`, not with a table keyed by its address.  The backward decides from these bits, never from the switches of forward time.
+// Unet_deconv: u_fwd_forms composes the word and u_bwd_forms reads it.  DeepLinearGenerator: the operand bits and its own flags (kKeptCollapsed ..).
+struct Kept {
+  unsigned w = 0;
+  // bit i (1 .. 9): layer i's input in split-operand form is in saved (xs3[i]) -- its weight gradient takes that instead of converting x again
+  bool operand(int i) const { return bit(i); }
+  // bit 16 + i: that copy is a two-term (H2) tensor -- a backward under another setting of nc_set_split_terms ignores it
+  bool operand_h2(int i) const { return bit(16 + i); }
+  // ... so the kept copy is usable now: it exists, in the form the layer has under the switches of this call
+  bool operand_usable(int i, bool now_h2) const { return operand(i) && operand_h2(i) == now_h2; }
+  // bits 10 .. 14 (nc_set_unet_lean): the fp32 input of block 1 / 3 / 5 / 6 / 8 (a1, a2, b1, b2, e2a) was not written -- only that block's H2 operand
+  bool lean_input(int consumer) const { return lean_bit(consumer) && bit(lean_bit(consumer)); }
+  // bit 15 (nc_set_unet_wprep; w_prep.hip): cells and packed weights of the two-term blocks, forward AND data-gradient form, are in saved
+  // (UPlan::wprep), from one batched pass at the forward's start -- the data gradients see the weights of FORWARD time
+  bool wprep() const { return bit(15); }
+  // bit 26 (the only bit nc_set_in_bwd_fold moves; norm_act.hip PoolGrad): one winner byte per pooled element of both max-pools is in saved (UPlan::parg)
+  bool pool_arg() const { return bit(26); }
+  // bit 27: e1 (block 9's output) was not written -- one_by_one ran on the two flat 1 x 1 kernels (conv_1x1.hip), which normalise raw[9] as they read
+  bool lean_e1() const { return bit(27); }
+  // bits 28, 29: the fp32 upper half of cat1 / cat2 was not written -- the transposed convolution wrote the H2 half of block 9 / 7's operand alone
+  bool lean_up(int level) const { return bit(27 + level); }
+  // bits 30, 31: block 1 / 3 normalises, converts and POOLS in one pass (h2.hip k_act_split2h_pool) -- the fp32 lower half of cat1 / cat2 was not
+  // written IF pool_arg() too: the pass is taken when the forward writes winner bytes, and only then
+  bool lean_lo(int level) const { return bit(29 + level); }
+  bool has(unsigned flags) const { return (w & flags) == flags; }  // (the deep-linear flags below)
 
-// ---- Unet_deconv ---------------------------------------------------------------------------------------------------
-// The LEAN forms of the two-term training step (nc_set_unet_lean, default on): fp32 tensors that only a fallback path reads are not written.
-//   forward   a1, a2, b1, b2, e2a (block outputs that feed neither a pool nor a concat) exist only as the H2 operand of the block behind
-//             them; `kept` bit 10 + j records that tensor j of that list was not written.  A backward that cannot use the kept H2 copy (the
-//             terms switch moved, the shape left the split kernels) or whose range guard may switch to the three-term kernels inside the call
-//             (nc_set_h2_guard(2)) first writes the tensor again from raw / mean / rstd into its own scratch.
-//             e1 (block 9's output) is not written when one_by_one runs on the two flat 1 x 1 kernels (conv_1x1.hip): they take raw[9] / mean /
-//             rstd and normalise the operand as they read it, in the forward and in the weight gradient (`kept` bit 27).
-//             The two halves of cat1 and cat2 exist only as the H2 operand of block 9 / 7: the transposed convolutions write no fp32 output
-//             (bits 28, 29), and blocks 1 and 3 normalise, convert and POOL in one pass (h2.hip k_act_split2h_pool<true>) that leaves p1 / p2 and
-//             the winner bytes but no full-resolution fp32 (bits 30, 31 TOGETHER WITH bit 26: only when the forward writes winner bytes,
-//             nc_set_in_bwd_fold -- that switch moves bit 26 alone).
-//             A backward that needs one of these tensors after all -- block 9 / 7 without the kept H2 copy or under a range guard that may
-//             switch, a pool whose backward is not folded into the norm backward, one_by_one off the flat kernels -- writes it again first, with
-//             the bits the full forward stores: the lower half of a concat buffer by nc_instnorm_act_fwd, the upper half by the transposed
-//             convolution's forward with its fp32 output alone (both into the tensor's own slot of `saved`), e1 into scratch.
-//   backward  the gradient at block 9's output is w12[c] * s2[v]: the InstanceNorm backward forms it from the one-channel s2 (norm_act.hip,
-//             the rank-one form) -- no 64-channel data gradient of one_by_one is written or read.
-// Every lean form applies to a block in the two-term form only; with three terms, the split kernels off or NC_S3_TRAIN_FUSE=0 the calls launch
-// what they launched before.  The backward decides from the `kept` bits, not from the switch.
-constexpr unsigned kLeanE1 = 1u << 27;            // e1 was not written
-constexpr unsigned kLeanUp1 = 1u << 28, kLeanUp2 = 1u << 29;  // the fp32 upper half of cat1 / cat2 (the transposed convolution's output) was not written
-// bits 30, 31: block 1 / 3 is in the form that pools in its normalisation pass -- the fp32 lower half of cat1 / cat2 was not written IF the winner
-// bytes exist too (bit 26, the only bit nc_set_in_bwd_fold moves: the pass is taken when the forward writes winner bytes, and only then)
-constexpr unsigned kLeanLo1 = 1u << 30, kLeanLo2 = 1u << 31;
-constexpr int kLeanBit0 = 10;                     // kept bits 10 .. 14
-constexpr int kLeanBlocks[5] = {1, 3, 5, 6, 8};   // the blocks whose fp32 input the lean forward leaves out (a1, a2, b1, b2, e2a)
-int lean_index(int consumer) {
-  for (int j = 0; j < 5; ++j) if (kLeanBlocks[j] == consumer) return j;
-  return -1;
+  void set_operand(int i, bool h2) { put(i); if (h2) put(16 + i); }
+  void set_lean_input(int consumer) { if (lean_bit(consumer)) put(lean_bit(consumer)); }
+  void set_wprep() { put(15); }
+  void set_pool_arg() { put(26); }
+  void set_lean_e1() { put(27); }
+  void set_lean_up(int level) { put(27 + level); }
+  void set_lean_lo(int level) { put(29 + level); }
+  void set(unsigned flags) { w |= flags; }
+
+ private:
+  bool bit(int b) const { return (w >> b) & 1; }
+  void put(int b) { w |= 1u << b; }
+  static int lean_bit(int c) { return c == 1 ? 10 : c == 3 ? 11 : c == 5 ? 12 : c == 6 ? 13 : c == 8 ? 14 : 0; }  // 0: not a lean input
+};
+
+size_t s3_floats(size_t elems) { return up64((elems * 6 + 3) / 4); }
+// are the layer's operands in the two-term form under the switches of now (nc_set_split_terms(2); conv_split.hip s3_layer_h2)?
+bool layer_h2_now(int N, int C, const int* d, int K, int k) {
+  ConvDims cd;
+  return make_dims(cd, N, C, d[0], d[1], d[2], K, k, k, k, 1, k / 2) && conv_layer_h2(cd);
 }
 
-// PREPARED WEIGHTS of the two-term training step (nc_set_unet_wprep, default on; w_prep.hip): the forward computes the weight cells and the packed
-// weights of blocks 1 .. 9, forward AND data-gradient form, in one batched pass at its start and keeps them in `saved` (UPlan::wprep); every
-// two-term convolution of the forward and of the backward then launches alone.  `kept` bit 15 records that the packs exist; the backward uses a
-// block's data-gradient pack when the block's form is still the forward's (kept bit 16 + i against the terms switch now, the test its kept H2
-// operand gets).  The data gradients therefore see the weights of FORWARD time -- autograd's semantics; the weight tensors are not read again
-// for them.  Blocks 7 and 9 take a concatenation: their forward packs fold in the ratio of the two halves' cells, the InstanceNorm bound and the
-// transposed convolution's output bound (convt_s3.hip), which the pass computes from the weights as well; with NC_CONVT_H2=0 that half's cell is
-// measured, and those two forward packs stay with the per-layer launches.
-constexpr unsigned kKeptWPrep = 1u << 15;
-// THE WINNER BYTES of the two max-pools (nc_set_in_bwd_fold, default on; norm_act.hip PoolGrad): the forward's pool kernel also writes one byte per
-// pooled element, the index of its window's winner, into `saved` (UPlan::parg); `kept` bit 26 records that they exist.  The backward of blocks 1
-// and 3 then forms the gradient at the block's output -- skip half of the concat gradient + the pool's backward -- inside its InstanceNorm
-// backward, and nc_maxpool2_bwd_add with its 64- / 128-channel tensor is not launched.
-constexpr unsigned kKeptPoolArg = 1u << 26;
-// segment 2 (i - 1) + form of block i (form 0: forward, 1: data gradient); all 18 have their place in the region whichever of them a call prepares
+// ---- Unet_deconv ---------------------------------------------------------------------------------------------------
+// segment 2 (i - 1) + form of block i's prepared weights (form 0: forward, 1: data gradient); all 18 have their place in the region whichever of
+// them a call prepares
 void wprep_segs(WPrepSeg (&sg)[18]) {
   for (int i = 1; i < 10; ++i) {
     sg[2 * (i - 1)] = WPrepSeg{nullptr, kUB[i].C, kUB[i].K, 0, 0u, -1, nullptr};
@@ -81,15 +80,14 @@ void wprep_segs(WPrepSeg (&sg)[18]) {
 }
 unsigned f32_bits(float f) { unsigned b; __builtin_memcpy(&b, &f, 4); return b; }
 
-
 struct UPlan {
   int N, d[3][3];      // spatial size per level
   long S[3];           // voxels per level
   // saved (floats): activations, raw conv outputs, statistics
   size_t a1, cat1, p1, a2, cat2, p2, b1, b2, b3, e2a, e2b, e1, t1, raw[10], mean[10], rstd[10], saved;
-  size_t xs3[10];      // S3 copy of block i's input (i >= 1), see `kept`
-  size_t wprep;        // the prepared weights (w_prep.hip wprep_run's region), see kKeptWPrep
-  size_t parg[2];      // the winner bytes of pool 1 (behind block 1) and pool 2 (behind block 3), see kKeptPoolArg
+  size_t xs3[10];      // the split-operand copy of block i's input (i >= 1), see Kept::operand
+  size_t wprep;        // the prepared weights (w_prep.hip wprep_run's region), see Kept::wprep
+  size_t parg[2];      // the winner bytes of pool 1 (behind block 1) and pool 2 (behind block 3), see Kept::pool_arg
   // backward scratch (floats)
   size_t G1, G2, G3, H1, H2, H3, Q1, Q2, s1, s2, T, grads;
   size_t conv_ws, in_ws, convT_ws;  // bytes
@@ -159,6 +157,131 @@ size_t u_ws_bytes(const UPlan& p, bool bwd) {
   return align256(p.conv_ws) + align256(p.in_ws) + align256(p.convT_ws) + (bwd ? p.grads * sizeof(float) : 0) + 256;
 }
 
+// The two skip levels.  Level L (1, 2): block `lo` writes the lower K channels of the concat buffer `cat` (resolution level L - 1) and is pooled into
+// `pooled`; transposed convolution `tw` (parameter id) takes `tin` (2 K channels, level L) to the upper K channels; block `cons` reads the concat.
+struct ULevel { int lo, cons, tw, K; size_t UPlan::*cat, UPlan::*pooled, UPlan::*tin; };
+constexpr ULevel kUL[3] = {{}, {1, 9, 11, 64, &UPlan::cat1, &UPlan::p1, &UPlan::e2b}, {3, 7, 10, 128, &UPlan::cat2, &UPlan::p2, &UPlan::b3}};
+
+// EVERY FORM OF THE FORWARD, decided before its first launch (all of it host state).  The forward reads these fields and launches.
+// use: the block runs forward and weight gradient on the split-operand kernels, NC_S3_TRAIN_FUSE on: its input is wanted in operand form.  pre: the
+//   PRODUCER of that input (the block in front's normalisation pass, the transposed convolution) writes it straight into xs3[i]; a block behind a
+//   max-pool (2, 4), or any block with the fusion off, converts inside conv_fwd_keep.
+// lean (nc_set_unet_lean): fp32 tensors that only a fallback path reads are not written -- behind two-term blocks only.  Kept says which.
+enum CtArm { kCtPlain, kCtSplit, kCtH2, kCtS3 };
+struct UFwdForms {
+  bool use[10], h2l[10], pre[10];  // h2l: the block's operands in the two-term form
+  bool epi[10];                    // the convolution's epilogue leaves the partial InstanceNorm sums (nc_set_epi_stats(2); conv_s3x.hip ST)
+  ConvDims cd[10];
+  // the transposed convolution of level L: ct on the bf16 matrix cores from an S3 copy of its input (convt_s3.hip; the layer-by-layer path makes
+  // the same choice), cth writing the H2 half of the consumer's operand itself, its power of two from a BOUND -- nothing measured (NC_CONVT_H2=0:
+  // fp32 output, measured and converted); ct_s3 writing the three-term half itself.  Level 1 alone has an arm for that without ct (convT_fwd_s3).
+  bool ct[3], cth[3], ct_s3[3];
+  bool bound[3];         // the prepared-weights pass leaves cth's bound in the consumer's second cell
+  bool lean, pool_arg;   // pool_arg: the pools also write their winner bytes
+  bool pool_in_norm[3];  // block lo of level L normalises, converts and pools in one pass: no full-resolution fp32, no pool launch
+  bool tail_flat;        // no e1: block 9 stops at its statistics and one_by_one's flat kernel normalises raw[9] as it reads it
+  bool seg[18];          // the prepared-weight segments of this call (wprep_segs' numbering)
+  Kept kept;
+  CtArm arm(int L) const { return cth[L] ? kCtH2 : ct[L] ? kCtSplit : ct_s3[L] ? kCtS3 : kCtPlain; }
+};
+
+UFwdForms u_fwd_forms(const UPlan& p) {
+  UFwdForms f{};
+  const int N = p.N;
+  const bool fuse_on = sw::raw(sw::S3_TRAIN_FUSE) != 0, ct_h2 = sw::raw(sw::CONVT_H2) != 0, wprep = sw::raw(sw::UNET_WPREP) != 0;
+  const bool epi_on = sw::raw(sw::EPI_STATS) == 2;  // an option, not the default (no measurable gain in the training step)
+  f.lean = sw::raw(sw::UNET_LEAN) != 0;
+  f.pool_arg = sw::get(sw::IN_BWD_FOLD) != 0;
+  if (f.pool_arg) f.kept.set_pool_arg();
+  for (int i = 0; i < 10; ++i) {
+    const UBlock& b = kUB[i];
+    const int* d = p.d[b.lvl];
+    const bool keep = i >= 1 && conv_keep_supported(N, b.C, d[0], d[1], d[2], b.K, 3);  // (conv_fwd_keep's *kept)
+    const bool h2 = make_dims(f.cd[i], N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && keep && conv_layer_h2(f.cd[i]);
+    f.use[i] = fuse_on && keep;
+    f.h2l[i] = f.use[i] && h2;
+    f.pre[i] = f.use[i] && i != 2 && i != 4;
+    const size_t sb = f.pre[i] && f.h2l[i] && epi_on ? s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) : 0;
+    f.epi[i] = sb && sb <= p.in_ws;
+    if (keep) f.kept.set_operand(i, h2);
+    if (f.lean && f.h2l[i]) f.kept.set_lean_input(i);  // (the block in front writes no fp32 output: the backward takes the H2 copy)
+    if (wprep && f.h2l[i]) { f.seg[2 * (i - 1)] = f.seg[2 * (i - 1) + 1] = true; f.kept.set_wprep(); }
+  }
+  for (int L = 1; L <= 2; ++L) {
+    const ULevel& u = kUL[L];
+    const int* d = p.d[L];
+    f.ct[L] = nc_convT_k2s2_split_active(1, 2 * u.K, d[0], d[1], d[2], u.K) &&
+              p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 2 * u.K, d[0], d[1], d[2], u.K);
+    f.cth[L] = f.ct[L] && f.h2l[u.cons] && ct_h2;
+    f.ct_s3[L] = f.use[u.cons] && !f.h2l[u.cons] && (f.ct[L] || (L == 1 && convT_fwd_s3_supported(1, 2 * u.K, d[0], d[1], d[2], u.K)));
+    f.bound[L] = wprep && f.cth[L];
+    if (f.seg[2 * (u.cons - 1)] && !f.cth[L]) f.seg[2 * (u.cons - 1)] = false;  // (a measured second cell: that forward pack stays per-layer)
+    f.pool_in_norm[L] = f.pool_arg && f.lean && f.h2l[u.cons];
+    if (f.lean && f.h2l[u.cons]) f.kept.set_lean_lo(L);
+    if (f.lean && f.cth[L]) f.kept.set_lean_up(L);  // (the H2 half is all block 9 / 7 reads of the transposed convolution's output)
+  }
+  f.tail_flat = f.lean && norm_1x1_taken(N, 64, p.d[0][0], p.d[0][1], p.d[0][2], 1);
+  if (f.tail_flat) f.kept.set_lean_e1();
+  return f;
+}
+
+// EVERY FORM OF THE BACKWARD, decided at its top from `kept`, the switches of NOW and the shape.  A tensor the lean forward left out is written
+// again wherever this backward reads it after all, with the bits the full forward stores: a block's fp32 input (rewrite_in: the block in front's
+// normalisation + ReLU, into scratch) unless the block leaves it alone (input_unread); the halves of the concat buffers (rebuild_lo / rebuild_up,
+// into their own slots of `saved`: the lower half is block 1 / 3's normalisation + ReLU, the upper half the transposed convolution's forward
+// again with its fp32 output alone) for block 9 / 7's weight gradient without the kept H2 copy and, the lower half, for a pool backward outside
+// the norm backward; e1 (rebuild_e1, into scratch) for one_by_one off the flat kernels.
+enum NormBwd { kNormFp32, kNormS3, kNormH2, kNormH2Pool, kNormRank1 };
+struct UBwdForms {
+  bool now_h2[10];        // the block is in the two-term form now
+  bool xs[10];            // its kept operand is usable (Kept::operand_usable)
+  bool pack[10];          // its data gradient takes the pack the forward prepared: same test, and nc_set_unet_wprep still on
+  bool input_unread[10];  // its backward leaves its fp32 input alone: the kept copy AND the split weight gradient AND a range guard that cannot
+                          // switch inside this call (a flagged call builds its three-term x operand from the fp32 tensor, conv_split.hip run_ws_h2)
+  bool rewrite_in[10];
+  // the InstanceNorm backward.  S3 / H2: it writes the convolution's dY straight in operand form at the head of the convolution workspace -- no fp32
+  // tensor, no conversion pass.  H2Pool (blocks 1, 3): it also takes skip half + pool backward from the winner bytes, and nc_maxpool2_bwd_add
+  // with its 64- / 128-channel tensor is not launched.  Rank1 (block 9, one sample): it forms w12[c] * s2[v] from the one-channel s2 -- no
+  // 64-channel data gradient of one_by_one is written or read.  Fp32: the fallback, then conv_bwd_keep.
+  NormBwd norm[10];
+  bool dy_guarded[10];    // the range guard may rewrite that dY as three terms inside the call
+  bool tail_flat, rebuild_e1, rebuild_lo[3], rebuild_up[3];
+  bool pool_folds(int L) const { return norm[kUL[L].lo] == kNormH2Pool; }
+  bool r1() const { return norm[9] == kNormRank1; }
+};
+
+UBwdForms u_bwd_forms(const UPlan& p, Kept k, bool want_dx0) {
+  UBwdForms f{};
+  const int N = p.N;
+  const bool fuse = sw::raw(sw::S3_TRAIN_FUSE) != 0, wprep_now = sw::raw(sw::UNET_WPREP) != 0, lean_now = sw::raw(sw::UNET_LEAN) != 0;
+  const bool flip = h2_guard_can_flip();
+  for (int i = 0; i < 10; ++i) {
+    const UBlock& b = kUB[i];
+    const int* d = p.d[b.lvl];
+    const bool pre_ok = conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, i >= 1 || want_dx0, p.conv_ws);
+    f.now_h2[i] = layer_h2_now(N, b.C, d, b.K, 3);
+    f.xs[i] = k.operand_usable(i, f.now_h2[i]);
+    f.pack[i] = i >= 1 && f.now_h2[i] && k.wprep() && k.operand_h2(i) && wprep_now;
+    f.input_unread[i] = f.xs[i] && !flip && pre_ok;
+    f.rewrite_in[i] = k.lean_input(i) && !f.input_unread[i];
+    f.norm[i] = !(fuse && i >= 1 && pre_ok && instnorm_bwd_s3_supported(N, b.K, p.S[b.lvl])) ? kNormFp32 : f.now_h2[i] ? kNormH2 : kNormS3;
+    f.dy_guarded[i] = f.now_h2[i] && flip;
+  }
+  if (lean_now && N == 1 && f.norm[9] == kNormH2) f.norm[9] = kNormRank1;  // (dW12 / db12 stay with the matrix kernel: their summation order is part of the step)
+  for (int L = 1; L <= 2; ++L) {
+    const ULevel& u = kUL[L];
+    const int* d = p.d[L - 1];
+    unsigned guard;  // (block_bwd always passes the guard's words: only their presence counts here)
+    if (k.pool_arg() && f.norm[u.lo] == kNormH2 && instnorm_bwd_h2_pool_supported(N, u.K, d[0], d[1], d[2], &guard)) f.norm[u.lo] = kNormH2Pool;
+    const bool cat_read = !f.input_unread[u.cons];
+    f.rebuild_lo[L] = k.lean_lo(L) && k.pool_arg() && (cat_read || f.norm[u.lo] != kNormH2Pool);
+    f.rebuild_up[L] = k.lean_up(L) && cat_read;
+  }
+  f.tail_flat = k.lean_e1() && norm_1x1_taken(N, 64, p.d[0][0], p.d[0][1], p.d[0][2], 1);
+  f.rebuild_e1 = k.lean_e1() && !f.tail_flat;
+  return f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -203,6 +326,12 @@ size_t nc_unet_deconv_train_ws_bytes(int N, int S0, int S1, int S2) {
   return u_plan(p, N, S0, S1, S2) ? u_ws_bytes(p, true) : 0;
 }
 
+unsigned nc_unet_deconv_kept_expected(int N, int S0, int S1, int S2) {
+  NetworkScope net_scope;
+  UPlan p;
+  return u_plan(p, N, S0, S1, S2) ? u_fwd_forms(p).kept.w : 0;
+}
+
 int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, float* saved, int N, int S0, int S1, int S2,
                              void* ws, size_t ws_bytes, void* stream, unsigned* kept) {
   NetworkScope net_scope;
@@ -213,6 +342,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
     return NC_ERR_SHAPE;
   }
   if (!ws || ws_bytes < u_ws_bytes(p, false)) { set_error("unet_deconv_train_fwd: workspace too small"); return NC_ERR_WS; }
+  const UFwdForms f = u_fwd_forms(p);
   const UOff o = u_offsets();
   void* cws = ws;
   void* iws = (char*)ws + align256(p.conv_ws);
@@ -220,117 +350,63 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   const float* P = params;
   if (kept) *kept = 0;
   hipStream_t hs = (hipStream_t)stream;
-  // Which blocks run on the split-operand kernels (forward and weight gradient)?  Their input is wanted in S3 form, and the producer of
-  // that input -- the normalisation + ReLU pass of the block in front, or the conversion of a transposed convolution's output -- writes
-  // the S3 form straight into the consumer's slot of `saved` (xs3[i]) instead of a separate conversion pass over the fp32 tensor
-  // (k_act_split3; a block fed by a max-pool still converts inside conv_fwd_keep).  NC_S3_TRAIN_FUSE=0: every block converts for itself.
-  const bool fuse_on = sw::raw(sw::S3_TRAIN_FUSE) != 0;
-  const bool lean = sw::raw(sw::UNET_LEAN) != 0;
-  bool use[10], pre[10], h2l[10];  // h2l: the block's operands in the two-term form (nc_set_split_terms(2); conv_split.hip s3_layer_h2)
-  ConvDims cd[10];
-  for (int i = 0; i < 10; ++i) {
-    const UBlock& b = kUB[i];
-    const int* d = p.d[b.lvl];
-    use[i] = fuse_on && i >= 1 && conv_keep_supported(N, b.C, d[0], d[1], d[2], b.K, 3);
-    pre[i] = false;
-    h2l[i] = make_dims(cd[i], N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && use[i] && conv_layer_h2(cd[i]);
-  }
-  const long S = p.S[0], Sh = p.S[1], Sq = p.S[2];
-  const int *d0 = p.d[0], *d1 = p.d[1], *d2 = p.d[2];
-  // The transposed convolutions run on the bf16 matrix cores from an S3 copy of their input (convt_s3.hip; the fp32 input stays in
-  // `saved` for their backward) whenever the split-operand kernels are on (the layer-by-layer host path makes the same choice:
-  // nc_convT_k2s2_split_active), and write the S3 form of their half of the concatenation themselves when the consuming block takes it
-  const bool ct2 = nc_convT_k2s2_split_active(1, 256, d2[0], d2[1], d2[2], 128) &&
-                   p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 256, d2[0], d2[1], d2[2], 128);
-  // Two-term form: the transposed convolution writes the H2 form of its half itself -- its power of two comes from a BOUND (one tap per input
-  // channel and output voxel: max column sum of |w| times the InstanceNorm bound of its input, convt_s3.hip), so nothing is measured and the
-  // whole forward is independent of what else is in the batch.  NC_CONVT_H2=0: fp32 output, measured and converted.
-  const bool ct_h2 = sw::raw(sw::CONVT_H2) != 0;
-  const bool ct2h = ct2 && h2l[7] && ct_h2;
-  const bool ct1 = nc_convT_k2s2_split_active(1, 128, d1[0], d1[1], d1[2], 64) &&
-                   p.conv_ws >= nc_convT_k2s2_split_ws_bytes(1, 128, d1[0], d1[1], d1[2], 64);
-  const bool ct1h = ct1 && h2l[9] && ct_h2;
-  unsigned* cell7 = h2_cells_of(V + p.xs3[7], (size_t)N * 256 * Sh) + 1;
-  unsigned* cell9 = h2_cells_of(V + p.xs3[9], (size_t)N * 128 * S) + 1;
-  unsigned kept_mask = 0;
-  const bool pool_arg = sw::get(sw::IN_BWD_FOLD) != 0;  // (the pools also leave their winner bytes, see kKeptPoolArg)
-  // the prepared weights (see kKeptWPrep): every two-term block's cells and packs, both forms, before the first convolution
+  const long S = p.S[0];
+  const int* d0 = p.d[0];
+  // the second cell of block 9 / 7's H2 operand: the upper half's, written by level 1 / 2's transposed convolution
+  unsigned* cell[3] = {nullptr, h2_cells_of(V + p.xs3[9], (size_t)N * 128 * S) + 1, h2_cells_of(V + p.xs3[7], (size_t)N * 256 * p.S[1]) + 1};
+  // the prepared weights (Kept::wprep): every two-term block's cells and packs, both forms, before the first convolution
   S3xPrepared prep[18] = {};
-  bool bound7 = false, bound9 = false;  // the pass set cell7 / cell9
-  if (sw::raw(sw::UNET_WPREP)) {
+  if (f.kept.wprep()) {
     WPrepSeg sg[18];
     wprep_segs(sg);
     WPrepBound wb[2];
-    int nb = 0, any = 0;
+    int nb = 0;  // (bounds are numbered in block order)
     for (int i = 1; i < 10; ++i) {
-      if (!h2l[i]) continue;
-      WPrepSeg& f = sg[2 * (i - 1)];
+      if (!f.seg[2 * (i - 1) + 1]) continue;
+      WPrepSeg& fw = sg[2 * (i - 1)];
       // the input's first cell: the InstanceNorm bound of its level (h2.hip act_split2h) -- or, behind a max-pool, a measured cell that both
       // halves share: the ratio is 1 whatever the value
-      f.a_bits = f32_bits(sqrtf((float)p.S[kUB[i].lvl]));
-      f.w = P + o.w[i];
-      if (i == 7 || i == 9) {
-        if (i == 7 ? ct2h : ct1h) {
-          f.b_cell = kWPrepBoundCell0 + nb;
-          f.ext_cell = i == 7 ? cell7 : cell9;
-          wb[nb++] = i == 7 ? WPrepBound{P + o.w[10], P + o.b[10], 256, 128, sqrtf((float)Sq), 0}
-                            : WPrepBound{P + o.w[11], P + o.b[11], 128, 64, sqrtf((float)Sh), 0};
-          (i == 7 ? bound7 : bound9) = true;
-        } else {
-          f.w = nullptr;  // (a measured second cell: the per-layer launches)
-        }
+      fw.a_bits = f32_bits(sqrtf((float)p.S[kUB[i].lvl]));
+      if (f.seg[2 * (i - 1)]) fw.w = P + o.w[i];
+      const int L = i == 7 ? 2 : i == 9 ? 1 : 0;
+      if (L && f.bound[L]) {
+        fw.b_cell = kWPrepBoundCell0 + nb;
+        fw.ext_cell = cell[L];
+        wb[nb++] = WPrepBound{P + o.w[kUL[L].tw], P + o.b[kUL[L].tw], 2 * kUL[L].K, kUL[L].K, sqrtf((float)p.S[L]), 0};
       }
       sg[2 * (i - 1) + 1].w = P + o.w[i];
-      any = 1;
     }
-    if (any) {
-      NC_TRY(wprep_run(sg, 18, wb, nb, V + p.wprep, prep, hs));
-      kept_mask |= kKeptWPrep;
-    }
+    NC_TRY(wprep_run(sg, 18, wb, nb, V + p.wprep, prep, hs));
   }
-  auto prep_of = [&](int seg) -> const S3xPrepared* { return prep[seg].wp ? &prep[seg] : nullptr; };
   // conv (3^3, pad 1) -> raw; statistics; normalise + ReLU into `out`, where sample n's K planes start at
   // out + n * out_stride (out_stride = K * S for a dense tensor, Ctot * S for a half of a concat buffer).
-  // to >= 0: block `to` consumes this output as channels [0, K) of its `to_ctot`-channel input
-  auto block = [&](int i, const float* in, float* out, size_t out_stride, int to, int to_ctot, float* pooled = nullptr,
-                   unsigned char* parg = nullptr) -> int {
+  // to >= 0: block `to` consumes this output as channels [0, K) of its `to_ctot`-channel input; to == -2: the consumer normalises for itself.
+  // skip = L: the block is level L's `lo`, a max-pool follows
+  auto block = [&](int i, const float* in, float* out, size_t out_stride, int to, int to_ctot, int skip = 0) -> int {
     const UBlock& b = kUB[i];
     const int* d = p.d[b.lvl];
     const long S = p.S[b.lvl];
-    // Two-term form with the input already converted by its producer (a power of two known by construction: nothing can fall back): the
-    // convolution's epilogue can leave the partial InstanceNorm sums (conv_s3x.hip ST) instead of a statistics pass over its output --
-    // nc_set_epi_stats(2): an option, not the default (no measurable gain in the training step)
-    const bool epi = pre[i] && h2l[i] && sw::raw(sw::EPI_STATS) == 2 && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) && s3x_stats_bytes(N, d[0], d[1], d[2], b.K, 3) <= p.in_ws;
-    if (pre[i]) {  // the producers left the S3 input in saved
+    const S3xPrepared* pw = i >= 1 && prep[2 * (i - 1)].wp ? &prep[2 * (i - 1)] : nullptr;
+    if (f.pre[i]) {  // the producers left the operand form of the input in saved
       NC_TRY(conv_fwd_pre(V + p.xs3[i], P + o.w[i], P + o.b[i], V + p.raw[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream,
-                          epi ? (float*)iws : nullptr, i >= 1 ? prep_of(2 * (i - 1)) : nullptr));
-      kept_mask |= 1u << i;
-      if (h2l[i]) kept_mask |= 1u << (16 + i);  // (bits 16..: the kept copy is an H2 tensor -- a backward under another setting of the switch ignores it)
+                          f.epi[i] ? (float*)iws : nullptr, pw));
     } else {
       bool kept1 = false;
       NC_TRY(conv_fwd_keep(in, P + o.w[i], P + o.b[i], V + p.raw[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream,
-                           i >= 1 ? (void*)(V + p.xs3[i]) : nullptr, &kept1, i >= 1 ? prep_of(2 * (i - 1)) : nullptr));
-      if (kept1) kept_mask |= 1u << i;
-      if (kept1 && i >= 1 && conv_layer_h2(cd[i])) kept_mask |= 1u << (16 + i);
+                           i >= 1 ? (void*)(V + p.xs3[i]) : nullptr, &kept1, pw));
+      if (kept1 != f.kept.operand(i)) { set_error("unet_deconv_train_fwd: block %d %s its converted input, against the plan", i, kept1 ? "kept" : "did not keep"); return NC_ERR_ARG; }
     }
-    if (epi) NC_TRY(s3x_stats_finalize((const float*)iws, P + o.b[i], N, d[0], d[1], d[2], b.K, 3, 1e-5f, V + p.mean[i], V + p.rstd[i], hs));
+    if (f.epi[i]) NC_TRY(s3x_stats_finalize((const float*)iws, P + o.b[i], N, d[0], d[1], d[2], b.K, 3, 1e-5f, V + p.mean[i], V + p.rstd[i], hs));
     else NC_TRY(nc_instnorm_stats(V + p.raw[i], N * b.K, S, 1e-5f, V + p.mean[i], V + p.rstd[i], iws, p.in_ws, stream));
-    // lean, blocks 1 and 3 (the lower half of a concat input, and a max-pool behind them): the H2 half, the fp32 POOLED tensor and the winner bytes in
-    // one pass -- no full-resolution fp32, and no pool launch (`pooled` / `parg` non-null: the caller's pool)
-    if (to >= 0 && lean && h2l[to] && to_ctot == 2 * b.K && pooled) kept_mask |= i == 1 ? kLeanLo1 : kLeanLo2;
-    if (pool_arg && (kept_mask & (i == 1 ? kLeanLo1 : kLeanLo2)) && pooled) {
-      return act_split2h_pool_arg(V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, V + p.xs3[to], pooled, parg, N, b.K, d[0], d[1], d[2], to_ctot, 0,
-                                  sqrtf((float)S), h2_cells_of(V + p.xs3[to], (size_t)N * to_ctot * S), hs);  // (act_operand's cell and bound)
+    if (skip && f.pool_in_norm[skip])  // the H2 half, the fp32 POOLED tensor and the winner bytes in one pass (act_operand's cell and bound)
+      return act_split2h_pool_arg(V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, V + p.xs3[to], V + p.*kUL[skip].pooled,
+                                  (unsigned char*)(V + p.parg[skip - 1]), N, b.K, d[0], d[1], d[2], to_ctot, 0, sqrtf((float)S),
+                                  h2_cells_of(V + p.xs3[to], (size_t)N * to_ctot * S), hs);
+    if (to >= 0 && f.use[to]) {  // fp32 (the backward of the pool / the fallback paths read it) AND the consumer's operand in one pass
+      if (f.kept.lean_input(to)) out = nullptr;  // (its only regular reader is the two-term block behind it)
+      return act_operand(f.cd[to], V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, out, (long)out_stride, V + p.xs3[to], N, b.K, S, to_ctot, 0, hs);
     }
-    if (to >= 0 && use[to]) {  // fp32 (the backward of the pool / the fallback paths read it) AND the consumer's S3 operand in one pass
-      // lean: a tensor whose only regular reader is the two-term block behind it stays unwritten (the backward takes the H2 copy)
-      const int lj = lean && h2l[to] && to_ctot == b.K ? lean_index(to) : -1;
-      if (lj >= 0) { out = nullptr; kept_mask |= 1u << (kLeanBit0 + lj); }
-      NC_TRY(act_operand(cd[to], V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, out, (long)out_stride, V + p.xs3[to], N, b.K, S, to_ctot, 0, hs));
-      if (to_ctot == b.K) pre[to] = true;  // (a concat input is complete once its second half has been converted, below)
-      return NC_OK;
-    }
-    if (to == -2) return NC_OK;  // (the consumer normalises for itself: the lean tail)
+    if (to == -2) return NC_OK;
     if (out_stride == (size_t)b.K * S || N == 1)
       return nc_instnorm_act_fwd(V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, out, N * b.K, S, stream);
     for (int n = 0; n < N; ++n)
@@ -338,81 +414,64 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
                                  out + n * out_stride, b.K, S, stream));
     return NC_OK;
   };
+  // level L's max-pool, unless its block pooled in its normalisation pass
+  auto pool = [&](int L) -> int {
+    const ULevel& u = kUL[L];
+    const int* d = p.d[L - 1];
+    const long Sc = p.S[L - 1], Sp = p.S[L];
+    for (int n = 0; n < N && !f.pool_in_norm[L]; ++n) {
+      const float* src = V + p.*u.cat + (size_t)n * 2 * u.K * Sc;
+      float* dst = V + p.*u.pooled + (size_t)n * u.K * Sp;
+      if (f.pool_arg) NC_TRY(maxpool2_fwd_arg(src, dst, (unsigned char*)(V + p.parg[L - 1]) + (size_t)n * u.K * Sp, u.K, d[0], d[1], d[2], hs));
+      else NC_TRY(nc_maxpool2_fwd(src, dst, u.K, d[0], d[1], d[2], stream));
+    }
+    return NC_OK;
+  };
+  // level L's transposed convolution writes the second half of the concat buffer, on the plan's arm, and the consumer's operand is completed (its
+  // first half came from block lo's normalisation pass).  A half in the two-term form that the arm did not write (kCtSplit under NC_CONVT_H2=0) is
+  // measured after the fact: its power of two cannot be known while it is written.
+  auto t_conv = [&](int L) -> int {
+    const ULevel& u = kUL[L];
+    const int C = 2 * u.K, *d = p.d[L];
+    const long Si = p.S[L], So = p.S[L - 1];
+    const float *w = P + o.w[u.tw], *bias = P + o.b[u.tw];
+    const CtArm arm = f.arm(L);
+    if (arm == kCtH2 && !f.bound[L]) {  // (the prepared pass leaves the bound in the cell itself)
+      NC_TRY(h2_zero_cells(cell[L], 1, hs));
+      NC_TRY(convT_h2_bound(w, bias, C, u.K, sqrtf((float)Si), cell[L], hs));
+    }
+    for (int n = 0; n < N; ++n) {
+      const float* tin = V + p.*u.tin + (size_t)n * C * Si;
+      float* half = V + p.*u.cat + ((size_t)n * C + u.K) * So;
+      char* xs = (char*)(V + p.xs3[u.cons]) + (size_t)n * C * So * (arm == kCtH2 ? 4 : 6);
+      if (arm == kCtH2)
+        NC_TRY(convT_fwd_split_h2(tin, w, bias, f.kept.lean_up(L) ? nullptr : half, xs, C, u.K, 1, C, d[0], d[1], d[2], u.K, cell[L], cws, p.conv_ws, hs));
+      else if (arm == kCtSplit)
+        NC_TRY(nc_convT_k2s2_fwd_split(tin, nullptr, w, bias, half, f.ct_s3[L] ? xs : nullptr, C, u.K, 1, C, d[0], d[1], d[2], u.K, cws, p.conv_ws, stream));
+      else if (arm == kCtS3)  // (level 1 only: u_fwd_forms)
+        NC_TRY(convT_fwd_s3(tin, w, bias, half, xs, C, u.K, 1, C, d[0], d[1], d[2], u.K, stream));
+      else
+        NC_TRY(nc_convT_k2s2_fwd(tin, w, bias, half, 1, C, d[0], d[1], d[2], u.K, stream));
+    }
+    if (f.use[u.cons] && !f.ct_s3[L] && arm != kCtH2)
+      NC_TRY(operand_into(f.cd[u.cons], V + p.*u.cat + (size_t)u.K * So, (long)C * So, V + p.xs3[u.cons], N, u.K, So, C, u.K, hs));
+    return NC_OK;
+  };
   NC_TRY(block(0, x, V + p.a1, (size_t)64 * S, 1, 64));
-  NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128, V + p.p1, (unsigned char*)(V + p.parg[0])));
-  if (pool_arg) kept_mask |= kKeptPoolArg;
-  for (int n = 0; n < N && !(pool_arg && (kept_mask & kLeanLo1)); ++n) {
-    if (pool_arg)
-      NC_TRY(maxpool2_fwd_arg(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, (unsigned char*)(V + p.parg[0]) + (size_t)n * 64 * Sh, 64,
-                              d0[0], d0[1], d0[2], hs));
-    else
-      NC_TRY(nc_maxpool2_fwd(V + p.cat1 + (size_t)n * 128 * S, V + p.p1 + (size_t)n * 64 * Sh, 64, d0[0], d0[1], d0[2], stream));
-  }
-  NC_TRY(block(2, V + p.p1, V + p.a2, (size_t)128 * Sh, 3, 128));
-  NC_TRY(block(3, V + p.a2, V + p.cat2, (size_t)256 * Sh, 7, 256, V + p.p2, (unsigned char*)(V + p.parg[1])));
-  for (int n = 0; n < N && !(pool_arg && (kept_mask & kLeanLo2)); ++n) {
-    if (pool_arg)
-      NC_TRY(maxpool2_fwd_arg(V + p.cat2 + (size_t)n * 256 * Sh, V + p.p2 + (size_t)n * 128 * Sq, (unsigned char*)(V + p.parg[1]) + (size_t)n * 128 * Sq,
-                              128, d1[0], d1[1], d1[2], hs));
-    else
-      NC_TRY(nc_maxpool2_fwd(V + p.cat2 + (size_t)n * 256 * Sh, V + p.p2 + (size_t)n * 128 * Sq, 128, d1[0], d1[1], d1[2], stream));
-  }
-  NC_TRY(block(4, V + p.p2, V + p.b1, (size_t)256 * Sq, 5, 256));
-  NC_TRY(block(5, V + p.b1, V + p.b2, (size_t)256 * Sq, 6, 256));
-  NC_TRY(block(6, V + p.b2, V + p.b3, (size_t)256 * Sq, -1, 0));
-  if (ct2h && !bound7) {  // (the prepared pass leaves the bound in cell7 itself)
-    NC_TRY(h2_zero_cells(cell7, 1, hs));
-    NC_TRY(convT_h2_bound(P + o.w[10], P + o.b[10], 256, 128, sqrtf((float)Sq), cell7, hs));
-  }
-  // lean: the H2 half is all block 7 / 9 read of a transposed convolution's output (ct2h / ct1h: the consumer is two-term) -- no fp32 half
-  if (lean && ct2h) kept_mask |= kLeanUp2;
-  if (lean && ct1h) kept_mask |= kLeanUp1;
-  for (int n = 0; n < N; ++n) {  // t_conv2 writes the second half of cat2
-    if (ct2h)
-      NC_TRY(convT_fwd_split_h2(V + p.b3 + (size_t)n * 256 * Sq, P + o.w[10], P + o.b[10], lean ? nullptr : V + p.cat2 + ((size_t)n * 256 + 128) * Sh,
-                                (char*)(V + p.xs3[7]) + (size_t)n * 256 * Sh * 4, 256, 128, 1, 256, d2[0], d2[1], d2[2], 128, cell7, cws, p.conv_ws, hs));
-    else if (ct2)
-      NC_TRY(nc_convT_k2s2_fwd_split(V + p.b3 + (size_t)n * 256 * Sq, nullptr, P + o.w[10], P + o.b[10], V + p.cat2 + ((size_t)n * 256 + 128) * Sh,
-                                     use[7] && !h2l[7] ? (char*)(V + p.xs3[7]) + (size_t)n * 256 * Sh * 6 : nullptr, 256, 128, 1, 256, d2[0], d2[1], d2[2], 128, cws,
-                                     p.conv_ws, stream));
-    else
-      NC_TRY(nc_convT_k2s2_fwd(V + p.b3 + (size_t)n * 256 * Sq, P + o.w[10], P + o.b[10], V + p.cat2 + ((size_t)n * 256 + 128) * Sh,
-                               1, 256, d2[0], d2[1], d2[2], 128, stream));
-  }
-  if (use[7]) {  // ... and its S3 form completes block 7's input (the first half came from block 3's normalisation pass)
-    // (two-term form: the transposed convolution's half is measured after the fact -- its power of two cannot be known while it is written)
-    if (!ct2 || (h2l[7] && !ct2h)) NC_TRY(operand_into(cd[7], V + p.cat2 + (size_t)128 * Sh, (long)256 * Sh, V + p.xs3[7], N, 128, Sh, 256, 128, hs));
-    pre[7] = true;
-  }
-  NC_TRY(block(7, V + p.cat2, V + p.e2a, (size_t)128 * Sh, 8, 128));
-  NC_TRY(block(8, V + p.e2a, V + p.e2b, (size_t)128 * Sh, -1, 0));
-  const bool ct_s3 = use[9] && !h2l[9] && (ct1 || convT_fwd_s3_supported(1, 128, d1[0], d1[1], d1[2], 64));  // t_conv1 writes the S3 form of its output itself
-  if (ct1h && !bound9) {
-    NC_TRY(h2_zero_cells(cell9, 1, hs));
-    NC_TRY(convT_h2_bound(P + o.w[11], P + o.b[11], 128, 64, sqrtf((float)Sh), cell9, hs));
-  }
-  for (int n = 0; n < N; ++n) {  // t_conv1 writes the second half of cat1
-    if (ct1h)
-      NC_TRY(convT_fwd_split_h2(V + p.e2b + (size_t)n * 128 * Sh, P + o.w[11], P + o.b[11], lean ? nullptr : V + p.cat1 + ((size_t)n * 128 + 64) * S,
-                                (char*)(V + p.xs3[9]) + (size_t)n * 128 * S * 4, 128, 64, 1, 128, d1[0], d1[1], d1[2], 64, cell9, cws, p.conv_ws, hs));
-    else if (ct1)
-      NC_TRY(nc_convT_k2s2_fwd_split(V + p.e2b + (size_t)n * 128 * Sh, nullptr, P + o.w[11], P + o.b[11], V + p.cat1 + ((size_t)n * 128 + 64) * S,
-                                     use[9] && !h2l[9] ? (char*)(V + p.xs3[9]) + (size_t)n * 128 * S * 6 : nullptr, 128, 64, 1, 128, d1[0], d1[1], d1[2], 64, cws,
-                                     p.conv_ws, stream));
-    else if (ct_s3)
-      NC_TRY(convT_fwd_s3(V + p.e2b + (size_t)n * 128 * Sh, P + o.w[11], P + o.b[11], V + p.cat1 + ((size_t)n * 128 + 64) * S,
-                          (char*)(V + p.xs3[9]) + (size_t)n * 128 * S * 6, 128, 64, 1, 128, d1[0], d1[1], d1[2], 64, stream));
-    else
-      NC_TRY(nc_convT_k2s2_fwd(V + p.e2b + (size_t)n * 128 * Sh, P + o.w[11], P + o.b[11], V + p.cat1 + ((size_t)n * 128 + 64) * S,
-                               1, 128, d1[0], d1[1], d1[2], 64, stream));
-  }
-  if (use[9]) {
-    if (!ct_s3 && !ct1h) NC_TRY(operand_into(cd[9], V + p.cat1 + (size_t)64 * S, (long)128 * S, V + p.xs3[9], N, 64, S, 128, 64, hs));
-    pre[9] = true;
-  }
-  // the 1x1 tail.  lean, one_by_one on the flat kernels: no e1 -- block 9 stops at its statistics and the kernel normalises raw[9] as it reads it
-  if (lean && norm_1x1_taken(N, 64, d0[0], d0[1], d0[2], 1)) {
-    kept_mask |= kLeanE1;
+  NC_TRY(block(1, V + p.a1, V + p.cat1, (size_t)128 * S, 9, 128, 1));
+  NC_TRY(pool(1));
+  NC_TRY(block(2, V + p.p1, V + p.a2, (size_t)128 * p.S[1], 3, 128));
+  NC_TRY(block(3, V + p.a2, V + p.cat2, (size_t)256 * p.S[1], 7, 256, 2));
+  NC_TRY(pool(2));
+  NC_TRY(block(4, V + p.p2, V + p.b1, (size_t)256 * p.S[2], 5, 256));
+  NC_TRY(block(5, V + p.b1, V + p.b2, (size_t)256 * p.S[2], 6, 256));
+  NC_TRY(block(6, V + p.b2, V + p.b3, (size_t)256 * p.S[2], -1, 0));
+  NC_TRY(t_conv(2));
+  NC_TRY(block(7, V + p.cat2, V + p.e2a, (size_t)128 * p.S[1], 8, 128));
+  NC_TRY(block(8, V + p.e2a, V + p.e2b, (size_t)128 * p.S[1], -1, 0));
+  NC_TRY(t_conv(1));
+  // the 1x1 tail
+  if (f.tail_flat) {
     NC_TRY(block(9, V + p.cat1, nullptr, (size_t)64 * S, -2, 0));
     NC_TRY(conv_fwd_norm_1x1(V + p.raw[9], V + p.mean[9], V + p.rstd[9], 0.f, P + o.w[12], P + o.b[12], V + p.t1, N, 64, d0[0], d0[1], d0[2], 1, cws,
                              p.conv_ws, stream));
@@ -422,7 +481,7 @@ int nc_unet_deconv_train_fwd(const float* params, const float* x, float* y, floa
   }
   // one_by_one_2 + sigmoid: y doubles as the buffer of the pre-sigmoid value (the sigmoid kernel is elementwise in place)
   NC_TRY(nc_conv_fwd(V + p.t1, P + o.w[13], P + o.b[13], y, N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
-  if (kept) *kept = kept_mask;
+  if (kept) *kept = f.kept.w;
   return nc_sigmoid_fwd(y, y, (long)N * S, stream);
 }
 
@@ -435,6 +494,7 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   UPlan p;
   if (!u_plan(p, N, S0, S1, S2)) { set_error("unet_deconv_bwd: bad shape"); return NC_ERR_SHAPE; }
   if (!ws || ws_bytes < u_ws_bytes(p, true)) { set_error("unet_deconv_bwd: workspace too small"); return NC_ERR_WS; }
+  const UBwdForms f = u_bwd_forms(p, Kept{kept}, dx != nullptr);
   const UOff o = u_offsets();
   hipStream_t hs = (hipStream_t)stream;
   void* cws = ws;
@@ -444,11 +504,8 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
   const float* V = saved;
   const float* P = params;
   float* DP = dparams;
-  const long S = p.S[0], Sh = p.S[1], Sq = p.S[2];
-  const int *d0 = p.d[0], *d1 = p.d[1], *d2 = p.d[2];
-  const unsigned kept_mask = kept;
-  const bool fuse_bwd = sw::raw(sw::S3_TRAIN_FUSE) != 0;
-  const bool wprep_now = sw::raw(sw::UNET_WPREP) != 0;
+  const long S = p.S[0];
+  const int* d0 = p.d[0];
   S3xPrepared prepd[10] = {};  // block i's data-gradient pack in `saved` (wprep_run's layout: cells, then the segments in order)
   {
     WPrepSeg sg[18];
@@ -460,167 +517,109 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
       off += s3x_packed_bytes(sg[k].Cin, sg[k].Kout, 3, 2);
     }
   }
-  // Does block i's backward leave its fp32 input alone?  Only with the kept copy in the form of now AND the split weight gradient AND a range guard
-  // that cannot switch inside this call: a flagged call builds its three-term x operand from the fp32 tensor (conv_split.hip run_ws_h2, "the
-  // flagged call").  A tensor the lean forward left out is written again in every other case.
-  auto input_unread = [&](int i, bool want_dx) -> bool {
-    const UBlock& b = kUB[i];
-    const int* d = p.d[b.lvl];
-    ConvDims cdk;
-    const bool now_h2 = make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk);
-    const bool have = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2;
-    return have && !h2_guard_can_flip() && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, want_dx, p.conv_ws);
-  };
   // backward of block i: g = gradient at the block's (post-ReLU) output, dense [N][K][S]; `in` = the block's input.
   // draw <- InstanceNorm/ReLU backward (+ the conv's bias gradient); dW <- wgrad; gin (nullable) <- dgrad
-  // pool (block_bwd, blocks 1 and 3 under pool_folds): g is the skip half of the concat gradient (sample stride 2 K Sl), pool the dense pooled
-  // gradient; the winner bytes are in `saved`
-  auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin, bool r1 = false, const float* pool = nullptr) -> int {
+  // kNormH2Pool: g is the skip half of the concat gradient (sample stride 2 K Sl), pool the dense pooled gradient; kNormRank1: g is the one-channel s2
+  auto block_bwd = [&](int i, const float* g, const float* in, float* draw, float* gin, const float* pool = nullptr) -> int {
     const UBlock& b = kUB[i];
     const int* d = p.d[b.lvl];
     const long Sl = p.S[b.lvl];
-    ConvDims cdk;
-    const bool now_h2 = make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk);
-    const void* xs = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2 ? (const void*)(V + p.xs3[i]) : nullptr;
-    // the data-gradient pack the forward prepared, under the same test (see kKeptWPrep); nc_set_unet_wprep(0) now: the per-layer launches
-    const S3xPrepared* pd = i >= 1 && gin && now_h2 && (kept_mask & kKeptWPrep) && ((kept_mask >> (16 + i)) & 1) && wprep_now ? &prepd[i] : nullptr;
-    // a lean forward did not write this block's fp32 input.  Unless the paths below leave `in` alone (input_unread) the tensor is written again
-    // (the block in front's normalisation + ReLU: the bits the full forward stores) into scratch no block's backward uses.
-    const int lj = lean_index(i);
-    if (lj >= 0 && ((kept_mask >> (kLeanBit0 + lj)) & 1) && !input_unread(i, gin != nullptr)) {
+    const void* xs = f.xs[i] ? (const void*)(V + p.xs3[i]) : nullptr;
+    if (f.rewrite_in[i]) {  // (into scratch no block's backward uses)
       NC_TRY(nc_instnorm_act_fwd(V + p.raw[i - 1], V + p.mean[i - 1], V + p.rstd[i - 1], 0.f, G + p.T, N * b.C, Sl, stream));
       in = G + p.T;
     }
-    if (r1) {  // (block 9, decided below: g is the one-channel s2)
-      NC_TRY(instnorm_act_bwd_dbias_h2_rank1(g, P + o.w[12], V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], b.K, Sl, iws, p.in_ws,
-                                             stream, conv_bwd_guard_words(cws, N, b.K, Sl)));
-      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, h2_guard_can_flip(), pd);
+    const float *raw = V + p.raw[i], *mean = V + p.mean[i], *rstd = V + p.rstd[i];
+    unsigned* gw = conv_bwd_guard_words(cws, N, b.K, Sl);  // (the norm backward counts, decides and -- flagged -- rewrites its dY as S3)
+    const NormBwd nf = f.norm[i];
+    if (nf == kNormFp32) {
+      NC_TRY(nc_instnorm_act_bwd_dbias(g, raw, mean, rstd, 0.f, draw, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream));
+      return conv_bwd_keep(in, xs, draw, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream);
     }
-    // the norm's backward writes the convolution's dY straight in S3 form at the head of the convolution workspace (where the
-    // conversion phase of the split-operand backward would put it): no fp32 tensor, no conversion pass
-    if (fuse_bwd && i >= 1 && conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, gin != nullptr, p.conv_ws) &&
-        instnorm_bwd_s3_supported(N, b.K, Sl)) {
-      if (now_h2 && pool)
-        NC_TRY(instnorm_act_bwd_dbias_h2_pool(g, (long)2 * b.K * Sl, pool, (const unsigned char*)(V + p.parg[i == 1 ? 0 : 1]), V + p.raw[i], V + p.mean[i],
-                                              V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, d[0], d[1], d[2], iws, p.in_ws, stream,
-                                              conv_bwd_guard_words(cws, N, b.K, Sl)));
-      else if (now_h2)  // (with the range guard's words of the dY operand: the norm backward counts, decides and -- flagged -- rewrites it as S3)
-        NC_TRY(instnorm_act_bwd_dbias_h2(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream,
-                                         conv_bwd_guard_words(cws, N, b.K, Sl)));
-      else
-        NC_TRY(instnorm_act_bwd_dbias_s3(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream));
-      return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, now_h2 && h2_guard_can_flip(), pd);
-    }
-    if (pool) { set_error("unet_deconv_bwd: block %d left the path its pooled gradient was planned for", i); return NC_ERR_ARG; }
-    NC_TRY(nc_instnorm_act_bwd_dbias(g, V + p.raw[i], V + p.mean[i], V + p.rstd[i], 0.f, draw, DP + o.b[i], N, b.K, Sl, iws,
-                                     p.in_ws, stream));
-    return conv_bwd_keep(in, xs, draw, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream);
+    if (nf == kNormRank1)
+      NC_TRY(instnorm_act_bwd_dbias_h2_rank1(g, P + o.w[12], raw, mean, rstd, 0.f, cws, DP + o.b[i], b.K, Sl, iws, p.in_ws, stream, gw));
+    else if (nf == kNormH2Pool)
+      NC_TRY(instnorm_act_bwd_dbias_h2_pool(g, (long)2 * b.K * Sl, pool, (const unsigned char*)(V + p.parg[i == 1 ? 0 : 1]), raw, mean, rstd, 0.f, cws,
+                                            DP + o.b[i], N, b.K, d[0], d[1], d[2], iws, p.in_ws, stream, gw));
+    else if (nf == kNormH2)
+      NC_TRY(instnorm_act_bwd_dbias_h2(g, raw, mean, rstd, 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream, gw));
+    else
+      NC_TRY(instnorm_act_bwd_dbias_s3(g, raw, mean, rstd, 0.f, cws, DP + o.b[i], N, b.K, Sl, iws, p.in_ws, stream));
+    return conv_bwd_pre(in, xs, P + o.w[i], gin, DP + o.w[i], N, b.C, d[0], d[1], d[2], b.K, 3, cws, p.conv_ws, stream, f.dy_guarded[i],
+                        f.pack[i] ? &prepd[i] : nullptr);
   };
-  // Does block i (1 or 3) take the pool's backward into its InstanceNorm backward?  block_bwd's own conditions for the two-term path with its dY
-  // written by the norm backward, the winner bytes, the switch, and a range guard that cannot switch kernels inside this call.
-  auto pool_folds = [&](int i) -> bool {
-    const UBlock& b = kUB[i];
-    const int* d = p.d[b.lvl];
-    ConvDims cdk;
-    return (kept_mask & kKeptPoolArg) && fuse_bwd && make_dims(cdk, N, b.C, d[0], d[1], d[2], b.K, 3, 3, 3, 1, 1) && conv_layer_h2(cdk) &&
-           conv_bwd_pre_supported(N, b.C, d[0], d[1], d[2], b.K, 3, true, p.conv_ws) &&
-           instnorm_bwd_h2_pool_supported(N, b.K, d[0], d[1], d[2], conv_bwd_guard_words(cws, N, b.K, p.S[b.lvl]));
+  // backward of level L's transposed convolution, from the gradient of the concat buffer's second half as a dense tensor (N == 1 needs no copy)
+  auto t_conv_bwd = [&](int L, const float* dcat, float* gin) -> int {
+    const ULevel& u = kUL[L];
+    const int* d = p.d[L];
+    const float* g = dcat + (size_t)u.K * p.S[L - 1];
+    if (N > 1) { NC_TRY(gather_half(dcat, G + p.T, N, 2 * u.K, u.K, u.K, p.S[L - 1], hs)); g = G + p.T; }
+    NC_TRY(nc_convT_k2s2_dgrad(g, P + o.w[u.tw], gin, N, 2 * u.K, d[0], d[1], d[2], u.K, tws, p.convT_ws, stream));
+    return nc_convT_k2s2_wgrad(V + p.*u.tin, g, DP + o.w[u.tw], DP + o.b[u.tw], N, 2 * u.K, d[0], d[1], d[2], u.K, tws, p.convT_ws, stream);
   };
-  // gradient of the second half of a concat buffer as a dense tensor
-  auto upper_half = [&](const float* dcat, int Ctot, long Sl, const float** out) -> int {
-    const int C = Ctot / 2;
-    if (N == 1) { *out = dcat + (size_t)C * Sl; return NC_OK; }
-    NC_TRY(gather_half(dcat, G + p.T, N, Ctot, C, C, Sl, hs));
-    *out = G + p.T;
+  // level L's halves of the concat buffer that a lean forward left out and this backward reads (UBwdForms), before anything of this call lives
+  // in the convolution workspace
+  auto rebuild = [&](int L) -> int {
+    const ULevel& u = kUL[L];
+    const int C = u.K, *td = p.d[L];
+    const long Sl = p.S[L - 1];
+    float* cat = const_cast<float*>(saved) + p.*u.cat;
+    for (int n = 0; n < N && f.rebuild_lo[L]; ++n)
+      NC_TRY(nc_instnorm_act_fwd(V + p.raw[u.lo] + (size_t)n * C * Sl, V + p.mean[u.lo] + n * C, V + p.rstd[u.lo] + n * C, 0.f,
+                                 cat + (size_t)n * 2 * C * Sl, C, Sl, stream));
+    for (int n = 0; n < N && f.rebuild_up[L]; ++n)
+      NC_TRY(convT_fwd_split_h2(V + p.*u.tin + (size_t)n * 2 * C * p.S[L], P + o.w[u.tw], P + o.b[u.tw], cat + ((size_t)n * 2 + 1) * C * Sl, nullptr, 2 * C,
+                                C, 1, 2 * C, td[0], td[1], td[2], C, nullptr, cws, p.conv_ws, hs));
     return NC_OK;
   };
-  // The halves of the concat buffers a lean forward left out (kept bits 28 .. 31), where this backward reads them after all: block 9 / 7's weight
-  // gradient without the kept H2 copy (both halves), a pool's backward outside the norm backward (the lower half, its source).  Written into
-  // their own slots of `saved` with the bits the full forward stores -- the lower half is block 1 / 3's normalisation + ReLU, the upper half the
-  // transposed convolution's forward again with its fp32 output alone -- before anything of this call lives in the convolution workspace.
-  {
-    float* Vw = const_cast<float*>(saved);
-    auto rebuild = [&](int lo_blk, size_t cat, int C, long Sl, bool lower, bool upper, const float* tin, int tw, const int* td) -> int {
-      for (int n = 0; n < N && lower; ++n)
-        NC_TRY(nc_instnorm_act_fwd(V + p.raw[lo_blk] + (size_t)n * C * Sl, V + p.mean[lo_blk] + n * C, V + p.rstd[lo_blk] + n * C, 0.f,
-                                   Vw + cat + (size_t)n * 2 * C * Sl, C, Sl, stream));
-      for (int n = 0; n < N && upper; ++n)
-        NC_TRY(convT_fwd_split_h2(tin + (size_t)n * 2 * C * (Sl / 8), P + o.w[tw], P + o.b[tw], Vw + cat + ((size_t)n * 2 + 1) * C * Sl, nullptr, 2 * C, C, 1,
-                                  2 * C, td[0], td[1], td[2], C, nullptr, cws, p.conv_ws, hs));
-      return NC_OK;
-    };
-    const bool in9 = !input_unread(9, true), in7 = !input_unread(7, true);
-    const bool lo1 = (kept_mask & kLeanLo1) && (kept_mask & kKeptPoolArg), lo2 = (kept_mask & kLeanLo2) && (kept_mask & kKeptPoolArg);
-    NC_TRY(rebuild(1, p.cat1, 64, S, lo1 && (in9 || !pool_folds(1)), (kept_mask & kLeanUp1) && in9, V + p.e2b, 11, d1));
-    NC_TRY(rebuild(3, p.cat2, 128, Sh, lo2 && (in7 || !pool_folds(3)), (kept_mask & kLeanUp2) && in7, V + p.b3, 10, d2));
-  }
+  // block lo of level L feeds the pool AND the skip: gradient = pool backward (of gpool) + the first half of dcat, formed inside the block's norm
+  // backward (no K-channel tensor) or by nc_maxpool2_bwd_add into gsum; then the block's backward, its data gradient into gsum
+  auto skip_bwd = [&](int L, const float* gpool, const float* dcat, float* gsum, const float* in, float* draw) -> int {
+    const ULevel& u = kUL[L];
+    const int* d = p.d[L - 1];
+    const long Sc = p.S[L - 1], Sp = p.S[L];
+    if (f.pool_folds(L)) return block_bwd(u.lo, dcat, in, draw, gsum, gpool);
+    for (int n = 0; n < N; ++n)
+      NC_TRY(nc_maxpool2_bwd_add(gpool + (size_t)n * u.K * Sp, V + p.*u.cat + (size_t)n * 2 * u.K * Sc, dcat + (size_t)n * 2 * u.K * Sc,
+                                 gsum + (size_t)n * u.K * Sc, u.K, d[0], d[1], d[2], stream));
+    return block_bwd(u.lo, gsum, in, draw, gsum);
+  };
+  NC_TRY(rebuild(1));
+  NC_TRY(rebuild(2));
   // 1x1 tail
   NC_TRY(nc_sigmoid_bwd(dy, y, G + p.s1, (long)N * S, stream));
   NC_TRY(nc_conv_wgrad(V + p.t1, G + p.s1, DP + o.w[13], DP + o.b[13], N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
   NC_TRY(nc_conv_dgrad(G + p.s1, P + o.w[13], G + p.s2, N, 1, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
-  // lean (one sample, block 9 in the two-term form with its dY written by the norm backward): one_by_one's data gradient is not expanded --
-  // block 9's InstanceNorm backward forms w12[c] * s2[v] itself; the conditions are block_bwd's own for that path.  (dW12 / db12 stay with the
-  // matrix kernel over e1: their summation order is part of what the step computes.)
-  ConvDims cd9;
-  const bool r1 = sw::raw(sw::UNET_LEAN) != 0 && N == 1 && fuse_bwd &&
-                  make_dims(cd9, N, 128, d0[0], d0[1], d0[2], 64, 3, 3, 3, 1, 1) && conv_layer_h2(cd9) &&
-                  conv_bwd_pre_supported(N, 128, d0[0], d0[1], d0[2], 64, 3, true, p.conv_ws) && instnorm_bwd_s3_supported(N, 64, S);
-  // a lean forward did not write e1 (kLeanE1): the weight gradient normalises raw[9] as it reads it -- or, off the flat kernels now, takes e1
-  // written again into scratch (block 9's normalisation + ReLU; T is free until block 9's backward)
-  if ((kept_mask & kLeanE1) && norm_1x1_taken(N, 64, d0[0], d0[1], d0[2], 1)) {
+  if (f.tail_flat) {  // (no e1: the weight gradient normalises raw[9] as it reads it)
     NC_TRY(conv_wgrad_norm_1x1(V + p.raw[9], V + p.mean[9], V + p.rstd[9], 0.f, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, cws,
                                p.conv_ws, stream));
   } else {
     const float* e1 = V + p.e1;
-    if (kept_mask & kLeanE1) {
+    if (f.rebuild_e1) {  // (T is free until block 9's backward)
       NC_TRY(nc_instnorm_act_fwd(V + p.raw[9], V + p.mean[9], V + p.rstd[9], 0.f, G + p.T, N * 64, S, stream));
       e1 = G + p.T;
     }
     NC_TRY(nc_conv_wgrad(e1, G + p.s2, DP + o.w[12], DP + o.b[12], N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
   }
-  if (!r1) {
-    NC_TRY(nc_conv_dgrad(G + p.s2, P + o.w[12], G + p.G1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
-  }
+  if (!f.r1()) NC_TRY(nc_conv_dgrad(G + p.s2, P + o.w[12], G + p.G1, N, 64, d0[0], d0[1], d0[2], 1, 1, 1, 1, 1, 0, cws, p.conv_ws, stream));
   // ex_conv1_1 (cat1 -> e1)
-  NC_TRY(block_bwd(9, r1 ? G + p.s2 : G + p.G1, V + p.cat1, G + p.G2, G + p.G3, r1));
-  // t_conv1 (e2b -> cat1[:, 64:])
-  const float* g;
-  NC_TRY(upper_half(G + p.G3, 128, S, &g));
-  NC_TRY(nc_convT_k2s2_dgrad(g, P + o.w[11], G + p.H1, N, 128, d1[0], d1[1], d1[2], 64, tws, p.convT_ws, stream));
-  NC_TRY(nc_convT_k2s2_wgrad(V + p.e2b, g, DP + o.w[11], DP + o.b[11], N, 128, d1[0], d1[1], d1[2], 64, tws, p.convT_ws, stream));
+  NC_TRY(block_bwd(9, f.r1() ? G + p.s2 : G + p.G1, V + p.cat1, G + p.G2, G + p.G3));
+  NC_TRY(t_conv_bwd(1, G + p.G3, G + p.H1));  // t_conv1 (e2b -> cat1[:, 64:])
   // ex_double_conv2 (cat2 -> e2a -> e2b)
   NC_TRY(block_bwd(8, G + p.H1, V + p.e2a, G + p.H2, G + p.H1));
   NC_TRY(block_bwd(7, G + p.H1, V + p.cat2, G + p.H2, G + p.H3));
-  // t_conv2 (b3 -> cat2[:, 128:])
-  NC_TRY(upper_half(G + p.H3, 256, Sh, &g));
-  NC_TRY(nc_convT_k2s2_dgrad(g, P + o.w[10], G + p.Q1, N, 256, d2[0], d2[1], d2[2], 128, tws, p.convT_ws, stream));
-  NC_TRY(nc_convT_k2s2_wgrad(V + p.b3, g, DP + o.w[10], DP + o.b[10], N, 256, d2[0], d2[1], d2[2], 128, tws, p.convT_ws, stream));
+  NC_TRY(t_conv_bwd(2, G + p.H3, G + p.Q1));  // t_conv2 (b3 -> cat2[:, 128:])
   // bottom_layer (p2 -> b1 -> b2 -> b3)
   NC_TRY(block_bwd(6, G + p.Q1, V + p.b2, G + p.Q2, G + p.Q1));
   NC_TRY(block_bwd(5, G + p.Q1, V + p.b1, G + p.Q2, G + p.Q1));
   NC_TRY(block_bwd(4, G + p.Q1, V + p.p2, G + p.Q2, G + p.Q1));
-  // conv2 = cat2[:, :128] feeds the pool AND the skip: gradient = pool backward + the first half of dcat2
-  if (pool_folds(3)) {  // (the gradient is formed inside block 3's norm backward: no 128-channel tensor)
-    NC_TRY(block_bwd(3, G + p.H3, V + p.a2, G + p.H2, G + p.H1, false, G + p.Q1));
-  } else {
-    for (int n = 0; n < N; ++n)
-      NC_TRY(nc_maxpool2_bwd_add(G + p.Q1 + (size_t)n * 128 * Sq, V + p.cat2 + (size_t)n * 256 * Sh, G + p.H3 + (size_t)n * 256 * Sh,
-                                 G + p.H1 + (size_t)n * 128 * Sh, 128, d1[0], d1[1], d1[2], stream));
-    // double_conv2 (p1 -> a2 -> conv2)
-    NC_TRY(block_bwd(3, G + p.H1, V + p.a2, G + p.H2, G + p.H1));
-  }
+  // double_conv2 (p1 -> a2 -> conv2 = cat2[:, :128]), double_conv1 (x -> a1 -> conv1 = cat1[:, :64])
+  NC_TRY(skip_bwd(2, G + p.Q1, G + p.H3, G + p.H1, V + p.a2, G + p.H2));
   NC_TRY(block_bwd(2, G + p.H1, V + p.p1, G + p.H2, G + p.H1));
-  if (pool_folds(1)) {
-    NC_TRY(block_bwd(1, G + p.G3, V + p.a1, G + p.G2, G + p.G1, false, G + p.H1));
-  } else {
-    for (int n = 0; n < N; ++n)
-      NC_TRY(nc_maxpool2_bwd_add(G + p.H1 + (size_t)n * 64 * Sh, V + p.cat1 + (size_t)n * 128 * S, G + p.G3 + (size_t)n * 128 * S,
-                                 G + p.G1 + (size_t)n * 64 * S, 64, d0[0], d0[1], d0[2], stream));
-    // double_conv1 (x -> a1 -> conv1)
-    NC_TRY(block_bwd(1, G + p.G1, V + p.a1, G + p.G2, G + p.G1));
-  }
+  NC_TRY(skip_bwd(1, G + p.H1, G + p.G3, G + p.G1, V + p.a1, G + p.G2));
   return block_bwd(0, G + p.G1, x, G + p.G2, dx);
 }
+
 
 }  // extern "C"
 
@@ -751,9 +750,10 @@ __global__ void __launch_bounds__(128) k_dl_w1_contract(const float* __restrict_
   for (int a = 0; a < 27; ++a) v += (double)E[k * 27 + a] * (double)Pq[((long)c * 32 + a) * 125 + 124 - t];
   dw1[((long)k * 64 + c) * 125 + t] = (float)v;
 }
-constexpr unsigned kKeptCollapsed = 1u << 31;
-constexpr unsigned kKeptNoAct1 = 1u << 30;
-constexpr unsigned kKeptTyped = 1u << 29;  // ... layers 1 .. 5 ran as ONE position-typed 7^3 kernel (dl_typed.hip): neither act1 nor a two-term copy of act0 exists  // ... and layer 1 ran in its 64 -> 27 form: act1 was never written ("the forward without act1")
+// the deep-linear flags of `kept` (Kept::has / Kept::set)
+constexpr unsigned kKeptCollapsed = 1u << 31;  // layers 2 .. 5 ran in the collapsed form: act2 .. act4 do not exist ("the collapsed tail")
+constexpr unsigned kKeptNoAct1 = 1u << 30;     // ... and layer 1 ran in its 64 -> 27 form: act1 was never written ("the forward without act1")
+constexpr unsigned kKeptTyped = 1u << 29;      // ... layers 1 .. 5 ran as ONE position-typed 7^3 kernel (dl_typed.hip): neither act1 nor a two-term copy of act0 exists
 
 // (8 workgroups, each derives a and e for itself and 216 of E's 1728 entries; loops unrolled so that the loads of a sum are in flight together)
 __global__ void __launch_bounds__(256) k_dl_compose(const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ w4,
@@ -940,7 +940,7 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
   void* cws = ws;
   float* G = (float*)((char*)ws + align256(p.conv_ws));
   const float* in = x;
-  unsigned kept_mask = 0;
+  Kept kept_mask;
   if (kept) *kept = 0;
   const bool collapse = sw::raw(sw::DL_COLLAPSE) != 0;
   char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
@@ -962,7 +962,7 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
       NC_TRY(dl_typed_compose((const float*)(tail + LTail::Wf), typed, N, S0, S1, S2, hs));
       NC_TRY(conv_c1k7_h2_dgrad(in, dl_typed_wp(typed, N, S0, S1, S2), y, d0, cws, p.conv_ws, hs));
       NC_TRY(dl_typed_fwd_boundary(in, y, typed, N, S0, S1, S2, hs));
-      kept_mask |= kKeptCollapsed | kKeptNoAct1 | kKeptTyped;
+      kept_mask.set(kKeptCollapsed | kKeptNoAct1 | kKeptTyped);
       break;
     }
     if (collapse && i == 1 && saved && k32_on && make_dims(dk, N, 64, S0, S1, S2, 32, 5, 5, 5, 1, 2) && conv_fwd_h2_k32_supported(dk) &&
@@ -975,14 +975,15 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
       NC_TRY(conv_fwd_h2_k32_keep(in, (const float*)(tail + LTail::Wf), Z, dk, cws, p.conv_ws, hs, saved + p.xs3[1]));
       hipLaunchKernelGGL(k_dl_combine27, dim3(1024, (unsigned)N), dim3(256), 0, hs, (const float*)Z, y, S0, S1, S2, 32);
       NC_TRY(check_launch("deep_linear_fwd: shifted sum"));
-      kept_mask |= kKeptCollapsed | kKeptNoAct1 | (1u << 1) | (1u << 17);
+      kept_mask.set(kKeptCollapsed | kKeptNoAct1);
+      kept_mask.set_operand(1, true);
       break;
     }
     if (collapse && i == 2) {  // layers 2 .. 5 as one 64 -> 1 convolution of act1 (see "the collapsed tail" above)
       hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, hs, params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail);
       NC_TRY(check_launch("deep_linear_fwd: compose"));
       NC_TRY(conv_fwd_to1_k3(in, (const float*)(tail + LTail::E), y, N, 64, S0, S1, S2, cws, p.conv_ws, hs));
-      kept_mask |= kKeptCollapsed;
+      kept_mask.set(kKeptCollapsed);
       break;
     }
     const LLayer& l = kLL[i];
@@ -993,12 +994,10 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
       NC_TRY(conv_fwd_keep(in, params + p.w[i], nullptr, out, N, l.C, S0, S1, S2, l.K, l.k, cws, p.conv_ws, stream, keep, &kept));
     else
       NC_TRY(nc_conv_fwd(in, params + p.w[i], nullptr, out, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2, cws, p.conv_ws, stream));
-    if (kept) kept_mask |= 1u << i;
-    ConvDims cdl;
-    if (kept && make_dims(cdl, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2) && conv_layer_h2(cdl)) kept_mask |= 1u << (16 + i);
+    if (kept) kept_mask.set_operand(i, layer_h2_now(N, l.C, p.d, l.K, l.k));
     in = out;
   }
-  if (kept) *kept = kept_mask;
+  if (kept) *kept = kept_mask.w;
   return NC_OK;
 }
 
@@ -1013,20 +1012,20 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
   void* cws = ws;
   float* G = (float*)((char*)ws + align256(p.conv_ws));
   const float* g = dy;
-  const unsigned kept_mask = kept;
+  const Kept kept_mask{kept};
   int top = 5;
   // layer 1's backward from the rank structure of its dY (see k_dl_shift27): decided here, because with both halves in that form dL/dact1 is
   // never formed
-  ConvDims dsh, cd1;
+  ConvDims dsh;
   const bool rank_on = sw::raw(sw::DL_RANK_WGRAD) != 0;
   const bool rank_dg_on = sw::raw(sw::DL_RANK_DGRAD) != 0;
-  const bool h2_1 = make_dims(cd1, N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2) && conv_layer_h2(cd1);
-  const bool have1 = ((kept_mask >> 1) & 1) && ((kept_mask >> 17) & 1) != 0;
-  const bool rank_w = (kept_mask & kKeptCollapsed) && rank_on && h2_1 && have1 && make_dims(dsh, N, 32, S0, S1, S2, 64, 5, 5, 5, 1, 2) &&
+  const bool h2_1 = layer_h2_now(N, 64, p.d, 64, 5);
+  const bool have1 = kept_mask.operand(1) && kept_mask.operand_h2(1);
+  const bool rank_w = kept_mask.has(kKeptCollapsed) && rank_on && h2_1 && have1 && make_dims(dsh, N, 32, S0, S1, S2, 64, 5, 5, 5, 1, 2) &&
                       wgrad_h2_supported(dsh) && s3_wgrad_ws_bytes(dsh) <= p.conv_ws;
   const bool rank_dgrad = rank_w && rank_dg_on && conv_fwd_h2_c32_supported(dsh) && conv_fwd_h2_c32_ws_bytes(dsh) <= p.conv_ws;
   const bool rank_all = rank_dgrad;
-  if (kept_mask & kKeptTyped) {  // layers 1 .. 5 ran as one position-typed 7^3 kernel (dl_typed.hip): their whole backward from dy, act0 and the weights
+  if (kept_mask.has(kKeptTyped)) {  // layers 1 .. 5 ran as one position-typed 7^3 kernel (dl_typed.hip): their whole backward from dy, act0 and the weights
     hipStream_t hs = (hipStream_t)stream;
     char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
     char* typed = tail + align256(LTail::bytes);
@@ -1059,7 +1058,7 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
     NC_TRY(check_launch("deep_linear_bwd: typed parameter gradients"));
     g = g0;
     top = 0;
-  } else if (kept_mask & kKeptCollapsed) {  // the forward left no act2 .. act4: layers 2 .. 5 from dy, act1 and the weights alone
+  } else if (kept_mask.has(kKeptCollapsed)) {  // the forward left no act2 .. act4: layers 2 .. 5 from dy, act1 and the weights alone
     hipStream_t hs = (hipStream_t)stream;
     char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
     const float* act1 = saved + p.act[1];  // (kKeptNoAct1: not there)
@@ -1075,7 +1074,7 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
       hipLaunchKernelGGL(k_dl_w1_contract, dim3(64, 64), dim3(128), 0, hs, (const float*)(tail + LTail::E), (const float*)(tail + LTail::P), dparams + p.w[1]);
       NC_TRY(check_launch("deep_linear_bwd: q, dW1"));
     } else {
-      if (kept_mask & kKeptNoAct1) {  // (the forward never wrote act1 and the switches changed since: form it now, in a gradient buffer)
+      if (kept_mask.has(kKeptNoAct1)) {  // (the forward never wrote act1 and the switches changed since: form it now, in a gradient buffer)
         NC_TRY(nc_conv_fwd(saved + p.act[0], params + p.w[1], nullptr, G + p.g[1], N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2, cws, p.conv_ws, stream));
         act1 = G + p.g[1];
       }
@@ -1095,9 +1094,8 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
     const LLayer& l = kLL[i];
     const float* in = i == 0 ? x : saved + p.act[i - 1];
     float* gin = i == 0 ? dx : G + p.g[i & 1];
-    ConvDims cdl;
-    const bool now_h2 = make_dims(cdl, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2) && conv_layer_h2(cdl);
-    const bool have = ((kept_mask >> i) & 1) && (((kept_mask >> (16 + i)) & 1) != 0) == now_h2;
+    const bool now_h2 = layer_h2_now(N, l.C, p.d, l.K, l.k);
+    const bool have = kept_mask.operand_usable(i, now_h2);
     if (i == 1 && rank_w && now_h2 && have) {  // the 32 x 64 problems of "layer 1's weight gradient from the rank structure of its dY" (above)
       hipStream_t hs = (hipStream_t)stream;
       char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;

@@ -183,25 +183,34 @@ def test_lean_forms_two_samples(switches):
         assert torch.equal(g0[k], g1[k]), k
 
 
+def moved_switch_case():
+    """The network, input and output gradient of the moved-switch runs below (tests/test_gpu_unet_forms.py repeats one of them)."""
+    torch.manual_seed(21)
+    net = networks.define_G(1, 1, 64, 'unet_deconv', 'instance', False, 'normal', 0.02, [0])
+    return net, torch.rand(1, 1, 24, 24, 24, device=DEV), torch.randn(1, 1, 24, 24, 24, device=DEV)
+
+
+def moved_switch_grads(net, x, g, before_fwd, before_bwd):
+    """One forward and its backward with before_fwd() / before_bwd() called in front of each; the weight gradients, flattened."""
+    for p_ in net.parameters():
+        p_.grad = None
+    before_fwd()
+    y = net(x)
+    before_bwd()
+    y.backward(g)
+    return torch.cat([p_.grad.reshape(-1).clone() for p_ in net.parameters() if p_.dim() > 1])
+
+
 def test_lean_forward_then_another_backward(switches):
     """A lean forward did not write a1, a2, b1, b2, e2a.  A backward that cannot use the kept H2 copies -- the split kernels were switched off,
     or the number of terms moved, between the two calls -- writes them again; a backward under the lean switch after a full forward needs
     nothing.  All combinations: finite and within 5e-3 (relative L2 of the weight gradients) of the all-fp32 run, as
     tests/test_gpu_split.py::test_switch_toggled_between_forward_and_backward asks of the full forms."""
-    torch.manual_seed(21)
-    net = networks.define_G(1, 1, 64, 'unet_deconv', 'instance', False, 'normal', 0.02, [0])
-    x = torch.rand(1, 1, 24, 24, 24, device=DEV)
-    g = torch.randn(1, 1, 24, 24, 24, device=DEV)
+    net, x, g = moved_switch_case()
     grads = {}
 
     def one(key, before_fwd, before_bwd):
-        for p_ in net.parameters():
-            p_.grad = None
-        before_fwd()
-        y = net(x)
-        before_bwd()
-        y.backward(g)
-        grads[key] = torch.cat([p_.grad.reshape(-1).clone() for p_ in net.parameters() if p_.dim() > 1])
+        grads[key] = moved_switch_grads(net, x, g, before_fwd, before_bwd)
     switches.nc_set_unet_lean(1)
     for fwd_on in (True, False):
         for bwd_on in (True, False):
