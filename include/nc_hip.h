@@ -469,13 +469,16 @@ int nc_convT_h2_bound_debug(const float* w, const float* bias, int C, int K, flo
 size_t nc_deep_linear_param_floats(void);
 size_t nc_deep_linear_saved_floats(int N, int S0, int S1, int S2);
 size_t nc_deep_linear_ws_bytes(int N, int S0, int S1, int S2);
+/* The `kept` word a TRAINING nc_deep_linear_fwd (saved != NULL) would return for this shape under the switches of now (the forward's plan,
+ * gen_nets.hip l_fwd_form); launches nothing.  0: N or an extent below 1 -- and the layered form with the split kernels off, which keeps nothing. */
+unsigned nc_deep_linear_kept_expected(int N, int S0, int S1, int S2);
 int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* saved /* or NULL */, int N, int S0, int S1,
                        int S2, void* ws, size_t ws_bytes, void* stream, unsigned* kept /* as above */);
 /* deep_linear_gen's layers 1 .. 5 (5^3, 3^3, then three 1 x 1; reference networks.py:900-911) are bias-free with nothing in between.  Level of
  * nc_set_dl_collapse (NC_DL_COLLAPSE at load time):
  *   0  layer by layer, as the reference's autograd does;
  *   1  (round 5) layers 2 .. 5 in collapsed form -- ONE 64 -> 1 convolution forward, and backward the six parameter gradients and dL/dact1 from
- *      dy, act1 and the weights alone (csrc/gen_nets.hip, "the collapsed tail") -- and the 5^3 layer's two gradients from 27 shifted copies of the
+ *      dy, act1 and the weights alone (csrc/dl_tail.hip, "the collapsed tail") -- and the 5^3 layer's two gradients from 27 shifted copies of the
  *      one-channel dy, its forward as a 64 -> 27 convolution plus a shifted sum ("the forward without act1");
  *   2  (default, round 6) layers 1 .. 5 as ONE position-typed 7^3 convolution 64 -> 1 of act0 (csrc/dl_typed.hip): the zero padding of
  *      act1 only matters ON the faces, where it removes the taps of the 3^3 kernel that point outside -- 27 composed kernels, one per position

@@ -465,9 +465,12 @@ int conv_fwd_h_c8(const void* xh, const float* w, const float* b, void* yh, int 
 int conv_fwd_h_na1(const void* xh, const float* w, float* y, const ConvDims& d, int dt, void* ws, size_t wsb, hipStream_t s);
 int conv_dgrad_h_c8(const void* dyh, const float* w, void* dxh, int ctot, int c0, const ConvDims& d, int dt, void* ws,
                     size_t wsb, hipStream_t s);
-// deep_linear_gen's collapsed tail (gen_nets.hip, "the collapsed tail"): the weight-space steps, shared with the 16-bit path.  tail: dl_tail_bytes()
-// of device scratch; compose fills E / Ef ([64][27] fp32: the 64 -> 1 kernel and its tap-flipped copy); q: [64][27], the caller's one-channel
-// weight gradient (x := dy, dY := act1); grads turns q into dW2 .. dW5
+// deep_linear_gen's layer table (reference networks.py:893-911: bias-free, k^3 kernels with padding k / 2), for gen_nets.hip and gen_nets_lp.hip
+struct LLayer { int C, K, k; };
+inline constexpr LLayer kLL[6] = {{1, 64, 7}, {64, 64, 5}, {64, 64, 3}, {64, 32, 1}, {32, 16, 1}, {16, 1, 1}};
+// deep_linear_gen's collapsed tail (dl_tail.hip, "the collapsed tail"): the weight-space steps, shared by the fp32 and the 16-bit path.  tail:
+// dl_tail_bytes() of device scratch; compose fills E / Ef ([64][27] fp32: the 64 -> 1 kernel and its tap-flipped copy); q: [64][27], the caller's
+// one-channel weight gradient (x := dy, dY := act1); grads turns q into dW2 .. dW5
 size_t dl_tail_bytes();
 const float* dl_tail_E(const char* tail);
 const float* dl_tail_Ef(const char* tail);
@@ -475,11 +478,14 @@ float* dl_tail_q(char* tail);
 int dl_tail_compose(const float* w2, const float* w3, const float* w4, const float* w5, char* tail, hipStream_t s);
 int dl_tail_grads(const float* w2, const float* w3, const float* w4, const float* w5, char* tail, float* dw2, float* dw3, float* dw4, float* dw5,
                   hipStream_t s);
-// layer 1's weight gradient from the rank structure of its dY (gen_nets.hip): P = the 32 x 64 weight gradient [64][32][125] the caller computed
+// layer 1's weight gradient from the rank structure of its dY (dl_tail.hip): P = the 32 x 64 weight gradient [64][32][125] the caller computed
+// between act0 and Dsh, shift27's 27 shifted copies of the one-channel dy ([N][32][S], five channels zero)
 float* dl_tail_P(char* tail);
+int dl_shift27(const float* dy, float* dsh, int N, int D, int H, int W, hipStream_t s);
 const float* dl_w1_fold(char* tail, const float* w1, hipStream_t s);  // [64][32][125]: layer 1's data gradient as a forward convolution of Dsh
 int dl_w1_contract(const char* tail, float* dw1, hipStream_t s);
 int dl_q_from_p(char* tail, const float* w1, hipStream_t s);
+const float* dl_fold_fwd(char* tail, const float* w1, hipStream_t s);  // F's first 32 rows [32][64][125] in the Wf region (the 64 -> 32 forward convolution's weights)
 const float* dl_fold_fwd64(char* tail, const float* w1, hipStream_t s);  // F[t][c][s] = sum_c' E[c'][t] W1[c'][c][s] as [64][64][125], rows >= 27 zero
 int dl_combine27(const float* Z, float* y, int N, int D, int H, int W, int zch, hipStream_t s);  // y[v] = sum_t [v + t - 1 inside] Z[t][v + t - 1]  // q (tap-flipped, into the tail scratch) as a contraction of P and W1
 // one-channel KS^3 layers (KS = 3, 7) in "pseudo-channel" form on the 16-bit cores (conv_h.hip)

@@ -5,7 +5,7 @@
 // 7^3 kernel is the zero padding of act1 -- which matters ON the faces only (E reaches one voxel) and there just removes the taps of E that
 // point outside.  So with the voxel's position TYPE tau (per axis: 0 = on the low face, 1 = inside, 2 = on the high face; 27 types, 13 = interior)
 //     y[v] = sum_{c, d} H_tau(v)[c][d] act0[c][v + d - 3],   H_tau[c][d] = sum over the taps t of E that tau allows, s = d - t, of F_t[c][s]
-// (F_t = E[., t] composed with W1: k_dl_fold_fwd, gen_nets.hip) -- exact on faces, edges and corners, 64 x 343 products per voxel where the 5^3 layer
+// (F_t = E[., t] composed with W1: k_dl_fold_fwd, dl_tail.hip) -- exact on faces, edges and corners, 64 x 343 products per voxel where the 5^3 layer
 // alone took 64 x 64 x 125.  The interior kernel H_13 runs everywhere on the two-term matrix kernels of conv_s3x.hip (the pseudo-channel forms of
 // Conv3d(1, 64, 7)); the 5.5 % of the voxels that lie on a face are recomputed / corrected here with their own type's kernel:
 //     forward    y[v] (v on a face) = its own H_tau                                                            k_dl_bnd_fwd
@@ -13,7 +13,7 @@
 //     dH_tau     = sum_{v of type tau} dy[v] act0[c][v + d - 3]  for the 26 boundary types                      k_dl_bnd_wgrad + k_dl_bnd_reduce
 //     dH_13      = (the full correlation of dy and act0: conv_wgrad_c1 with the operands' roles swapped) - sum of the boundary types'
 // and every parameter gradient follows in weight space: P[t][c][s] = sum_tau [tau allows t] dH_tau[c][t + s] is exactly the tensor the
-// rank-structured form took from a 32 x 64-channel 5^3 weight gradient (gen_nets.hip: dW1 = E . P, q = W1 . P, then the tail's formulas).
+// rank-structured form took from a 32 x 64-channel 5^3 weight gradient (dl_tail.hip: dW1 = E . P, q = W1 . P, then the tail's formulas).
 // Boundary voxels: the full rows (z, y) with z or y on a face (lanes run along x), and the two end voxels of every other row -- the x faces,
 // read through a transposed copy of the four columns next to each x face (k_dl_gather_x: lanes run along y).  Everything deterministic: no
 // floating-point atomics, partial sums reduced in a fixed order.

@@ -624,10 +624,9 @@ int nc_unet_deconv_bwd(const float* params, const float* x, const float* y, cons
 }  // extern "C"
 
 // ---- DeepLinearGenerator ------------------------------------------------------------------------------------------
+// The layer table kLL is common.hpp's.  The weight-space steps of the collapsed forms (their algebra, kernels and scratch) are dl_tail.hip's
+// nc::dl_*; the position-typed kernels are dl_typed.hip's.  Here: the plan of each direction, and the launches it names.
 namespace {
-
-struct LLayer { int C, K, k; };
-const LLayer kLL[6] = {{1, 64, 7}, {64, 64, 5}, {64, 64, 3}, {64, 32, 1}, {32, 16, 1}, {16, 1, 1}};
 
 struct LPlan {
   int N, d[3];
@@ -638,249 +637,6 @@ struct LPlan {
   size_t g[2], grads;         // gradient ping-pong
   size_t conv_ws;
 };
-
-// ---- the collapsed tail ----------------------------------------------------------------------------------------------------------------
-// Layers 2 .. 5 (3^3 64 -> 64, then 1 x 1: 64 -> 32 -> 16 -> 1; reference networks.py:902-911) have no bias and nothing between them, and the
-// 1 x 1 layers need no padding, so with  a = W5 W4 (1 x 32),  e = a W3 (1 x 64)  and  E[c][t] = sum_k e[k] W2[k][c][t]:
-//     y = E (*) act1                                   ONE 64 -> 1 convolution, 3^3, padding 1 -- exact at the borders too: the only padded
-//                                                      tensor of the four layers is act1 itself
-//     dL/dact1 = flip(E) (*) dy                        a 1 -> 64 convolution of the one-channel dy
-//     q[c][t]  = sum_v dy[v] act1[c][v + t - 1]        64 x 27 numbers: a weight gradient with ONE "output" channel
-//     dW2[k][c][t] = e[k] q[c][t];   r = sum_{c,t} W2[.][c][t] q[c][t]  (= sum_v dy[v] act2[.][v]);   dW3 = a^T r^T;   s = W3 r;
-//     dW4 = W5^T s^T;   dW5 = (W4 s)^T
-// -- the same output and the same six parameter gradients as the layer-by-layer evaluation (every product of the chain rule is there, the
-// rank-one factors are simply never expanded over the voxels), at 2 x 27 x 64 instead of 2 x (27 x 64 x 64 + 64 x 32 + 32 x 16 + 16) MACs per
-// voxel and direction, and act2 .. act4 are neither written nor read.  The weight-space products run in fp64.  Numerically this is at least
-// as close to the exact result as the fp32 chain (tests/test_gpu_nets.py: against the fp64 oracle, and against the layered path).
-// nc_set_dl_collapse(0) / NC_DL_COLLAPSE=0: the layered evaluation.  The forward records its choice in `kept` (bit 31): the backward of a
-// collapsed forward is collapsed whatever the switch says by then (act2 .. act4 do not exist).
-struct LTail {  // byte offsets into the tail scratch
-  static constexpr size_t a = 0, e = 32 * 8, r = e + 64 * 8, E = r + 64 * 8, Ef = E + 1728 * 4, q = Ef + 1728 * 4, P = q + 1728 * 4 + 256,
-                          Wf = P + (size_t)64 * 32 * 125 * 4 + 256, bytes = Wf + (size_t)64 * 32 * 125 * 4 + 256;
-};
-
-// ---- layer 1's weight gradient from the rank structure of its dY ---------------------------------------------------------------------------
-// With the tail collapsed, dL/dact1 = g1 is 64 channels made from ONE: g1[k][v] = sum_a E[k][a] dy[v - (a - 1)] on the volume (27 shifts a).
-// Write Dsh[a][v] = dy[v - (a - 1)] for v inside the volume (27 channels, padded to 32): g1 = E . Dsh, and the 5^3 layer's weight gradient
-//     dW1[k][c][t] = sum_v g1[k][v] act0[c][v + t - 2] = sum_a E[k][a] P[a][c][t],   P[a][c][t] = sum_v Dsh[a][v] act0[c][v + t - 2]
-// -- P is a 5^3 weight gradient between a 32- and a 64-channel tensor: HALF the matrix work of the 64 x 64 one, same kernel (k_wgrad_s3x with
-// act0's kept two-term copy in the dY role, which turns P around: Pq[c][a][t'] = P[a][c][124 - t']), then 64 x 64 x 125 x 27 MACs in weight
-// space.  Exact: the truncation of g1 to the volume is IN Dsh.  The data gradient of the layer still takes g1 itself.
-__global__ void __launch_bounds__(256) k_dl_shift27(const float* __restrict__ dy, float* __restrict__ dsh, int D, int H, int W) {
-  const long S = (long)D * H * W;
-  const int a = blockIdx.y, n = blockIdx.z;
-  float* out = dsh + ((long)n * 32 + a) * S;
-  const float* in = dy + (long)n * S;
-  const int az = a / 9 - 1, ay = (a / 3) % 3 - 1, ax = a % 3 - 1;
-  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < S; v += (long)gridDim.x * 256) {
-    float r = 0.f;
-    if (a < 27) {
-      const int x = (int)(v % W), y = (int)((v / W) % H), z = (int)(v / ((long)W * H));
-      const int sx = x - ax, sy = y - ay, sz = z - az;
-      if ((unsigned)sx < (unsigned)W && (unsigned)sy < (unsigned)H && (unsigned)sz < (unsigned)D) r = in[((long)sz * H + sy) * W + sx];
-    }
-    out[v] = r;
-  }
-}
-// The data gradient of the same layer in the same form (used where the convolution kernel takes 32 input channels: the 16-bit path):
-//     dL/dact0[c][u] = sum_{k,t} W1[k][c][t] g1[k][u - t + 2] = sum_{a,s} Wf[c][a][s] Dsh[a][u + s - 2],   Wf[c][a][s] = sum_k W1[k][c][124 - s] E[k][a]
-// -- a FORWARD 5^3 convolution 32 -> 64 of Dsh with weights composed here (zero for the five padding shifts).
-__global__ void __launch_bounds__(128) k_dl_w1_fold(const float* __restrict__ E, const float* __restrict__ w1, float* __restrict__ wf) {
-  const int c = blockIdx.x, a = blockIdx.y, sidx = threadIdx.x;
-  if (sidx >= 125) return;
-  double v = 0.0;
-  if (a < 27)
-    for (int k = 0; k < 64; ++k) v += (double)w1[((long)k * 64 + c) * 125 + 124 - sidx] * (double)E[k * 27 + a];
-  wf[((long)c * 32 + a) * 125 + sidx] = (float)v;
-}
-// ---- the forward without act1 ---------------------------------------------------------------------------------------------------------------
-// Once the backward takes q from P, act1 is wanted by ONE consumer: y = E (*) act1.  With F_t[c][s] = sum_c' E[c'][t] W1[c'][c][s] (27 kernels
-// 64 -> 1, 5^3):   y[v] = sum_t [v + t - 1 inside the volume] Z_t[v + t - 1],   Z_t = F_t (*) act0  on the volume
-// -- a 5^3 convolution 64 -> 27 (padded to 32: k_conv_s3x K32, half the matrix work of 64 -> 64) and a 27-term shifted sum; the bracket IS
-// the zero padding of act1.  act1 is never written; the backward (rank forms above) does not miss it.
-__global__ void __launch_bounds__(128) k_dl_fold_fwd(const float* __restrict__ E, const float* __restrict__ w1, float* __restrict__ F) {
-  const int t = blockIdx.x, c = blockIdx.y, sidx = threadIdx.x;
-  if (sidx >= 125) return;
-  double v = 0.0;
-  if (t < 27)
-    for (int cp = 0; cp < 64; ++cp) v += (double)E[cp * 27 + t] * (double)w1[((long)cp * 64 + c) * 125 + sidx];
-  F[((long)t * 64 + c) * 125 + sidx] = (float)v;
-}
-__global__ void __launch_bounds__(256) k_dl_combine27(const float* __restrict__ Z, float* __restrict__ y, int D, int H, int W, int zch) {
-  const long S = (long)D * H * W;
-  const int n = blockIdx.y;
-  const float* z = Z + (long)n * zch * S;  // (zch: channels per sample of the Z tensor, 32 or 64; the first 27 are read)
-  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < S; v += (long)gridDim.x * 256) {
-    const int x = (int)(v % W), yy = (int)((v / W) % H), zz = (int)(v / ((long)W * H));
-    float acc = 0.f;
-#pragma unroll
-    for (int t = 0; t < 27; ++t) {
-      const int dz = t / 9 - 1, dy = (t / 3) % 3 - 1, dx = t % 3 - 1;
-      if ((unsigned)(x + dx) < (unsigned)W && (unsigned)(yy + dy) < (unsigned)H && (unsigned)(zz + dz) < (unsigned)D)
-        acc += z[(long)t * S + v + ((long)dz * H + dy) * W + dx];
-    }
-    y[(long)n * S + v] = acc;
-  }
-}
-
-// q itself is a contraction of the same P: q[c'][t] = sum_{c,s} W1[c'][c][s] P[t][c][s] (act1 = W1 (*) act0, and the shift a = t of dy IS the
-// mask "v + t - 1 inside the volume") -- no pass over act1.  Written tap-flipped, as k_dl_tail_w2 reads it.  Block (c', t), fixed-order tree.
-__global__ void __launch_bounds__(256) k_dl_q_from_p(const float* __restrict__ w1, const float* __restrict__ Pq, float* __restrict__ qf) {
-  __shared__ double red[256];
-  const int cp = blockIdx.x, t = blockIdx.y, th = threadIdx.x;
-  double v = 0.0;
-  for (int i = th; i < 64 * 125; i += 256) {
-    const int c = i / 125, sidx = i - c * 125;
-    v += (double)w1[((long)cp * 64 + c) * 125 + sidx] * (double)Pq[((long)c * 32 + t) * 125 + 124 - sidx];
-  }
-  red[th] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (th < o) red[th] += red[th + o];
-    __syncthreads();
-  }
-  if (th == 0) qf[cp * 27 + 26 - t] = (float)red[0];
-}
-// dW1[k][c][t] = sum_a E[k][a] Pq[c][a][124 - t]
-__global__ void __launch_bounds__(128) k_dl_w1_contract(const float* __restrict__ E, const float* __restrict__ Pq, float* __restrict__ dw1) {
-  const int k = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
-  if (t >= 125) return;
-  double v = 0.0;
-#pragma unroll
-  for (int a = 0; a < 27; ++a) v += (double)E[k * 27 + a] * (double)Pq[((long)c * 32 + a) * 125 + 124 - t];
-  dw1[((long)k * 64 + c) * 125 + t] = (float)v;
-}
-// the deep-linear flags of `kept` (Kept::has / Kept::set)
-constexpr unsigned kKeptCollapsed = 1u << 31;  // layers 2 .. 5 ran in the collapsed form: act2 .. act4 do not exist ("the collapsed tail")
-constexpr unsigned kKeptNoAct1 = 1u << 30;     // ... and layer 1 ran in its 64 -> 27 form: act1 was never written ("the forward without act1")
-constexpr unsigned kKeptTyped = 1u << 29;      // ... layers 1 .. 5 ran as ONE position-typed 7^3 kernel (dl_typed.hip): neither act1 nor a two-term copy of act0 exists
-
-// (8 workgroups, each derives a and e for itself and 216 of E's 1728 entries; loops unrolled so that the loads of a sum are in flight together)
-__global__ void __launch_bounds__(256) k_dl_compose(const float* __restrict__ w2, const float* __restrict__ w3, const float* __restrict__ w4,
-                                                    const float* __restrict__ w5, char* __restrict__ tail) {
-  __shared__ double sa[32], se[64];
-  const int t = threadIdx.x;
-  if (t < 32) {
-    double v = 0.0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v += (double)w5[i] * (double)w4[i * 32 + t];
-    sa[t] = v;
-    if (blockIdx.x == 0) ((double*)(tail + LTail::a))[t] = v;
-  }
-  __syncthreads();
-  if (t < 64) {
-    double v = 0.0;
-#pragma unroll
-    for (int b = 0; b < 32; ++b) v += sa[b] * (double)w3[b * 64 + t];
-    se[t] = v;
-    if (blockIdx.x == 0) ((double*)(tail + LTail::e))[t] = v;
-  }
-  __syncthreads();
-  if (t < 216) {
-    const int i = blockIdx.x * 216 + t;  // i = c * 27 + tap
-    double v = 0.0;
-#pragma unroll 16
-    for (int k = 0; k < 64; ++k) v += se[k] * (double)w2[(long)k * 1728 + i];
-    const int c = i / 27, tap = i - c * 27;
-    ((float*)(tail + LTail::E))[i] = (float)v;
-    ((float*)(tail + LTail::Ef))[c * 27 + 26 - tap] = (float)v;
-  }
-}
-
-// block k: dW2[k][.][.] and r[k].  qf = the weight gradient of the SWAPPED problem (x := dy, dY := act1): qf[c][t] = q[c][26 - t]
-__global__ void __launch_bounds__(256) k_dl_tail_w2(const float* __restrict__ w2, char* __restrict__ tail, float* __restrict__ dw2) {
-  __shared__ double red[256];
-  const int k = blockIdx.x, t = threadIdx.x;
-  const float* qf = (const float*)(tail + LTail::q);
-  const double ek = ((const double*)(tail + LTail::e))[k];
-  double part = 0.0;
-  for (int i = t; i < 1728; i += 256) {
-    const int c = i / 27, tap = i - c * 27;
-    const double q = (double)qf[c * 27 + 26 - tap];
-    dw2[(long)k * 1728 + i] = (float)(ek * q);
-    part += (double)w2[(long)k * 1728 + i] * q;
-  }
-  red[t] = part;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] += red[t + o];
-    __syncthreads();
-  }
-  if (t == 0) ((double*)(tail + LTail::r))[k] = red[0];
-}
-
-__global__ void __launch_bounds__(256) k_dl_tail_w345(const float* __restrict__ w3, const float* __restrict__ w4, const float* __restrict__ w5,
-                                                      const char* __restrict__ tail, float* __restrict__ dw3, float* __restrict__ dw4,
-                                                      float* __restrict__ dw5) {
-  __shared__ double ss[32];
-  const int t = threadIdx.x;
-  const double* a = (const double*)(tail + LTail::a);
-  const double* r = (const double*)(tail + LTail::r);
-  for (int i = t; i < 32 * 64; i += 256) dw3[i] = (float)(a[i / 64] * r[i % 64]);
-  if (t < 32) {
-    double v = 0.0;
-    for (int c = 0; c < 64; ++c) v += (double)w3[t * 64 + c] * r[c];
-    ss[t] = v;
-  }
-  __syncthreads();
-  for (int i = t; i < 16 * 32; i += 256) dw4[i] = (float)((double)w5[i / 32] * ss[i % 32]);
-  if (t < 16) {
-    double v = 0.0;
-    for (int b = 0; b < 32; ++b) v += (double)w4[t * 32 + b] * ss[b];
-    dw5[t] = (float)v;
-  }
-}
-
-// 0: layer by layer; 1: the collapsed tail + the rank forms of the 5^3 layer (round 5); 2 (default): layers 1 .. 5 as one position-typed 7^3 kernel
-// where the shape admits it (dl_typed.hip), else as 1: sw::DL_COLLAPSE
-
-}  // namespace
-
-// the same weight-space steps for the 16-bit path (gen_nets_lp.hip)
-namespace nc {
-size_t dl_tail_bytes() { return LTail::bytes; }
-const float* dl_tail_E(const char* tail) { return (const float*)(tail + LTail::E); }
-const float* dl_tail_Ef(const char* tail) { return (const float*)(tail + LTail::Ef); }
-float* dl_tail_q(char* tail) { return (float*)(tail + LTail::q); }
-int dl_tail_compose(const float* w2, const float* w3, const float* w4, const float* w5, char* tail, hipStream_t s) {
-  hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, s, w2, w3, w4, w5, tail);
-  return check_launch("deep_linear: compose");
-}
-float* dl_tail_P(char* tail) { return (float*)(tail + LTail::P); }
-const float* dl_w1_fold(char* tail, const float* w1, hipStream_t s) {  // composes Wf into the tail scratch and returns it (NULL: launch failed)
-  hipLaunchKernelGGL(k_dl_w1_fold, dim3(64, 32), dim3(128), 0, s, (const float*)(tail + LTail::E), w1, (float*)(tail + LTail::Wf));
-  return check_launch("deep_linear_bwd: composed data-gradient weights") ? nullptr : (const float*)(tail + LTail::Wf);
-}
-// the forward without act1 for the 16-bit path: F as a [64][64][125] tensor (rows 27 .. 63 zero) in the tail scratch (the P and Wf regions,
-// adjacent, 2 MB + 512 B; free in a forward), and the shifted sum over a Z tensor of `zch` channels per sample
-const float* dl_fold_fwd64(char* tail, const float* w1, hipStream_t s) {
-  static_assert(LTail::Wf == LTail::P + (size_t)64 * 32 * 125 * 4 + 256, "P and Wf adjacent");
-  float* F = (float*)(tail + LTail::P);
-  if (hipMemsetAsync(F + (size_t)32 * 64 * 125, 0, (size_t)32 * 64 * 125 * 4, s) != hipSuccess) return nullptr;
-  hipLaunchKernelGGL(k_dl_fold_fwd, dim3(32, 64), dim3(128), 0, s, (const float*)(tail + LTail::E), w1, F);
-  return check_launch("deep_linear_fwd: composed forward weights") ? nullptr : F;
-}
-int dl_combine27(const float* Z, float* y, int N, int D, int H, int W, int zch, hipStream_t s) {
-  hipLaunchKernelGGL(k_dl_combine27, dim3(1024, (unsigned)N), dim3(256), 0, s, Z, y, D, H, W, zch);
-  return check_launch("deep_linear_fwd: shifted sum");
-}
-int dl_q_from_p(char* tail, const float* w1, hipStream_t s) {
-  hipLaunchKernelGGL(k_dl_q_from_p, dim3(64, 27), dim3(256), 0, s, w1, (const float*)(tail + LTail::P), (float*)(tail + LTail::q));
-  return check_launch("deep_linear_bwd: q");
-}
-int dl_w1_contract(const char* tail, float* dw1, hipStream_t s) {
-  hipLaunchKernelGGL(k_dl_w1_contract, dim3(64, 64), dim3(128), 0, s, (const float*)(tail + LTail::E), (const float*)(tail + LTail::P), dw1);
-  return check_launch("deep_linear_bwd: dW1");
-}
-int dl_tail_grads(const float* w2, const float* w3, const float* w4, const float* w5, char* tail, float* dw2, float* dw3, float* dw4, float* dw5,
-                  hipStream_t s) {
-  hipLaunchKernelGGL(k_dl_tail_w2, dim3(64), dim3(256), 0, s, w2, tail, dw2);
-  hipLaunchKernelGGL(k_dl_tail_w345, dim3(1), dim3(256), 0, s, w3, w4, w5, (const char*)tail, dw3, dw4, dw5);
-  return check_launch("deep_linear: tail gradients");
-}
-}  // namespace nc
-
-namespace {
 
 bool l_plan(LPlan& p, int N, int S0, int S1, int S2) {
   if (N < 1 || S0 < 1 || S1 < 1 || S2 < 1) return false;
@@ -909,6 +665,127 @@ bool l_plan(LPlan& p, int N, int S0, int S1, int S2) {
   return true;
 }
 
+// THE WORKSPACE of both directions: convolution scratch | the gradient ping-pong (inference: the activations') | the tail scratch of the
+// weight-space steps | the typed form's scratch.  ws == NULL: the size alone.
+struct LWs { void* cws; float* G; char* tail; char* typed; size_t bytes; };
+LWs l_ws(const LPlan& p, void* ws) {
+  uintptr_t at = (uintptr_t)ws;
+  auto take = [&](size_t bytes) { const uintptr_t r = at; at += bytes; return r; };
+  LWs v;
+  v.cws = (void*)take(align256(p.conv_ws));
+  v.G = (float*)take(p.grads * sizeof(float) + 256);
+  v.tail = (char*)take(align256(dl_tail_bytes()));
+  v.typed = (char*)take(dl_typed_bytes(p.N, p.d[0], p.d[1], p.d[2]));
+  v.bytes = at - (uintptr_t)ws;
+  return v;
+}
+
+// the deep-linear flags of `kept` (Kept::has / Kept::set)
+constexpr unsigned kKeptCollapsed = 1u << 31;  // layers 2 .. 5 ran in the collapsed form: act2 .. act4 do not exist ("the collapsed tail")
+constexpr unsigned kKeptNoAct1 = 1u << 30;     // ... and layer 1 ran in its 64 -> 27 form: act1 was never written ("the forward without act1")
+constexpr unsigned kKeptTyped = 1u << 29;      // ... layers 1 .. 5 ran as ONE position-typed 7^3 kernel (dl_typed.hip): neither act1 nor a two-term copy of act0 exists
+
+// THE FORM OF THE FORWARD, decided before its first launch (all of it host state).  The forward reads these fields and launches.
+// sw::DL_COLLAPSE 0: layer by layer; 1: the collapsed tail + the rank forms of the 5^3 layer (round 5); 2 (default): layers 1 .. 5 as one
+// position-typed 7^3 kernel where the shape admits it (dl_typed.hip), else as 1.
+//   kLTyped    layers 1 .. 5 as ONE position-typed 7^3 convolution 64 -> 1 of act0 (dl_typed.hip): the interior kernel on the
+//              two-term pseudo-channel kernel of Conv3d(1, 64, 7)'s data gradient, the voxels on a face recomputed with their own kernels
+//   kLNoAct1   layers 1 .. 5 without act1 (dl_tail.hip, "the forward without act1"): Z = the 64 -> 27 convolution of act0, which leaves the
+//              two-term copy of act0, and y = its shifted sum
+//   kLTail     layers 2 .. 5 as one 64 -> 1 convolution of act1 (dl_tail.hip, "the collapsed tail")
+//   kLLayered  all six layers
+// The first two are training forms (they pay off through their backward): inference, saved == NULL, takes kLTail under levels 1 and 2.
+// A layer that runs layer by layer keeps its converted input where conv_fwd_keep does (Kept::operand, training only).
+enum LForm { kLLayered, kLTail, kLNoAct1, kLTyped };
+struct LFwdForms {
+  LForm form;
+  int layered;  // layers 0 .. layered - 1 run layer by layer, in front of the form's own launches
+  ConvDims cd;  // kLTyped: Conv3d(1, 64, 7)'s problem; kLNoAct1: the 64 -> 32 one, 5^3
+  Kept kept;
+};
+
+LFwdForms l_fwd_form(const LPlan& p, bool training) {
+  LFwdForms f{};
+  const int N = p.N, *d = p.d;
+  const int level = sw::raw(sw::DL_COLLAPSE);
+  if (level == 2 && training && dl_typed_supported(N, d[0], d[1], d[2]) && make_dims(f.cd, N, 1, d[0], d[1], d[2], 64, 7, 7, 7, 1, 3) &&
+      c1k7_h2_supported(f.cd) && c1_wgrad_supported(f.cd) && c1k7_h2_dgrad_ws_bytes(f.cd) <= p.conv_ws && c1k7_h2_ws_bytes(f.cd) <= p.conv_ws &&
+      c1_wgrad_ws_bytes(f.cd) <= p.conv_ws) {
+    f.form = kLTyped;
+    f.kept.set(kKeptCollapsed | kKeptNoAct1 | kKeptTyped);
+  } else if (level && training && sw::raw(sw::DL_K32) != 0 && make_dims(f.cd, N, 64, d[0], d[1], d[2], 32, 5, 5, 5, 1, 2) &&
+             conv_fwd_h2_k32_supported(f.cd) && (size_t)256 + s3x_packed_bytes(64, 32, 5, 2) + 512 <= p.conv_ws) {
+    f.form = kLNoAct1;
+    f.kept.set(kKeptCollapsed | kKeptNoAct1);
+    f.kept.set_operand(1, true);
+  } else if (level) {
+    f.form = kLTail;
+    f.kept.set(kKeptCollapsed);
+  } else {
+    f.form = kLLayered;
+  }
+  f.layered = f.form == kLLayered ? 6 : f.form == kLTail ? 2 : 1;
+  for (int i = 0; i < f.layered; ++i) {
+    const LLayer& l = kLL[i];
+    if (training && l.k > 1 && l.C % 8 == 0 && conv_keep_supported(N, l.C, d[0], d[1], d[2], l.K, l.k))  // (conv_fwd_keep's *kept)
+      f.kept.set_operand(i, layer_h2_now(N, l.C, d, l.K, l.k));
+  }
+  return f;
+}
+
+// THE FORM OF THE BACKWARD, decided at its top from `kept`, the switches of NOW and the shape.
+// top: where it starts.  kLTopTyped (kKeptTyped): layers 1 .. 5 from dy, act0 and the weights, then layer 0.  kLTopTail (kKeptCollapsed): layers
+// 2 .. 5 from dy, act1 and the weights alone, then layer 1 in the form below, then layer 0.  kLTopLayered: layers 5 .. 0.
+// Layer 1 behind a collapsed tail (dl_tail.hip, "layer 1's weight gradient from the rank structure of its dY"):
+//   rank_w      dW1 and q from P, the 32 x 64 weight gradient between the 27 shifted copies of dy and act0's kept two-term copy -- act1 is not read
+//   rank_dgrad  ... and dL/dact0 as a forward 32 -> 64 convolution of the shifted copies with composed weights: dL/dact1 is never formed (!g1)
+//   neither     q from dy and act1, dL/dact1 = flip(E) (*) dy, then the layer's ordinary backward in the loop.  remake_act1: the forward never
+//               wrote act1 (kKeptNoAct1) and the switches moved since -- it is formed now, in a gradient buffer
+// Whether dx is wanted is no input: layer 1's data gradient feeds layer 0's weight gradient either way, and layer 0 skips its own on a NULL dx.
+enum LTop { kLTopLayered, kLTopTail, kLTopTyped };
+struct LBwdForms {
+  LTop top;
+  int first;         // the layer loop runs first .. 0
+  bool xs[6];        // the layer's kept operand is usable (Kept::operand_usable)
+  bool rank_w, rank_dgrad, remake_act1, g1;
+  ConvDims cd;       // kLTopTyped: Conv3d(1, 64, 7)'s problem; rank_w: the 32 x 64 one, 5^3
+  const char* error; // `kept` names a form that this shape does not admit
+};
+
+LBwdForms l_bwd_forms(const LPlan& p, Kept k) {
+  LBwdForms f{};
+  const int N = p.N, *d = p.d;
+  bool now_h2[6] = {};
+  for (int i = 0; i < 6; ++i) {
+    const LLayer& l = kLL[i];
+    now_h2[i] = l.k > 1 && layer_h2_now(N, l.C, d, l.K, l.k);
+    f.xs[i] = l.k > 1 && k.operand_usable(i, now_h2[i]);
+  }
+  if (k.has(kKeptTyped)) {
+    // (its kernels exist in the two-term form only and convert their fp32 operands themselves: a caller who moved nc_set_split_terms after the
+    // forward still gets this form's backward)
+    ForceTwoTerm two_;
+    f.top = kLTopTyped;
+    f.first = 0;
+    if (!dl_typed_supported(N, d[0], d[1], d[2]) || !make_dims(f.cd, N, 1, d[0], d[1], d[2], 64, 7, 7, 7, 1, 3) || !c1k7_h2_supported(f.cd) ||
+        !c1_wgrad_supported(f.cd))
+      f.error = "deep_linear_bwd: the forward ran the position-typed form, which this shape does not admit";
+  } else if (k.has(kKeptCollapsed)) {
+    f.top = kLTopTail;
+    // now_h2[1] && xs[1]: the layer is two-term now AND its kept copy is there in that form -- so a rank form never needs a second look at either
+    f.rank_w = sw::raw(sw::DL_RANK_WGRAD) != 0 && now_h2[1] && f.xs[1] && make_dims(f.cd, N, 32, d[0], d[1], d[2], 64, 5, 5, 5, 1, 2) &&
+               wgrad_h2_supported(f.cd) && s3_wgrad_ws_bytes(f.cd) <= p.conv_ws;
+    f.rank_dgrad = f.rank_w && sw::raw(sw::DL_RANK_DGRAD) != 0 && conv_fwd_h2_c32_supported(f.cd) && conv_fwd_h2_c32_ws_bytes(f.cd) <= p.conv_ws;
+    f.remake_act1 = !f.rank_w && k.has(kKeptNoAct1);
+    f.g1 = !f.rank_dgrad;
+    f.first = f.rank_w ? 0 : 1;
+  } else {
+    f.top = kLTopLayered;
+    f.first = 5;
+  }
+  return f;
+}
+
 }  // namespace
 
 extern "C" {
@@ -926,7 +803,13 @@ size_t nc_deep_linear_saved_floats(int N, int S0, int S1, int S2) {
 
 size_t nc_deep_linear_ws_bytes(int N, int S0, int S1, int S2) {
   LPlan p;
-  return l_plan(p, N, S0, S1, S2) ? align256(p.conv_ws) + p.grads * sizeof(float) + 256 + align256(LTail::bytes) + dl_typed_bytes(N, S0, S1, S2) : 0;
+  return l_plan(p, N, S0, S1, S2) ? l_ws(p, nullptr).bytes : 0;
+}
+
+unsigned nc_deep_linear_kept_expected(int N, int S0, int S1, int S2) {
+  NetworkScope net_scope;
+  LPlan p;
+  return l_plan(p, N, S0, S1, S2) ? l_fwd_form(p, true).kept.w : 0;
 }
 
 // saved == NULL: inference -- the intermediate activations ping-pong through the workspace instead
@@ -936,68 +819,53 @@ int nc_deep_linear_fwd(const float* params, const float* x, float* y, float* sav
   if (!params || !x || !y) { set_error("deep_linear_fwd: null pointer"); return NC_ERR_ARG; }
   LPlan p;
   if (!l_plan(p, N, S0, S1, S2)) { set_error("deep_linear_fwd: bad shape"); return NC_ERR_SHAPE; }
-  if (!ws || ws_bytes < nc_deep_linear_ws_bytes(N, S0, S1, S2)) { set_error("deep_linear_fwd: workspace too small"); return NC_ERR_WS; }
-  void* cws = ws;
-  float* G = (float*)((char*)ws + align256(p.conv_ws));
-  const float* in = x;
-  Kept kept_mask;
-  if (kept) *kept = 0;
-  const bool collapse = sw::raw(sw::DL_COLLAPSE) != 0;
-  char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
+  const LWs w = l_ws(p, ws);
+  if (!ws || ws_bytes < w.bytes) { set_error("deep_linear_fwd: workspace too small"); return NC_ERR_WS; }
+  const LFwdForms f = l_fwd_form(p, saved != nullptr);
+  const float* P = params;
   hipStream_t hs = (hipStream_t)stream;
-  const bool k32_on = sw::raw(sw::DL_K32) != 0;
-  char* typed = tail + align256(LTail::bytes);
-  ConvDims d0;
-  // layers 1 .. 5 as ONE position-typed 7^3 convolution 64 -> 1 of act0 (dl_typed.hip): the interior kernel on the two-term
-  // pseudo-channel kernel of Conv3d(1, 64, 7)'s data gradient, the voxels on a face recomputed with their own kernels
-  const bool typed_ok = sw::raw(sw::DL_COLLAPSE) == 2 && saved && dl_typed_supported(N, S0, S1, S2) && make_dims(d0, N, 1, S0, S1, S2, 64, 7, 7, 7, 1, 3) && c1k7_h2_supported(d0) &&
-                        c1_wgrad_supported(d0) && c1k7_h2_dgrad_ws_bytes(d0) <= p.conv_ws && c1k7_h2_ws_bytes(d0) <= p.conv_ws &&
-                        c1_wgrad_ws_bytes(d0) <= p.conv_ws;
-  for (int i = 0; i < 6; ++i) {
-    ConvDims dk;
-    if (typed_ok && i == 1) {
-      hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, hs, params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail);
-      hipLaunchKernelGGL(k_dl_fold_fwd, dim3(32, 64), dim3(128), 0, hs, (const float*)(tail + LTail::E), params + p.w[1], (float*)(tail + LTail::Wf));
-      NC_TRY(check_launch("deep_linear_fwd: composed kernels"));
-      NC_TRY(dl_typed_compose((const float*)(tail + LTail::Wf), typed, N, S0, S1, S2, hs));
-      NC_TRY(conv_c1k7_h2_dgrad(in, dl_typed_wp(typed, N, S0, S1, S2), y, d0, cws, p.conv_ws, hs));
-      NC_TRY(dl_typed_fwd_boundary(in, y, typed, N, S0, S1, S2, hs));
-      kept_mask.set(kKeptCollapsed | kKeptNoAct1 | kKeptTyped);
-      break;
-    }
-    if (collapse && i == 1 && saved && k32_on && make_dims(dk, N, 64, S0, S1, S2, 32, 5, 5, 5, 1, 2) && conv_fwd_h2_k32_supported(dk) &&
-        (size_t)256 + s3x_packed_bytes(64, 32, 5, 2) + 512 <= p.conv_ws) {
-      // layers 1 .. 5 without act1 ("the forward without act1" above): Z = the 64 -> 27 convolution of act0, y = its shifted sum
-      hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, hs, params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail);
-      hipLaunchKernelGGL(k_dl_fold_fwd, dim3(32, 64), dim3(128), 0, hs, (const float*)(tail + LTail::E), params + p.w[1], (float*)(tail + LTail::Wf));
-      NC_TRY(check_launch("deep_linear_fwd: composed forward weights"));
-      float* Z = saved + p.act[1];  // (the slot act1 would take: 32 of its 64 channels)
-      NC_TRY(conv_fwd_h2_k32_keep(in, (const float*)(tail + LTail::Wf), Z, dk, cws, p.conv_ws, hs, saved + p.xs3[1]));
-      hipLaunchKernelGGL(k_dl_combine27, dim3(1024, (unsigned)N), dim3(256), 0, hs, (const float*)Z, y, S0, S1, S2, 32);
-      NC_TRY(check_launch("deep_linear_fwd: shifted sum"));
-      kept_mask.set(kKeptCollapsed | kKeptNoAct1);
-      kept_mask.set_operand(1, true);
-      break;
-    }
-    if (collapse && i == 2) {  // layers 2 .. 5 as one 64 -> 1 convolution of act1 (see "the collapsed tail" above)
-      hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, hs, params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail);
-      NC_TRY(check_launch("deep_linear_fwd: compose"));
-      NC_TRY(conv_fwd_to1_k3(in, (const float*)(tail + LTail::E), y, N, 64, S0, S1, S2, cws, p.conv_ws, hs));
-      kept_mask.set(kKeptCollapsed);
-      break;
-    }
+  if (kept) *kept = 0;
+  const float* in = x;
+  for (int i = 0; i < f.layered; ++i) {
     const LLayer& l = kLL[i];
-    float* out = i == 5 ? y : (saved ? saved + p.act[i] : G + p.g[i & 1]);
-    bool kept = false;
-    void* keep = saved && l.k > 1 && l.C % 8 == 0 ? (void*)(saved + p.xs3[i]) : nullptr;
-    if (l.k > 1)
-      NC_TRY(conv_fwd_keep(in, params + p.w[i], nullptr, out, N, l.C, S0, S1, S2, l.K, l.k, cws, p.conv_ws, stream, keep, &kept));
-    else
-      NC_TRY(nc_conv_fwd(in, params + p.w[i], nullptr, out, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2, cws, p.conv_ws, stream));
-    if (kept) kept_mask.set_operand(i, layer_h2_now(N, l.C, p.d, l.K, l.k));
+    float* out = i == 5 ? y : (saved ? saved + p.act[i] : w.G + p.g[i & 1]);
+    if (l.k > 1) {
+      bool kept1 = false;
+      void* keep = saved && l.C % 8 == 0 ? (void*)(saved + p.xs3[i]) : nullptr;
+      NC_TRY(conv_fwd_keep(in, P + p.w[i], nullptr, out, N, l.C, S0, S1, S2, l.K, l.k, w.cws, p.conv_ws, stream, keep, &kept1));
+      if (kept1 != f.kept.operand(i)) { set_error("deep_linear_fwd: layer %d %s its converted input, against the plan", i, kept1 ? "kept" : "did not keep"); return NC_ERR_ARG; }
+    } else {
+      NC_TRY(nc_conv_fwd(in, P + p.w[i], nullptr, out, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2, w.cws, p.conv_ws, stream));
+    }
     in = out;
   }
-  if (kept) *kept = kept_mask.w;
+  switch (f.form) {
+    case kLTyped: {
+      NC_TRY(dl_tail_compose(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, hs));
+      const float* F = dl_fold_fwd(w.tail, P + p.w[1], hs);
+      if (!F) return NC_ERR_HIP;
+      NC_TRY(dl_typed_compose(F, w.typed, N, S0, S1, S2, hs));
+      NC_TRY(conv_c1k7_h2_dgrad(in, dl_typed_wp(w.typed, N, S0, S1, S2), y, f.cd, w.cws, p.conv_ws, hs));
+      NC_TRY(dl_typed_fwd_boundary(in, y, w.typed, N, S0, S1, S2, hs));
+      break;
+    }
+    case kLNoAct1: {
+      NC_TRY(dl_tail_compose(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, hs));
+      const float* F = dl_fold_fwd(w.tail, P + p.w[1], hs);
+      if (!F) return NC_ERR_HIP;
+      float* Z = saved + p.act[1];  // (the slot act1 would take: 32 of its 64 channels)
+      NC_TRY(conv_fwd_h2_k32_keep(in, F, Z, f.cd, w.cws, p.conv_ws, hs, saved + p.xs3[1]));
+      NC_TRY(dl_combine27(Z, y, N, S0, S1, S2, 32, hs));
+      break;
+    }
+    case kLTail:
+      NC_TRY(dl_tail_compose(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, hs));
+      NC_TRY(conv_fwd_to1_k3(in, dl_tail_E(w.tail), y, N, 64, S0, S1, S2, w.cws, p.conv_ws, hs));
+      break;
+    case kLLayered:
+      break;
+  }
+  if (kept) *kept = f.kept.w;
   return NC_OK;
 }
 
@@ -1008,118 +876,77 @@ int nc_deep_linear_bwd(const float* params, const float* x, const float* saved, 
   if (!params || !x || !saved || !dy || !dparams) { set_error("deep_linear_bwd: null pointer"); return NC_ERR_ARG; }
   LPlan p;
   if (!l_plan(p, N, S0, S1, S2)) { set_error("deep_linear_bwd: bad shape"); return NC_ERR_SHAPE; }
-  if (!ws || ws_bytes < nc_deep_linear_ws_bytes(N, S0, S1, S2)) { set_error("deep_linear_bwd: workspace too small"); return NC_ERR_WS; }
-  void* cws = ws;
-  float* G = (float*)((char*)ws + align256(p.conv_ws));
-  const float* g = dy;
-  const Kept kept_mask{kept};
-  int top = 5;
-  // layer 1's backward from the rank structure of its dY (see k_dl_shift27): decided here, because with both halves in that form dL/dact1 is
-  // never formed
-  ConvDims dsh;
-  const bool rank_on = sw::raw(sw::DL_RANK_WGRAD) != 0;
-  const bool rank_dg_on = sw::raw(sw::DL_RANK_DGRAD) != 0;
-  const bool h2_1 = layer_h2_now(N, 64, p.d, 64, 5);
-  const bool have1 = kept_mask.operand(1) && kept_mask.operand_h2(1);
-  const bool rank_w = kept_mask.has(kKeptCollapsed) && rank_on && h2_1 && have1 && make_dims(dsh, N, 32, S0, S1, S2, 64, 5, 5, 5, 1, 2) &&
-                      wgrad_h2_supported(dsh) && s3_wgrad_ws_bytes(dsh) <= p.conv_ws;
-  const bool rank_dgrad = rank_w && rank_dg_on && conv_fwd_h2_c32_supported(dsh) && conv_fwd_h2_c32_ws_bytes(dsh) <= p.conv_ws;
-  const bool rank_all = rank_dgrad;
-  if (kept_mask.has(kKeptTyped)) {  // layers 1 .. 5 ran as one position-typed 7^3 kernel (dl_typed.hip): their whole backward from dy, act0 and the weights
-    hipStream_t hs = (hipStream_t)stream;
-    char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
-    char* typed = tail + align256(LTail::bytes);
-    ConvDims d0;
-    // (its kernels exist in the two-term form only and convert their fp32 operands themselves: a caller who moved nc_set_split_terms after the
-    // forward still gets this form's backward)
-    ForceTwoTerm two_;
-    if (!dl_typed_supported(N, S0, S1, S2) || !make_dims(d0, N, 1, S0, S1, S2, 64, 7, 7, 7, 1, 3) || !c1k7_h2_supported(d0) || !c1_wgrad_supported(d0)) {
-      set_error("deep_linear_bwd: the forward ran the position-typed form, which this shape does not admit");
-      return NC_ERR_ARG;
+  const LWs w = l_ws(p, ws);
+  if (!ws || ws_bytes < w.bytes) { set_error("deep_linear_bwd: workspace too small"); return NC_ERR_WS; }
+  const LBwdForms f = l_bwd_forms(p, Kept{kept});
+  if (f.error) { set_error("%s", f.error); return NC_ERR_ARG; }
+  const float *P = params, *act0 = saved + p.act[0];
+  float *DP = dparams, *g0 = w.G + p.g[0], *g1 = w.G + p.g[1];
+  hipStream_t hs = (hipStream_t)stream;
+  const float* g = dy;  // the gradient at the output of layer f.first
+  switch (f.top) {
+    case kLTopTyped: {
+      ForceTwoTerm two_;
+      NC_TRY(dl_tail_compose(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, hs));
+      const float* F = dl_fold_fwd(w.tail, P + p.w[1], hs);
+      if (!F) return NC_ERR_HIP;
+      NC_TRY(dl_typed_compose(F, w.typed, N, S0, S1, S2, hs));
+      // dL/dact0: the 1 -> 64 convolution of dy with the interior kernel (the pseudo-channel forward kernel), then the boundary voxels' differences
+      NC_TRY(conv_c1k7_h2(dy, dl_typed_wp(w.typed, N, S0, S1, S2), nullptr, g1, f.cd, w.cws, p.conv_ws, hs));
+      NC_TRY(dl_typed_dgrad_boundary(act0, dy, g1, w.typed, N, S0, S1, S2, hs));
+      // every parameter gradient through dH: the full correlation of dy and act0 (the one-channel 7^3 weight gradient with the operands' roles swapped)
+      // and the boundary types' sums -> P, then weight space as in the rank forms
+      NC_TRY(conv_wgrad_c1(dy, act0, dl_typed_dwsw(w.typed, N, S0, S1, S2), f.cd, w.cws, p.conv_ws, hs));
+      NC_TRY(dl_typed_p(act0, dy, dl_tail_P(w.tail), w.typed, N, S0, S1, S2, hs));
+      NC_TRY(dl_q_from_p(w.tail, P + p.w[1], hs));
+      NC_TRY(dl_w1_contract(w.tail, DP + p.w[1], hs));
+      NC_TRY(dl_tail_grads(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, DP + p.w[2], DP + p.w[3], DP + p.w[4], DP + p.w[5], hs));
+      g = g1;
+      break;
     }
-    const float* act0 = saved + p.act[0];
-    hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, hs, params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail);
-    hipLaunchKernelGGL(k_dl_fold_fwd, dim3(32, 64), dim3(128), 0, hs, (const float*)(tail + LTail::E), params + p.w[1], (float*)(tail + LTail::Wf));
-    NC_TRY(check_launch("deep_linear_bwd: composed kernels"));
-    NC_TRY(dl_typed_compose((const float*)(tail + LTail::Wf), typed, N, S0, S1, S2, hs));
-    // dL/dact0: the 1 -> 64 convolution of dy with the interior kernel (the pseudo-channel forward kernel), then the boundary voxels' differences
-    float* g0 = G + p.g[1];
-    NC_TRY(conv_c1k7_h2(dy, dl_typed_wp(typed, N, S0, S1, S2), nullptr, g0, d0, cws, p.conv_ws, hs));
-    NC_TRY(dl_typed_dgrad_boundary(act0, dy, g0, typed, N, S0, S1, S2, hs));
-    // every parameter gradient through dH: the full correlation of dy and act0 (the one-channel 7^3 weight gradient with the operands' roles swapped)
-    // and the boundary types' sums -> P, then weight space as in the rank forms
-    NC_TRY(conv_wgrad_c1(dy, act0, dl_typed_dwsw(typed, N, S0, S1, S2), d0, cws, p.conv_ws, hs));
-    NC_TRY(dl_typed_p(act0, dy, (float*)(tail + LTail::P), typed, N, S0, S1, S2, hs));
-    hipLaunchKernelGGL(k_dl_q_from_p, dim3(64, 27), dim3(256), 0, hs, params + p.w[1], (const float*)(tail + LTail::P), (float*)(tail + LTail::q));
-    hipLaunchKernelGGL(k_dl_w1_contract, dim3(64, 64), dim3(128), 0, hs, (const float*)(tail + LTail::E), (const float*)(tail + LTail::P), dparams + p.w[1]);
-    hipLaunchKernelGGL(k_dl_tail_w2, dim3(64), dim3(256), 0, hs, params + p.w[2], tail, dparams + p.w[2]);
-    hipLaunchKernelGGL(k_dl_tail_w345, dim3(1), dim3(256), 0, hs, params + p.w[3], params + p.w[4], params + p.w[5], (const char*)tail, dparams + p.w[3],
-                       dparams + p.w[4], dparams + p.w[5]);
-    NC_TRY(check_launch("deep_linear_bwd: typed parameter gradients"));
-    g = g0;
-    top = 0;
-  } else if (kept_mask.has(kKeptCollapsed)) {  // the forward left no act2 .. act4: layers 2 .. 5 from dy, act1 and the weights alone
-    hipStream_t hs = (hipStream_t)stream;
-    char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
-    const float* act1 = saved + p.act[1];  // (kKeptNoAct1: not there)
-    hipLaunchKernelGGL(k_dl_compose, dim3(8), dim3(256), 0, hs, params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail);
-    NC_TRY(check_launch("deep_linear_bwd: compose"));
-    if (rank_w) {
-      // the 32 x 64 weight gradient P between the 27 shifted copies of dy and act0 (see k_dl_shift27): dW1 and q are both contractions of it
-      float* Dsh = G + p.g[1];  // (free until layer 1's data gradient is written there, below)
-      hipLaunchKernelGGL(k_dl_shift27, dim3(256, 32, (unsigned)N), dim3(256), 0, hs, dy, Dsh, S0, S1, S2);
-      NC_TRY(check_launch("deep_linear_bwd: shifted copies of dy"));
-      NC_TRY(conv_wgrad_h2(Dsh, nullptr, nullptr, saved + p.xs3[1], (float*)(tail + LTail::P), dsh, cws, p.conv_ws, hs));
-      hipLaunchKernelGGL(k_dl_q_from_p, dim3(64, 27), dim3(256), 0, hs, params + p.w[1], (const float*)(tail + LTail::P), (float*)(tail + LTail::q));
-      hipLaunchKernelGGL(k_dl_w1_contract, dim3(64, 64), dim3(128), 0, hs, (const float*)(tail + LTail::E), (const float*)(tail + LTail::P), dparams + p.w[1]);
-      NC_TRY(check_launch("deep_linear_bwd: q, dW1"));
-    } else {
-      if (kept_mask.has(kKeptNoAct1)) {  // (the forward never wrote act1 and the switches changed since: form it now, in a gradient buffer)
-        NC_TRY(nc_conv_fwd(saved + p.act[0], params + p.w[1], nullptr, G + p.g[1], N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2, cws, p.conv_ws, stream));
-        act1 = G + p.g[1];
+    case kLTopTail: {
+      NC_TRY(dl_tail_compose(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, hs));
+      if (f.rank_w) {  // the shifted copies of dy in g1: free until layer 1's data gradient is written there, below
+        NC_TRY(dl_shift27(dy, g1, N, S0, S1, S2, hs));
+        NC_TRY(conv_wgrad_h2(g1, nullptr, nullptr, saved + p.xs3[1], dl_tail_P(w.tail), f.cd, w.cws, p.conv_ws, hs));
+        NC_TRY(dl_q_from_p(w.tail, P + p.w[1], hs));
+        NC_TRY(dl_w1_contract(w.tail, DP + p.w[1], hs));
+      } else {
+        const float* act1 = saved + p.act[1];
+        if (f.remake_act1) {
+          NC_TRY(nc_conv_fwd(act0, P + p.w[1], nullptr, g1, N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2, w.cws, p.conv_ws, stream));
+          act1 = g1;
+        }
+        // q (tap-flipped): the weight gradient of Conv3d(1, 64, 3) with x := dy and dY := act1
+        NC_TRY(nc_conv_wgrad(dy, act1, dl_tail_q(w.tail), nullptr, N, 1, S0, S1, S2, 64, 3, 3, 3, 1, 1, w.cws, p.conv_ws, stream));
       }
-      // q (tap-flipped): the weight gradient of Conv3d(1, 64, 3) with x := dy and dY := act1
-      NC_TRY(nc_conv_wgrad(dy, act1, (float*)(tail + LTail::q), nullptr, N, 1, S0, S1, S2, 64, 3, 3, 3, 1, 1, cws, p.conv_ws, stream));
+      NC_TRY(dl_tail_grads(P + p.w[2], P + p.w[3], P + p.w[4], P + p.w[5], w.tail, DP + p.w[2], DP + p.w[3], DP + p.w[4], DP + p.w[5], hs));
+      if (f.g1) NC_TRY(nc_conv_fwd(dy, dl_tail_Ef(w.tail), nullptr, g0, N, 1, S0, S1, S2, 64, 3, 3, 3, 1, 1, w.cws, p.conv_ws, stream));
+      g = g0;
+      if (f.rank_w) {  // layer 1's data gradient (dW1 came out of P above); layer 0 needs it whether or not dx is wanted
+        if (f.rank_dgrad) {
+          const float* Wf = dl_w1_fold(w.tail, P + p.w[1], hs);
+          if (!Wf) return NC_ERR_HIP;
+          NC_TRY(conv_fwd_h2_c32(g1, Wf, g1, f.cd, w.cws, p.conv_ws, hs));  // (converts the shifted copies into cws first: the output is their buffer)
+        } else {
+          NC_TRY(nc_conv_dgrad(g0, P + p.w[1], g1, N, 64, S0, S1, S2, 64, 5, 5, 5, 1, 2, w.cws, p.conv_ws, stream));
+        }
+        g = g1;
+      }
+      break;
     }
-    hipLaunchKernelGGL(k_dl_tail_w2, dim3(64), dim3(256), 0, hs, params + p.w[2], tail, dparams + p.w[2]);
-    hipLaunchKernelGGL(k_dl_tail_w345, dim3(1), dim3(256), 0, hs, params + p.w[3], params + p.w[4], params + p.w[5], (const char*)tail, dparams + p.w[3],
-                       dparams + p.w[4], dparams + p.w[5]);
-    NC_TRY(check_launch("deep_linear_bwd: tail gradients"));
-    // dL/dact1 = flip(E) (*) dy -- unless layer 1's whole backward runs from the shifted copies of dy (below), which never looks at it
-    if (!rank_all) NC_TRY(nc_conv_fwd(dy, (const float*)(tail + LTail::Ef), nullptr, G + p.g[0], N, 1, S0, S1, S2, 64, 3, 3, 3, 1, 1, cws, p.conv_ws, stream));
-    g = G + p.g[0];
-    top = 1;
+    case kLTopLayered:
+      break;
   }
-  for (int i = top; i >= 0; --i) {
+  for (int i = f.first; i >= 0; --i) {
     const LLayer& l = kLL[i];
     const float* in = i == 0 ? x : saved + p.act[i - 1];
-    float* gin = i == 0 ? dx : G + p.g[i & 1];
-    const bool now_h2 = layer_h2_now(N, l.C, p.d, l.K, l.k);
-    const bool have = kept_mask.operand_usable(i, now_h2);
-    if (i == 1 && rank_w && now_h2 && have) {  // the 32 x 64 problems of "layer 1's weight gradient from the rank structure of its dY" (above)
-      hipStream_t hs = (hipStream_t)stream;
-      char* tail = (char*)ws + align256(p.conv_ws) + p.grads * sizeof(float) + 256;
-      float* Dsh = G + p.g[1];  // (dW1 came out of P in the prologue; the shifted copies are still there)
-      // ... and its data gradient the same way where the planner covers it: a FORWARD 32 -> 64 convolution of Dsh with the composed weights
-      // Wf (k_dl_w1_fold) -- half the matrix work again, and g1 itself is not needed at all (rank_g1 below)
-      if (rank_dgrad) {
-        if (gin) {
-          hipLaunchKernelGGL(k_dl_w1_fold, dim3(64, 32), dim3(128), 0, hs, (const float*)(tail + LTail::E), params + p.w[1], (float*)(tail + LTail::Wf));
-          NC_TRY(check_launch("deep_linear_bwd: composed data-gradient weights"));
-          NC_TRY(conv_fwd_h2_c32(Dsh, (const float*)(tail + LTail::Wf), gin, dsh, cws, p.conv_ws, hs));  // (converts Dsh into cws first: gin may be its buffer)
-        }
-      } else {
-        NC_TRY(nc_conv_dgrad(g, params + p.w[i], gin, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2, cws, p.conv_ws, stream));
-      }
-      g = gin;
-      continue;
-    }
+    float* gin = i == 0 ? dx : w.G + p.g[i & 1];
     if (l.k > 1)
-      NC_TRY(conv_bwd_keep(in, have ? (const void*)(saved + p.xs3[i]) : nullptr, g, params + p.w[i], gin, dparams + p.w[i],
-                           N, l.C, S0, S1, S2, l.K, l.k, cws, p.conv_ws, stream));
+      NC_TRY(conv_bwd_keep(in, f.xs[i] ? (const void*)(saved + p.xs3[i]) : nullptr, g, P + p.w[i], gin, DP + p.w[i], N, l.C, S0, S1, S2, l.K, l.k,
+                           w.cws, p.conv_ws, stream));
     else
-      NC_TRY(nc_conv_bwd(in, g, params + p.w[i], gin, dparams + p.w[i], nullptr, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2, cws,
-                         p.conv_ws, stream));
+      NC_TRY(nc_conv_bwd(in, g, P + p.w[i], gin, DP + p.w[i], nullptr, N, l.C, S0, S1, S2, l.K, l.k, l.k, l.k, 1, l.k / 2, w.cws, p.conv_ws, stream));
     g = gin;
   }
   return NC_OK;

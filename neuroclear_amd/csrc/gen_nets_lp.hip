@@ -331,7 +331,7 @@ __global__ void k_lin_tail_wgrad(const float* __restrict__ W4, const float* __re
 }
 
 // Dsh[a][v] = dy[v - (a - 1)] inside the volume (27 shifts of the one-channel dy, padded to 32 channels) as a bf16 C8 tensor: the x operand of
-// layer 1's weight gradient in its rank-structured form (gen_nets.hip, "layer 1's weight gradient from the rank structure of its dY")
+// layer 1's weight gradient in its rank-structured form (dl_tail.hip, "layer 1's weight gradient from the rank structure of its dY")
 __global__ void __launch_bounds__(256) k_dl_shift27_c8(const float* __restrict__ dy, uint4* __restrict__ dsh, int D, int H, int W) {
   const long S = (long)D * H * W;
   const int q = blockIdx.y, n = blockIdx.z;  // q: chunk of 8 shifts
@@ -365,7 +365,7 @@ struct LLp {
   size_t F, A, B, q, tail, grads;                // bytes into the scratch
   size_t conv_ws, f32conv_ws, o64_ws, c1_ws;
   bool ok, c1;
-  bool c3;  // the 3^3 one-channel kernels cover the shape too: layers 2 .. 5 can run in collapsed form (gen_nets.hip, "the collapsed tail")
+  bool c3;  // the 3^3 one-channel kernels cover the shape too: layers 2 .. 5 can run in collapsed form (dl_tail.hip, "the collapsed tail")
 };
 
 bool llp_plan(LLp& p, int N, int S0, int S1, int S2) {
@@ -373,9 +373,8 @@ bool llp_plan(LLp& p, int N, int S0, int S1, int S2) {
   if (N < 1 || S0 < 1 || S1 < 1 || S2 < 1) return false;
   p.N = N; p.d[0] = S0; p.d[1] = S1; p.d[2] = S2;
   p.S = (long)S0 * S1 * S2;
-  const int ks[6] = {7, 5, 3, 1, 1, 1}, C[6] = {1, 64, 64, 64, 32, 16}, K[6] = {64, 64, 64, 32, 16, 1};
   size_t off = 0;
-  for (int i = 0; i < 6; ++i) { p.w[i] = off; off += (size_t)K[i] * C[i] * ks[i] * ks[i] * ks[i]; }
+  for (int i = 0; i < 6; ++i) { p.w[i] = off; off += (size_t)kLL[i].K * kLL[i].C * kLL[i].k * kLL[i].k * kLL[i].k; }
   const size_t n = (size_t)N, S = (size_t)p.S;
   off = 0;
   auto take = [&](size_t bytes) { size_t r = off; off += align256(bytes); return r; };
@@ -387,7 +386,7 @@ bool llp_plan(LLp& p, int N, int S0, int S1, int S2) {
   p.ok = true;
   for (int i = 1; i <= 2; ++i) {
     ConvDims cd;
-    if (!make_dims(cd, N, 64, S0, S1, S2, 64, ks[i], ks[i], ks[i], 1, ks[i] / 2) || !h_fwd_supported(cd) || !h_dgrad_supported(cd) ||
+    if (!make_dims(cd, N, 64, S0, S1, S2, 64, kLL[i].k, kLL[i].k, kLL[i].k, 1, kLL[i].k / 2) || !h_fwd_supported(cd) || !h_dgrad_supported(cd) ||
         !h_wgrad_supported(cd)) { p.ok = false; return true; }
     const size_t b = h_ws_bytes(cd);
     if (b > p.conv_ws) p.conv_ws = b;
@@ -402,7 +401,7 @@ bool llp_plan(LLp& p, int N, int S0, int S1, int S2) {
   return true;
 }
 
-// the rank-structured backward of the 5^3 layer (gen_nets.hip) is available at this shape: 32-channel shapes of the weight-gradient and
+// the rank-structured backward of the 5^3 layer (dl_tail.hip) is available at this shape: 32-channel shapes of the weight-gradient and
 // forward kernels fit the plan's workspace
 bool llp_rank_ok(const LLp& p, ConvDims& dsh) {
   const bool rank_on = sw::raw(sw::DL_RANK_WGRAD) != 0;
@@ -464,7 +463,7 @@ int nc_deep_linear_lp_fwd(const float* params, const float* x, float* y, void* s
   ConvDims dshf;
   const bool k32_on = sw::raw(sw::DL_K32) != 0;
   if (k32_on && sw::raw(sw::DL_COLLAPSE) && c1_wgrad_on() && llp_rank_ok(p, dshf)) {
-    // layers 1 .. 5 without f2 (gen_nets.hip, "the forward without act1"): Z = F (*) f1 on the first 32 channels of a 64-channel tile (half the
+    // layers 1 .. 5 without f2 (dl_tail.hip, "the forward without act1"): Z = F (*) f1 on the first 32 channels of a 64-channel tile (half the
     // matrix work of the 5^3 layer), y = its 27-term shifted sum.  The backward in its rank form does not miss f2 (q comes from P).
     char* tail = G + p.tail;
     NC_TRY(dl_tail_compose(params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail, hs));
@@ -476,7 +475,7 @@ int nc_deep_linear_lp_fwd(const float* params, const float* x, float* y, void* s
   }
   NC_TRY(conv_fwd_h_c8(V + p.f1h, params + p.w[1], nullptr, V + p.f2h, 64, 0, c5, dtype, cws, p.conv_ws, hs));
   if (p.c3 && sw::raw(sw::DL_COLLAPSE) && c1_wgrad_on()) {
-    // layers 2 .. 5 as ONE 64 -> 1 convolution of f2 (gen_nets.hip, "the collapsed tail"): the data-gradient form of the one-channel 3^3 kernel
+    // layers 2 .. 5 as ONE 64 -> 1 convolution of f2 (dl_tail.hip, "the collapsed tail"): the data-gradient form of the one-channel 3^3 kernel
     // with the tap-flipped composed weights IS that convolution.
     char* tail = G + p.tail;
     NC_TRY(dl_tail_compose(params + p.w[2], params + p.w[3], params + p.w[4], params + p.w[5], tail, hs));
@@ -513,7 +512,7 @@ int nc_deep_linear_lp_bwd(const float* params, const float* x, const void* saved
   bool rank_w1 = false;
   if (kept != kLpLayered) {  // what the FORWARD took (the switches may have moved since)
     if (!p.c3) { set_error("deep_linear_lp_bwd: `kept` names a form this shape has no kernels for"); return NC_ERR_ARG; }
-    // collapsed tail (gen_nets.hip): dW2 .. dW5 in weight space from q[c][t] = sum_v dy[v] f2[c][v + t - 1]; the 5^3 layer's backward from the rank
+    // collapsed tail (dl_tail.hip): dW2 .. dW5 in weight space from q[c][t] = sum_v dy[v] f2[c][v + t - 1]; the 5^3 layer's backward from the rank
     // structure of df2 = E . Dsh (Dsh: 27 shifted copies of dy as a bf16 C8 tensor): its weight gradient a 32 x 64 problem P, its data gradient
     // a forward convolution 32 -> 64 of Dsh with composed weights -- half the matrix work each; q is a contraction of the same P, and df2
     // itself is never written

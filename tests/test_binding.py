@@ -34,7 +34,7 @@ def test_one_prototype_per_declared_name():
     by_name = {n for n in protos if n.endswith('_bytes') or n.endswith('_bytes_debug') or n.endswith('_floats') or n == 'nc_h2_cells_offset'}
     assert {n for n, (ret, _) in protos.items() if ret is ctypes.c_size_t} == by_name
     assert [n for n, (ret, _) in protos.items() if ret is ctypes.c_char_p] == ['nc_last_error']
-    assert [n for n, (ret, _) in protos.items() if ret is ctypes.c_uint] == ['nc_unet_deconv_kept_expected']  # (a `kept` word)
+    assert [n for n, (ret, _) in protos.items() if ret is ctypes.c_uint] == ['nc_unet_deconv_kept_expected', 'nc_deep_linear_kept_expected']  # (`kept` words)
     assert all(ret in (ctypes.c_int, ctypes.c_size_t, ctypes.c_uint, ctypes.c_char_p, None) for ret, _ in protos.values())
 
 

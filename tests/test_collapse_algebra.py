@@ -1,6 +1,6 @@
 """The algebra behind the default evaluation of DeepLinearGenerator (reference models/networks.py:893-917: Conv3d 7^3 1 -> 64, 5^3, 3^3 64 -> 64,
 then 1 x 1: 64 -> 32 -> 16 -> 1; no bias, nothing between the layers, every convolution zero-pads its own input), checked on the CPU in fp64
-against torch autograd of the layer-by-layer chain -- independent of any kernel (csrc/gen_nets.hip):
+against torch autograd of the layer-by-layer chain -- independent of any kernel (csrc/dl_tail.hip):
 
   * layers 2 .. 5 are ONE 64 -> 1 convolution of act1 with E[c][t] = sum_k e[k] W2[k][c][t], e = W5 W4 W3 -- exact at the faces too;
   * dW2 .. dW5 and dL/dact1 follow from dy, act1 and the weights (q[c][t] = sum_v dy[v] act1[c][v + t - 1]);

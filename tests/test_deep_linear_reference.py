@@ -46,8 +46,8 @@ def test_restated_constants_are_the_sources():
     assert 'return lds_bytes <= 160 * 1024 && p.SD / 256 <= 8 * kC1wMaxPD && 8 * p.PRx / 256 <= 8;' in c   # :597
     assert [w for w in range(4, 260, 4) if R.c1_wgrad_admits(w)] == list(range(R.C1W_W_MIN, R.C1W_W_MAX + 1, 4))
     g = _src('gen_nets.hip')
-    assert 'constexpr unsigned kKeptTyped = 1u << 29;' in g and 'constexpr unsigned kKeptNoAct1 = 1u << 30;' in g   # :681-682
-    assert 'constexpr unsigned kKeptCollapsed = 1u << 31;' in g                                                      # :680
+    assert 'constexpr unsigned kKeptTyped = 1u << 29;' in g and 'constexpr unsigned kKeptNoAct1 = 1u << 30;' in g   # :685-686
+    assert 'constexpr unsigned kKeptCollapsed = 1u << 31;' in g                                                      # :684
 
 
 @pytest.mark.parametrize('dims', sorted({c[0][2:] for c in R.ALL_CASES.values()}))

@@ -27,7 +27,7 @@ from neuroclear_amd.models import networks  # noqa: E402
 from neuroclear_amd.util import seed as S  # noqa: E402
 
 DEV = 'cuda'
-KEPT_TYPED = 1 << 29   # kKeptTyped, csrc/gen_nets.hip:682
+KEPT_TYPED = 1 << 29   # kKeptTyped, csrc/gen_nets.hip:686
 F_FLOOR = 6e-7          # see test_forward_per_type
 
 

@@ -670,7 +670,7 @@ def test_deep_linear_collapsed_tail_equals_the_layered_chain(shape, want_dx, ter
 
 
 def test_deep_linear_backward_survives_a_switch_of_arithmetic_after_the_forward():
-    """The default forward of deep_linear_gen never writes act1 (csrc/gen_nets.hip, "the forward without act1") and its backward takes q from the
+    """The default forward of deep_linear_gen never writes act1 (csrc/dl_tail.hip, "the forward without act1") and its backward takes q from the
     32 x 64 weight gradient P -- in the two-term arithmetic.  A caller who switches to the three-term form BETWEEN a forward and its backward
     (include/nc_hip.h advises against it) must still get the right gradients: the backward sees in `kept` that act1 is missing, forms it in a
     gradient buffer and walks the first-stage collapsed path."""
