@@ -633,6 +633,9 @@ WPlan plan_swgrad(const ConvDims& d) {
   if ((pitch & 7) == 0) pitch += 4;
   const int urows = (kWNJ + d.Wo - 1) / d.Wo + 1;
   const int rows = (urows - 1) * s + 2 * 4 + s;
+  // k_swgrad decodes the input rows of a stage with ONE LANE PER ROW (rowoff, read back by readlane): a plane so thin that 64 columns span more
+  // than 64 input rows (an output width of 1, or of 2 under stride 2) stays on the gather GEMM
+  if (rows > kWNJ) return w;
   const int CS = rows * pitch + 16;  // (+16: two channels of an n-tile on different bank groups when rows * pitch is a multiple of 32)
   static const int only = 0;
   for (int NTW : {4, 2}) {

@@ -350,9 +350,9 @@ def newer_family(op, d, mode):
             return True    # conv_s3x.hip c1k7_h2_supported
     pg = d.D == 1 and d.kd == 1 and d.kh == 4 and d.kw == 4 and d.ph == 1 and d.pw == 1 and d.sh in (1, 2)
     if pg and d.C == 1 and d.sh == 2:
-        return True        # patchgan_edge.hip pg1_supported
+        return True        # patchgan_edge.hip pg1_supported (rung 8): tests/test_gpu_patchgan_fp32.py
     if pg and (d.K % 128 == 0 and d.C % 8 == 0 if op == WGRAD else red % 2 == 0 and red >= 16 and out % 64 == 0):
-        return True        # conv2d_img.hip sconv_*_supported, conv_p2d.hip p2_shape, wgrad_p2d.hip q_shape
+        return True        # conv2d_img.hip sconv_*_supported (rung 7): tests/test_gpu_patchgan_fp32.py; conv_p2d.hip p2_shape, wgrad_p2d.hip q_shape
     if op != WGRAD and d.D == 1 and d.kd == 1 and d.kh == 3 and d.sh == 1 and d.ph == 1 and red % 2 == 0 and red >= 16 and out % 64 == 0:
         return True        # conv2d_k3.hip k3_shape_ok
     if op == FWD and d.C == 1 and d.K % 64 == 0 and cubic_same and d.kd == 3 and d.W >= 8:

@@ -354,7 +354,8 @@ def test_image_staged_patchgan_convs(B, C, K, H, W, s):
     """conv2d_img.hip (k_sconv): the 4 x 4 / padding 1 PatchGAN layers at batches that fill the chip (smaller ones stay on
     the gather GEMM: last case), forward and data gradient (stride 2: four parity classes in one launch), against torch
     fp32 -- odd sizes, tiles that span three images, Athena's real + fake batch; the last four: weight-gradient stages whose
-    input rows are wider than one 64-lane copy (W = 74 / 70), odd non-square planes, 8 input channels."""
+    input rows are wider than one 64-lane copy (W = 74 / 70), odd non-square planes, 8 input channels.
+    The comparison with float64 at the smallest shapes of every planner branch: tests/test_gpu_patchgan_fp32.py."""
     import torch.nn.functional as F
     from neuroclear_amd._lib import lib
     g = torch.Generator(device=DEV).manual_seed(B * 1000 + H)
@@ -385,7 +386,8 @@ def test_image_staged_patchgan_convs(B, C, K, H, W, s):
 def test_image_staged_configs_agree(B, C, K, H, W, s):
     """The tile shape of k_sconv is picked per problem by timing (conv2d_img.hip, run_tuned).  That is only admissible because
     every shape accumulates an output element in the same order: forward and data gradient of every applicable shape must be
-    BIT-equal to the automatically chosen one."""
+    BIT-equal to the automatically chosen one.
+    Every shape against float64 at a small layer, and the timed against the heuristic choice: tests/test_gpu_patchgan_fp32.py."""
     from neuroclear_amd._lib import lib, I
     L = lib()
     g = torch.Generator(device=DEV).manual_seed(B + H)
@@ -420,7 +422,8 @@ def test_image_staged_configs_agree(B, C, K, H, W, s):
 def test_patchgan_first_layer_kernels(B, K, H, W):
     """patchgan_edge.hip: Conv2d(1 -> K, k 4, s 2, p 1) forward, weight + bias gradient (MFMA over the pixel axis, the bias as
     a column of ones) and data gradient (2 x 2 input blocks; below 128 workgroups of pixel blocks the few-planes kernel: 8 channel groups per
-    workgroup, K not a multiple of 8 included), against torch fp32 -- Athena's batch, Apollo's one to four planes, odd planes, K < 64."""
+    workgroup, K not a multiple of 8 included), against torch fp32 -- Athena's batch, Apollo's one to four planes, odd planes, K < 64.
+    The comparison with float64 at the smallest shapes of every branch: tests/test_gpu_patchgan_fp32.py."""
     import torch.nn.functional as F
     from neuroclear_amd._lib import lib
     g = torch.Generator(device=DEV).manual_seed(B * 100 + H)
