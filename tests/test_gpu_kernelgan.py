@@ -128,9 +128,11 @@ def ref64(x_np, r_np, net, nd):
     return y.detach().numpy(), x.grad.numpy(), [p.grad.numpy() for p in prm]
 
 
-@pytest.mark.parametrize('nd,shape', [(2, (3, 1, 36, 36)), (3, (1, 1, 14, 15, 16))])
+@pytest.mark.parametrize('nd,shape', [(2, (3, 1, 36, 36)), (3, (1, 1, 14, 15, 16)), (2, (2, 1, 13, 15))])
 def test_against_fp64(nd, shape, monkeypatch):
-    """The fused path's error against fp64 is no worse than twice the layered fp32 path's on the same case (y, dx, every weight)."""
+    """The fused path's error against fp64 is no worse than twice the layered fp32 path's on the same case (y, dx, every weight and every
+    bias gradient; the third shape has P = 63, P % 4 != 0: the scalar instantiation of the 1x1 kernels).  The bias gradients in front of an
+    InstanceNorm are zero up to rounding: their error is taken on the weight gradients' scale, as in test_golden."""
     net = make_net(nd)
     x_np = rnd(11, shape) - np.float32(0.5)
     oshape = (shape[0], 1) + tuple(s - 6 for s in shape[2:])
@@ -140,10 +142,14 @@ def test_against_fp64(nd, shape, monkeypatch):
     monkeypatch.setenv('NC_FUSED_KGAN', '0')
     layered = run(net, x_np, r_np)
     names = [k for k, _ in net.named_parameters()]
+    wscale = max(float(np.abs(gr).max()) for k, gr in zip(names, g64) if k.endswith('weight') and gr.ndim > 1)
     pairs = [('y', fused[0], layered[0], y64), ('dx', fused[1], layered[1], dx64)]
-    pairs += [(k, a, b, c) for k, a, b, c in zip(names, fused[2], layered[2], g64) if k.endswith('weight')]
+    pairs += list(zip(names, fused[2], layered[2], g64))
     for k, a, b, ref in pairs:
-        ea, eb = rel2(a, ref), rel2(b, ref)
+        if k.endswith('bias') and not k.startswith('final_layer'):
+            ea, eb = float(np.abs(a - ref).max()) / wscale, float(np.abs(b - ref).max()) / wscale
+        else:
+            ea, eb = rel2(a, ref), rel2(b, ref)
         print(k, ea, eb)
         assert ea <= 2 * eb + 1e-7, (k, ea, eb)
 
