@@ -803,6 +803,20 @@ int nc_kgan_fwd(const float* params, const float* x, float* y, float* saved, int
 int nc_kgan_bwd(const float* params, const float* x, const float* saved, const float* dy, float* dx, float* dparams, int B, int D, int H,
                 int W, int ndf, int nd, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Training progress views (--display_freq; csrc/views.hip).  nc_tensor2im is util.tensor2im (util/util.py:26-39) on n dense fp32
+ *      values: v = min(max(x, 0), 1) * 255.0f (out_is_u16 = 1: 65535.0f) in fp32, as numpy computes it on a float32 array, clipped to the
+ *      range again, truncating cast to uint8 / uint16 (out: n elements of that type).  NaN input is outside the contract.
+ *      nc_progress_views is what Visualizer.display_current_results shows of one visual (util/visualizer.py:138-144, 171-173): from sample 0,
+ *      channel 0 of vol[N][C][D][H][W], after tensor2im(., uint8), six arrays packed back to back into `views` (nc_progress_views_bytes):
+ *      the slices [index,:,:] (H x W), [:,index,:] (D x W), [:,:,index] (D x H), then the maxima over axis 0 (H x W), axis 1 (D x W), axis 2
+ *      (D x H); hist256[v] = the number of voxels of that sample with uint8 value v (zeroed by the call first; the sum is D*H*W).  views and
+ *      hist256 may each be NULL.  One call per visual, on the given stream, no host synchronisation; integer maxima and integer adds only, so
+ *      the bytes are the same from run to run and on every stream.  Refused before anything is written: a NULL vol (NC_ERR_ARG); an extent
+ *      below 1, index outside [0, min(D, H, W)), D*H*W >= 2^31 (NC_ERR_SHAPE).  nc_progress_views_bytes is 0 for an extent below 1. */
+int nc_tensor2im(const float* x, void* out, int out_is_u16, long n, void* stream);
+size_t nc_progress_views_bytes(int D, int H, int W);
+int nc_progress_views(const float* vol, int N, int C, int D, int H, int W, int index, uint8_t* views, uint32_t* hist256, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ header for the file:line of every call site."""
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1781,3 +1782,56 @@ def dropout(x, p=0.5, training=True):
     if not training:
         return x
     return _Dropout.apply(x, float(p))
+
+
+VIEW_KEYS = ('slice_xy', 'slice_xz', 'slice_yz', 'mip_xy', 'mip_xz', 'mip_yz')
+
+
+def tensor2im(t, imtype=np.uint16):
+    """util.tensor2im (util/util.py:11-39) of a dense fp32 tensor on the device: clip to [0, 1], scale by 255 / 65535 in fp32, clip, truncating
+    cast.  -> numpy array of t's shape, np.uint8 or np.uint16 (the copy to the host synchronises, as the reference's .cpu() does)."""
+    if imtype not in (np.uint8, np.uint16):
+        raise ValueError('tensor2im: imtype must be np.uint8 or np.uint16, got %r' % (imtype,))
+    t = t.detach().contiguous()
+    _chk(t)
+    _f32(t)
+    u16 = imtype == np.uint16
+    out = torch.empty(t.shape, dtype=torch.int16 if u16 else torch.uint8, device=t.device)
+    if t.numel():
+        check(lib().nc_tensor2im(_ptr(t), _ptr(out), 1 if u16 else 0, t.numel(), _stream()), 'nc_tensor2im')
+    a = out.cpu().numpy()
+    return a.view(np.uint16) if u16 else a
+
+
+def progress_views(t, index=None):
+    """What Visualizer.display_current_results shows of one visual (util/visualizer.py:138-144, 171-173), from one C call: the slices
+    [index,:,:], [:,index,:], [:,:,index] and the maximum projections over the three axes of tensor2im(t, uint8)[0, 0], plus `hist`, the
+    counts of its 256 values (int64).  index defaults to int(D / 2) for all three axes, as in the reference, whose errors are mirrored
+    before any launch: a tensor that is not 5-D raises ValueError (the unpack of img_shape), an index past H or W raises IndexError."""
+    if t.dim() != 5:
+        raise ValueError('progress_views: expected a [N, C, D, H, W] tensor, got %d dimensions' % t.dim())
+    N, C, D, H, W = t.shape
+    if min(N, C, D, H, W) < 1:
+        raise IndexError('progress_views: empty tensor %s' % (tuple(t.shape),))
+    if index is None:
+        index = int(D / 2)
+    index = int(index)
+    for name, ext in (('D', D), ('H', H), ('W', W)):
+        if not 0 <= index < ext:
+            raise IndexError('progress_views: index %d is out of bounds for axis %s with size %d' % (index, name, ext))
+    t = t.detach().contiguous()
+    _chk(t)
+    _f32(t)
+    L = lib()
+    nv = int(L.nc_progress_views_bytes(D, H, W))
+    hoff = (nv + 3) & ~3
+    buf = torch.empty(hoff + 1024, dtype=torch.uint8, device=t.device)  # the views, then the histogram: one copy to the host
+    check(L.nc_progress_views(_ptr(t), N, C, D, H, W, index, P(buf.data_ptr()), P(buf.data_ptr() + hoff), _stream()), 'nc_progress_views')
+    host = buf.cpu().numpy()
+    out, off = {}, 0
+    for key, shape in zip(VIEW_KEYS, ((H, W), (D, W), (D, H)) * 2):
+        n = shape[0] * shape[1]
+        out[key] = host[off:off + n].reshape(shape)
+        off += n
+    out['hist'] = host[hoff:hoff + 1024].view(np.uint32).astype(np.int64)
+    return out

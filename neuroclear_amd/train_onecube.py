@@ -1,5 +1,7 @@
 """train_onecube.py on MI355X (reference: train_onecube.py:35-110): the same loop -- random index, set_input,
-optimize_parameters, periodic loss print / checkpoint, update_learning_rate -- with the visualiser left out.
+optimize_parameters, periodic loss print / checkpoint, update_learning_rate.  With --display_freq N (N > 0; off by default) rank 0 also
+follows the run as the reference's visualiser does (util/visualizer.py): slices and maximum projections of real / fake / rec every N
+iterations, loss_log.txt, and the visuals (with --display_histogram their histograms) beside every checkpoint.
 
     python -m neuroclear_amd.train_onecube --dataroot DIR --name NAME --model axial_to_lateral_gan_apollo \\
         --preprocess randomcrop_randomflip_addColorChannel_addBatchChannel --crop_size 108 108 108 --gan_mode lsgan \\
@@ -34,6 +36,12 @@ def main(argv=None):
             torch.distributed.broadcast(o.flat, 0)
         from .util.dist import broadcast_buffers
         broadcast_buffers(model)  # (--norm batch: running statistics start equal; afterwards rank-local, rank 0's are saved -- util/dist.py)
+    visualizer = None
+    if opt.display_freq > 0 and rank == 0:  # (train_onecube.py:53, 65-66)
+        from .util.visualizer import Visualizer
+        visualizer = Visualizer(opt)
+        visualizer.reset()
+        visualizer.display_model_hyperparameters()
     total_iters = opt.load_iter + 1 if opt.load_iter > 0 else 0
     loaded = total_iters
     iter_data_time = time.time()
@@ -44,13 +52,22 @@ def main(argv=None):
         total_iters += opt.batch_size
         model.set_input(data)
         model.optimize_parameters()
+        if visualizer and total_iters % opt.display_freq == 0:
+            model.compute_visuals()
+            visualizer.display_current_results(model.get_current_visuals(), total_iters)
         if total_iters % opt.print_freq == 0 and rank == 0:
             losses = model.get_current_losses()
             t_comp = (time.time() - iter_start_time) / opt.batch_size
-            print('(iters: %d, time: %.3f, data: %.3f) ' % (total_iters, t_comp, t_data) +
-                  ' '.join('%s: %.3f' % kv for kv in losses.items()), flush=True)
+            if visualizer:
+                visualizer.print_current_losses(1, total_iters, losses, t_comp, t_data)
+            else:
+                print('(iters: %d, time: %.3f, data: %.3f) ' % (total_iters, t_comp, t_data) +
+                      ' '.join('%s: %.3f' % kv for kv in losses.items()), flush=True)
         if total_iters % opt.save_latest_freq == 0 and rank == 0:
             model.save_networks('iter_%d' % total_iters if opt.save_by_iter else 'latest')
+            if visualizer:
+                visualizer.display_current_histogram(model.get_current_visuals(), total_iters)
+                visualizer.save_current_visuals(model.get_current_visuals(), total_iters)
         model.update_learning_rate()
         iter_data_time = time.time()
         if opt.max_iters and total_iters - loaded >= opt.max_iters:
