@@ -39,9 +39,19 @@ int nc_version(void);
 /* Which implementation nc_conv_* would pick for a shape: 0 = direct (VALU), 1 = MFMA brick implicit GEMM (3^3/5^3,
  * stride 1), 2 = MFMA gather implicit GEMM (any kernel / stride), 3 = flat-voxel MFMA kernel of the 1x1 weight
  * gradient (<= 64 channels, planes of >= 16384 voxels), 4 = tap-axis MFMA kernel of the 1 -> 64 channel weight
- * gradient (3^3 / 7^3, W % 4 == 0).  The query assumes a 256^2 plane for pointwise kernels, a 32^3 volume otherwise. */
+ * gradient (3^3 / 7^3, W % 4 == 0), ... -- the path field of the profiler's cls; nc_conv_path_name gives the tag of every number.  The query
+ * assumes batch 1, a 256^2 plane for pointwise kernels, a 32^2 image / 32^3 volume otherwise, and a sufficient workspace; kernels whose
+ * coverage depends on the batch or the image (5, 7, 10, 13, the one-channel 3^3 kernel among the 1s; 8 for the weight gradient) are not
+ * reported: the answer is the one behind them. */
 int nc_conv_fwd_path(int C, int K, int kd, int kh, int kw, int stride, int pad);
 int nc_conv_wgrad_path(int C, int K, int kd, int kh, int kw, int stride, int pad);
+/* What nc_conv_fwd (op 0), nc_conv_dgrad (1) or nc_conv_wgrad (2) launch for exactly this layer under the switches as they are, called with a
+ * workspace of ws_bytes (0: ws = NULL): path | rung << 8, or -1 for dimensions the entry points refuse.  rung: the kernel family in the order
+ * the dispatch tries them (csrc/conv_route.hpp ConvRung; finer than the path).  Host arithmetic, launches nothing. */
+int nc_conv_route(int op, int N, int C, int D, int H, int W, int K, int kd, int kh, int kw, int stride, int pad, size_t ws_bytes);
+/* The tag of a profiler path (0 'direct', 1 'mfma', ... 12 'lk', 13 'k3img'; 9 and 11 are both 'split') copied to buf (cap bytes with the
+ * terminator); returns its length, 0 for a number no kernel reports. */
+int nc_conv_path_name(int path, char* buf, int cap);
 /* Test query (tests/test_gpu_conv_fp32.py): which variant of the fp32 brick kernels (csrc/conv_mfma_fwd.hip, conv_mfma_wgrad.hip) a k^3, stride 1,
  * padding k / 2 layer takes; launches nothing.  out: 8 ints (host).  what = 0 forward, 1 data gradient: cfg (0 .. 4: waves along M x waves along
  * N x position blocks 8x1x4, 8x1x2, 4x2x2, 2x4x2, 2x4x1), CK, Tz, Ty, 1 for the TAIL kernels (W % 4 != 0), nchunks, units (stream-K: tiles x

@@ -73,48 +73,56 @@ ProfScope::~ProfScope() {
   if (idx < (int)g_prof.size()) (void)hipEventRecord(g_prof[idx].e1, s);
 }
 
-// NC_SCONV=0 switches the image-staged kernels of the PatchGAN layers off (A/B runs against the gather GEMM)
-static bool sconv_on(const ConvDims& d, int dgrad) {
-  return sw::raw(sw::SCONV) && (dgrad ? sconv_dgrad_supported(d) : sconv_fwd_supported(d));
+// ---- the layer dispatch (conv_route.hpp): ONE ordered list of rungs.  conv_route walks it, nc_conv_ws_bytes takes the maximum of its workspace
+// column, and the `switch` of an entry point is the only other place a family is named.  gate: the switches that must be on.  pred / ws: per op
+// (forward, data gradient, weight gradient); no predicate = no kernel for that op.  when: nc_conv_ws_bytes counts the row's workspace always, only
+// where its predicate holds, only while its gate is open (kWsGated); kWsRequired: the CALL must bring it for the rung to be taken at all.
+enum { kOnSplit = 1, kOnK3 = 2, kOnPg1 = 4, kOnImg = 8, kOnImgWgrad = 16 };
+enum { kWsAlways = 0, kWsIfPred = 1, kWsGated = 2, kWsRequired = 4 };
+struct Rung { ConvRung rung; int path; unsigned gate; bool (*pred[3])(const ConvDims&); size_t (*ws[3])(const ConvDims&); int when; };
+static unsigned switches_on() {  // every switch of the dispatch but FORCE_DIRECT, read once
+  return (sw::raw(sw::CONV_SPLIT) ? kOnSplit : 0) | (sw::raw(sw::CONV2D_K3) ? kOnK3 : 0) | (sw::raw(sw::PG1) ? kOnPg1 : 0) |
+         (sw::raw(sw::SCONV) ? kOnImg : 0) | (sw::raw(sw::SCONV_WGRAD) ? kOnImgWgrad : 0);
 }
-// NC_PG1=0: the PatchGAN's first layer back on the generic kernels (A/B runs)
-static bool pg1_on(const ConvDims& d) {
-  return sw::raw(sw::PG1) && pg1_supported(d);
+static size_t s3_wgrad_bwd_ws_bytes(const ConvDims& d) {  // the weight gradient alone, or fused with the data gradient (nc_conv_bwd)
+  return s3_wgrad_ws_bytes(d) > s3_bwd_ws_bytes(d) ? s3_wgrad_ws_bytes(d) : s3_bwd_ws_bytes(d);
 }
-// Split-operand kernels (conv_split.hip): the fp32 3^3 / 5^3 convolutions they cover run as six bf16 MFMA products of an exact
-// three-term operand split (same operands, fp32 accumulation, error against fp64 not above the fp32 MFMA kernel's:
-// tests/test_gpu_split.py).  On by default; nc_set_conv_split(0) or NC_CONV_SPLIT=0 put those layers back on the fp32 MFMA kernels.
-// NC_S3_FUSE=0 (nc_set_s3_fusion(0)): nc_unet_deconv_fwd converts every convolution input to S3 in a separate pass (A/B, tests)
-static int fwd_path(const ConvDims& d) {
-  if (sw::raw(sw::FORCE_DIRECT)) return 0;
-  if (sw::raw(sw::CONV_SPLIT) && s3_fwd_supported(d)) return 9;
-  if (sw::raw(sw::CONV_SPLIT) && p2d_fwd_supported(d)) return 10;
-  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) in pseudo-channel form on the two-term kernels (conv_s3x.hip)
-  if (sw::raw(sw::CONV2D_K3) && conv2d_k3_fwd_supported(d)) return 12;  // Conv2d 3 x 3 of the 2-D generators, image-tiled (conv2d_k3.hip)
-  return (c1k3_fwd_supported(d) || mfma_fwd_supported(d)) ? 1 : flat_1x1_supported(d) ? 3 : k1_fwd_supported(d) ? 5 : pg1_on(d) ? 8 : sconv_on(d, 0) ? 7 : gemm_fwd_supported(d) ? 2 : 0;
-}
-static int dgrad_path(const ConvDims& d) {
-  if (sw::raw(sw::FORCE_DIRECT)) return 0;
-  if (sw::raw(sw::CONV_SPLIT) && s3_dgrad_supported(d)) return 9;
-  if (sw::raw(sw::CONV_SPLIT) && p2d_dgrad_supported(d)) return 10;
-  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7): two-term pseudo-channel form + fold (conv_s3x.hip)
-  if (sw::raw(sw::CONV2D_K3) && conv2d_k3_dgrad_supported(d)) return 12;
-  return mfma_dgrad_supported(d) ? 1 : flat_1x1_supported(d) ? 3 : to1_mfma_supported(d) ? 6 : to1_dgrad_supported(d) ? 0
-                                                                                              : pg1_on(d)             ? 8
-                                                                                              : sconv_on(d, 1)        ? 7
-                                                                                              : gemm_dgrad_supported(d) ? 2 : 0;
-}
-static bool sconv_wgrad_on(const ConvDims& d) {
-  return sw::raw(sw::SCONV) && sw::raw(sw::SCONV_WGRAD) && sconv_wgrad_supported(d);
-}
-static int wgrad_path(const ConvDims& d) {
-  if (sw::raw(sw::FORCE_DIRECT)) return 0;
-  if (sw::raw(sw::CONV_SPLIT) && s3_wgrad_supported(d)) return 9;
-  if (sw::raw(sw::CONV_SPLIT) && p2d_wgrad_supported(d)) return 10;
-  return mfma_wgrad_supported(d) ? 1 : wgrad_1x1_supported(d) ? 3 : c1_wgrad_supported(d) ? 4 : k1_wgrad_supported(d) ? 5
-                                                                                            : pg1_on(d)              ? 8
-                                                                                            : sconv_wgrad_on(d)      ? 7
-                                                                                            : gemm_wgrad_supported(d) ? 2 : 0;
+static constexpr Rung kRungs[kRungCount] = {  // (in the order of enum ConvRung: the route tries them top down)
+    // Split-operand kernels (conv_split.hip): the fp32 3^3 / 5^3 convolutions they cover as six bf16 MFMA products of an exact three-term operand
+    // split, fp32 accumulation (tests/test_gpu_split.py).  nc_set_conv_split(0) / NC_CONV_SPLIT=0: these three rungs back on the fp32 kernels.
+    {kRungS3, kPathSplit, kOnSplit, {s3_fwd_supported, s3_dgrad_supported, s3_wgrad_supported}, {s3_ws_bytes, s3_ws_bytes, s3_wgrad_bwd_ws_bytes}, kWsIfPred | kWsGated},
+    {kRungP2d, kPathSplit2d, kOnSplit, {p2d_fwd_supported, p2d_dgrad_supported, p2d_wgrad_supported}, {p2d_ws_bytes, p2d_ws_bytes, p2d_wgrad_ws_bytes}, kWsGated},
+    // Conv3d(1, 64, 7) in pseudo-channel form on the two-term kernels (conv_s3x.hip; data gradient: + fold); a call without its workspace moves on
+    {kRungC1k7, kPathC1k7, kOnSplit, {c1k7_h2_supported, c1k7_h2_supported, nullptr}, {c1k7_h2_ws_bytes, c1k7_h2_dgrad_ws_bytes, nullptr}, kWsGated | kWsRequired},
+    // Conv2d 3 x 3 of the 2-D generators, image-tiled (conv2d_k3.hip); nc_set_conv2d_k3(0): the gather GEMM (the packed weights stay counted)
+    {kRungK3Img, kPathK3Img, kOnK3, {conv2d_k3_fwd_supported, conv2d_k3_dgrad_supported, nullptr}, {conv2d_k3_ws_bytes, conv2d_k3_ws_bytes, nullptr}, kWsAlways},
+    {kRungC1k3, kPathMfma, 0, {c1k3_fwd_supported, nullptr, nullptr}, {}, kWsAlways},  // 1 -> K channels, 3^3: its own fp32 MFMA kernel
+    {kRungBrick, kPathMfma, 0, {mfma_fwd_supported, mfma_dgrad_supported, mfma_wgrad_supported}, {mfma_ws_bytes, mfma_ws_bytes, mfma_ws_bytes}, kWsAlways},
+    {kRungFlat, kPathFlat, 0, {flat_1x1_supported, flat_1x1_supported, wgrad_1x1_supported}, {nullptr, nullptr, wgrad_1x1_ws_bytes}, kWsAlways},
+    {kRungTaps, kPathTaps, 0, {nullptr, nullptr, c1_wgrad_supported}, {nullptr, nullptr, c1_wgrad_ws_bytes}, kWsAlways},
+    {kRungK1, kPathK1, 0, {k1_fwd_supported, nullptr, k1_wgrad_supported}, {}, kWsAlways},
+    {kRungTo1Mfma, kPathTo1, 0, {nullptr, to1_mfma_supported, nullptr}, {nullptr, to1_mfma_ws_bytes, nullptr}, kWsAlways},
+    {kRungTo1, kPathDirect, 0, {nullptr, to1_dgrad_supported, nullptr}, {}, kWsAlways},  // k_conv_to1: VALU, but not the direct kernel
+    // NC_PG1=0: the PatchGAN's first layer back on the generic kernels (A/B runs)
+    {kRungPg1, kPathPg1, kOnPg1, {pg1_supported, pg1_supported, pg1_supported}, {pg1_ws_bytes, pg1_ws_bytes, pg1_ws_bytes}, kWsIfPred},
+    // NC_SCONV=0: the image-staged kernels of the PatchGAN layers off (A/B runs against the gather GEMM); NC_SCONV_WGRAD=0: the weight gradient's
+    {kRungImg, kPathImg, kOnImg, {sconv_fwd_supported, sconv_dgrad_supported, nullptr}, {sconv_ws_bytes, sconv_ws_bytes, nullptr}, kWsIfPred},
+    {kRungImgWgrad, kPathImg, kOnImg | kOnImgWgrad, {nullptr, nullptr, sconv_wgrad_supported}, {nullptr, nullptr, sconv_wgrad_ws_bytes}, kWsIfPred},
+    {kRungGemm, kPathGemm, 0, {gemm_fwd_supported, gemm_dgrad_supported, gemm_wgrad_supported}, {gemm_ws_bytes, gemm_ws_bytes, gemm_ws_bytes}, kWsAlways},
+    {kRungDirect, kPathDirect, 0, {}, {}, kWsAlways},  // what is left, and everything under nc_set_force_direct(1)
+};
+static_assert([] { for (int i = 0; i < kRungCount; ++i) if (kRungs[i].rung != i) return false; return true; }(), "kRungs follows enum ConvRung");
+static const char* const kPathNames[16] = {"direct", "mfma", "gemm", "flat", "taps", "k1", "to1", "img", "pg1", "split", "split2d", "split", "lk", "k3img"};
+static const char kWsGranted = 0;  // the host queries' workspace: (&kWsGranted, SIZE_MAX) is "whatever the rung needs is there"
+int path_of(ConvRung r) { return kRungs[r].path; }
+ConvRung conv_route(int op, const ConvDims& d, const void* ws, size_t ws_bytes, unsigned skip) {
+  const unsigned on = switches_on();
+  if (!sw::raw(sw::FORCE_DIRECT))
+    for (const Rung& r : kRungs) {
+      if (!r.pred[op] || (on & r.gate) != r.gate || (skip >> r.rung & 1) || !r.pred[op](d)) continue;
+      if (!(r.when & kWsRequired) || (ws && ws_bytes >= r.ws[op](d))) return r.rung;
+    }
+  return kRungDirect;
 }
 
 }  // namespace nc
@@ -188,38 +196,38 @@ int nc_h2_guard_stats(unsigned long long* out4, int reset) {
   return h2_guard_read(out4, reset);
 }
 
+// Views of the route for callers that plan ahead.  Host arithmetic only.
 int nc_conv2d_split_active(int what, int N, int C, int H, int W, int K, int k, int stride, int pad) {
   ConvDims d;
-  if (!make_dims(d, N, C, 1, H, W, K, 1, k, k, stride, pad) || sw::raw(sw::FORCE_DIRECT) || !sw::raw(sw::CONV_SPLIT)) return 0;
-  return what == 0 ? (p2d_fwd_supported(d) ? 1 : 0) : what == 1 ? (p2d_dgrad_supported(d) ? 1 : 0) : what == 2 ? (p2d_wgrad_supported(d) ? 1 : 0) : 0;
+  return what >= 0 && what <= 2 && make_dims(d, N, C, 1, H, W, K, 1, k, k, stride, pad) && conv_route(what, d) == kRungP2d;
 }
-
 int nc_conv2d_k3_num_cfgs(void) { return conv2d_k3_num_cfgs(); }
 int nc_conv2d_k3_active(int what, int N, int C, int H, int W, int K) {
   ConvDims d;
-  if (!make_dims(d, N, C, 1, H, W, K, 1, 3, 3, 1, 1)) return 0;
-  return what == 0 ? (fwd_path(d) == 12 ? 1 : 0) : what == 1 ? (dgrad_path(d) == 12 ? 1 : 0) : 0;
+  return what >= 0 && what <= 2 && make_dims(d, N, C, 1, H, W, K, 1, 3, 3, 1, 1) && conv_route(what, d) == kRungK3Img;
 }
-
-int nc_conv_fwd_path(int C, int K, int kd, int kh, int kw, int stride, int pad) {
+// The path of a layer at a probe extent with batch 1 and every workspace granted.  The rungs that depend on the batch or the image, which these
+// queries do not take, are not reported: such a layer answers with the rung behind them.
+static int probe_path(int op, int C, int K, int kd, int kh, int kw, int stride, int pad, unsigned skip) {
   ConvDims d;
   const int e = (kd == 1 && kh == 1 && kw == 1) ? 256 : 32;  // pointwise: a plane large enough for the flat kernel
-  if (!make_dims(d, 1, C, kd > 1 ? 32 : 1, e, e, K, kd, kh, kw, stride, pad)) return -1;
-  if (sw::raw(sw::FORCE_DIRECT)) return 0;
-  if (sw::raw(sw::CONV_SPLIT) && s3_fwd_supported(d)) return 9;
-  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_supported(d)) return 11;  // Conv3d(1, 64, 7) on the two-term kernels in pseudo-channel form (round 6)
-  return mfma_fwd_supported(d) ? 1 : flat_1x1_supported(d) ? 3 : pg1_on(d) ? 8 : gemm_fwd_supported(d) ? 2 : 0;  // (the K = 1
-  // reduction kernel of the PatchGAN head and the image-staged kernels depend on the batch, which this query does not take:
-  // reported as 2)
+  return make_dims(d, 1, C, kd > 1 ? 32 : 1, e, e, K, kd, kh, kw, stride, pad) ? path_of(conv_route(op, d, &kWsGranted, SIZE_MAX, skip)) : -1;
+}
+int nc_conv_fwd_path(int C, int K, int kd, int kh, int kw, int stride, int pad) {
+  return probe_path(0, C, K, kd, kh, kw, stride, pad, 1u << kRungP2d | 1u << kRungK3Img | 1u << kRungC1k3 | 1u << kRungK1 | 1u << kRungImg);
 }
 int nc_conv_wgrad_path(int C, int K, int kd, int kh, int kw, int stride, int pad) {
+  return probe_path(2, C, K, kd, kh, kw, stride, pad, 1u << kRungP2d | 1u << kRungK1 | 1u << kRungPg1 | 1u << kRungImgWgrad);
+}
+int nc_conv_route(int op, int N, int C, int D, int H, int W, int K, int kd, int kh, int kw, int stride, int pad, size_t ws_bytes) {
   ConvDims d;
-  const int e = (kd == 1 && kh == 1 && kw == 1) ? 256 : 32;  // pointwise: a plane large enough for the flat kernel
-  if (!make_dims(d, 1, C, kd > 1 ? 32 : 1, e, e, K, kd, kh, kw, stride, pad)) return -1;
-  if (sw::raw(sw::FORCE_DIRECT)) return 0;
-  if (sw::raw(sw::CONV_SPLIT) && s3_wgrad_supported(d)) return 9;
-  return mfma_wgrad_supported(d) ? 1 : wgrad_1x1_supported(d) ? 3 : c1_wgrad_supported(d) ? 4
-                                                                         : gemm_wgrad_supported(d) ? 2 : 0;
+  if (op < 0 || op > 2 || !make_dims(d, N, C, D, H, W, K, kd, kh, kw, stride, pad)) return -1;
+  const ConvRung r = conv_route(op, d, ws_bytes ? &kWsGranted : nullptr, ws_bytes);
+  return path_of(r) | r << 8;
+}
+int nc_conv_path_name(int path, char* buf, int cap) {
+  const char* name = (path >= 0 && path < 16) ? kPathNames[path] : nullptr;
+  return (name && buf && cap > 0) ? snprintf(buf, (size_t)cap, "%s", name) : 0;  // (its length, also where cap cuts it)
 }
 
 int nc_conv_mfma_plan_debug(int what, int N, int C, int D, int H, int W, int K, int k, int* out) {
@@ -234,47 +242,14 @@ int nc_conv_mfma_plan_debug(int what, int N, int C, int D, int H, int W, int K, 
 size_t nc_conv_ws_bytes(int N, int C, int D, int H, int W, int K, int kd, int kh, int kw, int stride, int pad) {
   ConvDims d;
   if (!make_dims(d, N, C, D, H, W, K, kd, kh, kw, stride, pad)) return 0;
-  size_t b = mfma_ws_bytes(d);
-  const size_t g = gemm_ws_bytes(d);
-  if (g > b) b = g;
-  const size_t o = wgrad_1x1_ws_bytes(d);
-  if (o > b) b = o;
-  const size_t c1 = c1_wgrad_ws_bytes(d);
-  if (c1 > b) b = c1;
-  const size_t t1 = to1_mfma_ws_bytes(d);
-  if (t1 > b) b = t1;
-  if (sconv_fwd_supported(d) || sconv_dgrad_supported(d)) {
-    const size_t sc = sconv_ws_bytes(d);
-    if (sc > b) b = sc;
-  }
-  if (sconv_wgrad_supported(d)) {
-    const size_t sc = sconv_wgrad_ws_bytes(d);
-    if (sc > b) b = sc;
-  }
-  if (pg1_supported(d)) {
-    const size_t sc = pg1_ws_bytes(d);
-    if (sc > b) b = sc;
-  }
-  if (conv2d_k3_ws_bytes(d) > b) b = conv2d_k3_ws_bytes(d);  // its packed weights (whether or not the switch is on: the size does not depend on it)
-  if (sw::raw(sw::CONV_SPLIT)) {
-    size_t sc = p2d_ws_bytes(d);
-    if (sc > b) b = sc;
-    sc = p2d_wgrad_ws_bytes(d);
-    if (sc > b) b = sc;
-  }
-  if (sw::raw(sw::CONV_SPLIT) && (s3_fwd_supported(d) || s3_dgrad_supported(d))) {
-    const size_t sc = s3_ws_bytes(d);
-    if (sc > b) b = sc;
-  }
-  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_ws_bytes(d) > b) b = c1k7_h2_ws_bytes(d);
-  if (sw::raw(sw::CONV_SPLIT) && c1k7_h2_dgrad_ws_bytes(d) > b) b = c1k7_h2_dgrad_ws_bytes(d);
-  if (sw::raw(sw::CONV_SPLIT) && s3_wgrad_supported(d)) {
-    size_t sc = s3_wgrad_ws_bytes(d);
-    if (sc > b) b = sc;
-    sc = s3_bwd_ws_bytes(d);
-    if (sc > b) b = sc;
-  }
-  if (b < kBiasGradWsBytes) b = kBiasGradWsBytes;
+  const unsigned on = switches_on();
+  size_t b = kBiasGradWsBytes;
+  for (const Rung& r : kRungs)
+    for (int op = 0; op < 3; ++op) {
+      if (!r.ws[op] || ((r.when & kWsGated) && (on & r.gate) != r.gate) || ((r.when & kWsIfPred) && !r.pred[op](d))) continue;
+      const size_t n = r.ws[op](d);
+      if (n > b) b = n;
+    }
   return (b + 255) & ~(size_t)255;
 }
 
@@ -294,20 +269,22 @@ int nc_conv_fwd(const float* x, const float* w, const float* bias, float* y, int
   ConvDims d;
   if (int e = conv_args("conv_fwd", d, x, w, y, N, C, D, H, W, K, kd, kh, kw, stride, pad)) return e;
   hipStream_t s = (hipStream_t)stream;
-  const int path = fwd_path(d);
-  ProfScope ps(0, path, d, 0, s);
-  if (path == 9) return conv_fwd_s3(x, nullptr, w, bias, y, d, ws, ws_bytes, s);
-  if (path == 10) return conv_fwd_p2d(x, w, bias, y, d, ws, ws_bytes, s);
-  if (path == 11 && ws && ws_bytes >= c1k7_h2_ws_bytes(d)) return conv_c1k7_h2(x, w, bias, y, d, ws, ws_bytes, s);
-  if (path == 12) return conv_fwd_k3(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && c1k3_fwd_supported(d)) return conv_fwd_c1k3(x, w, bias, y, d, s);  // 1 -> K channels, 3^3: its own fp32 MFMA kernel
-  if (!sw::raw(sw::FORCE_DIRECT) && mfma_fwd_supported(d)) return conv_fwd_mfma(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && flat_1x1_supported(d)) return conv_fwd_1x1(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && k1_fwd_supported(d)) return conv_fwd_k1(x, w, bias, y, d, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && fwd_path(d) == 8) return conv_fwd_pg1(x, w, bias, y, d, 1.f, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && sconv_on(d, 0)) return conv_fwd_sconv(x, w, bias, y, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && gemm_fwd_supported(d)) return conv_fwd_gemm(x, w, bias, y, d, ws, ws_bytes, s);
-  return conv_fwd_direct(x, w, bias, y, d, s);
+  const ConvRung rung = conv_route(0, d, ws, ws_bytes);
+  ProfScope ps(0, path_of(rung), d, 0, s);
+  switch (rung) {
+    case kRungS3: return conv_fwd_s3(x, nullptr, w, bias, y, d, ws, ws_bytes, s);
+    case kRungP2d: return conv_fwd_p2d(x, w, bias, y, d, ws, ws_bytes, s);
+    case kRungC1k7: return conv_c1k7_h2(x, w, bias, y, d, ws, ws_bytes, s);
+    case kRungK3Img: return conv_fwd_k3(x, w, bias, y, d, ws, ws_bytes, s);
+    case kRungC1k3: return conv_fwd_c1k3(x, w, bias, y, d, s);
+    case kRungBrick: return conv_fwd_mfma(x, w, bias, y, d, ws, ws_bytes, s);
+    case kRungFlat: return conv_fwd_1x1(x, w, bias, y, d, ws, ws_bytes, s);
+    case kRungK1: return conv_fwd_k1(x, w, bias, y, d, s);
+    case kRungPg1: return conv_fwd_pg1(x, w, bias, y, d, 1.f, s);
+    case kRungImg: return conv_fwd_sconv(x, w, bias, y, d, ws, ws_bytes, s);
+    case kRungGemm: return conv_fwd_gemm(x, w, bias, y, d, ws, ws_bytes, s);
+    default: return conv_fwd_direct(x, w, bias, y, d, s);
+  }
 }
 
 int nc_conv_dgrad(const float* dy, const float* w, float* dx, int N, int C, int D, int H, int W, int K, int kd, int kh,
@@ -315,20 +292,22 @@ int nc_conv_dgrad(const float* dy, const float* w, float* dx, int N, int C, int 
   ConvDims d;
   if (int e = conv_args("conv_dgrad", d, dy, w, dx, N, C, D, H, W, K, kd, kh, kw, stride, pad)) return e;
   hipStream_t s = (hipStream_t)stream;
-  const int path = dgrad_path(d);
-  ProfScope ps(1, path, d, 0, s);
-  if (path == 9) return conv_dgrad_s3(dy, nullptr, w, dx, d, ws, ws_bytes, s);
-  if (path == 10) return conv_dgrad_p2d(dy, w, dx, d, ws, ws_bytes, s);
-  if (path == 11 && ws && ws_bytes >= c1k7_h2_dgrad_ws_bytes(d)) return conv_c1k7_h2_dgrad(dy, w, dx, d, ws, ws_bytes, s);
-  if (path == 12) return conv_dgrad_k3(dy, w, dx, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && mfma_dgrad_supported(d)) return conv_dgrad_mfma(dy, w, dx, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && flat_1x1_supported(d)) return conv_dgrad_1x1(dy, w, dx, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && to1_mfma_supported(d)) return conv_dgrad_to1_mfma(dy, w, dx, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && to1_dgrad_supported(d)) return conv_dgrad_to1(dy, w, dx, d, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && dgrad_path(d) == 8) return conv_dgrad_pg1(dy, nullptr, 1.f, w, dx, d, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && sconv_on(d, 1)) return conv_dgrad_sconv(dy, w, dx, d, ws, ws_bytes, s);
-  if (!sw::raw(sw::FORCE_DIRECT) && gemm_dgrad_supported(d)) return conv_dgrad_gemm(dy, w, dx, d, ws, ws_bytes, s);
-  return conv_dgrad_direct(dy, w, dx, d, s);
+  const ConvRung rung = conv_route(1, d, ws, ws_bytes);
+  ProfScope ps(1, path_of(rung), d, 0, s);
+  switch (rung) {
+    case kRungS3: return conv_dgrad_s3(dy, nullptr, w, dx, d, ws, ws_bytes, s);
+    case kRungP2d: return conv_dgrad_p2d(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungC1k7: return conv_c1k7_h2_dgrad(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungK3Img: return conv_dgrad_k3(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungBrick: return conv_dgrad_mfma(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungFlat: return conv_dgrad_1x1(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungTo1Mfma: return conv_dgrad_to1_mfma(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungTo1: return conv_dgrad_to1(dy, w, dx, d, s);
+    case kRungPg1: return conv_dgrad_pg1(dy, nullptr, 1.f, w, dx, d, s);
+    case kRungImg: return conv_dgrad_sconv(dy, w, dx, d, ws, ws_bytes, s);
+    case kRungGemm: return conv_dgrad_gemm(dy, w, dx, d, ws, ws_bytes, s);
+    default: return conv_dgrad_direct(dy, w, dx, d, s);
+  }
 }
 
 int nc_conv_lp_supported(int what, int N, int C, int D, int H, int W, int K, int kd, int kh, int kw, int stride, int pad) {
@@ -366,7 +345,7 @@ int nc_conv_fwd_lp(const float* x, const void* xh, const float* w, const float* 
   ConvDims d;
   if (int e = lp_args("conv_fwd_lp", d, x, xh, w, y, N, C, D, H, W, K, kd, kh, kw, stride, pad, dtype)) return e;
   if (!h_fwd_supported(d)) { set_error("conv_fwd_lp: shape not covered by the 16-bit kernels"); return NC_ERR_SHAPE; }
-  ProfScope ps(0, 1, d, 1, (hipStream_t)stream);
+  ProfScope ps(0, kPathMfma, d, 1, (hipStream_t)stream);
   return conv_fwd_h(x, xh, w, bias, y, d, dtype, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -375,7 +354,7 @@ int nc_conv_dgrad_lp(const float* dy, const void* dyh, const float* w, float* dx
   ConvDims d;
   if (int e = lp_args("conv_dgrad_lp", d, dy, dyh, w, dx, N, C, D, H, W, K, kd, kh, kw, stride, pad, dtype)) return e;
   if (!h_dgrad_supported(d)) { set_error("conv_dgrad_lp: shape not covered by the 16-bit kernels"); return NC_ERR_SHAPE; }
-  ProfScope ps(1, 1, d, 1, (hipStream_t)stream);
+  ProfScope ps(1, kPathMfma, d, 1, (hipStream_t)stream);
   return conv_dgrad_h(dy, dyh, w, dx, d, dtype, ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -389,7 +368,7 @@ int nc_conv_wgrad_lp(const float* x, const void* xh, const float* dy, const void
   if (!h_wgrad_supported(d)) { set_error("conv_wgrad_lp: shape not covered by the 16-bit kernels"); return NC_ERR_SHAPE; }
   hipStream_t s = (hipStream_t)stream;
   {
-    ProfScope ps(2, 1, d, 1, s);
+    ProfScope ps(2, kPathMfma, d, 1, s);
     if (int e = conv_wgrad_h(x, xh, dy, dyh, dw, d, dtype, ws, ws_bytes, s)) return e;
   }
   if (dbias) return bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s);  // fp32, from the fp32 dy
@@ -403,25 +382,23 @@ int nc_conv_wgrad(const float* x, const float* dy, float* dw, float* dbias, int 
   hipStream_t s = (hipStream_t)stream;
   int e;
   {
-  const int path = wgrad_path(d);
-  ProfScope ps(2, path, d, 0, s);
-  if (path == 9) e = conv_wgrad_s3(x, nullptr, dy, nullptr, dw, d, ws, ws_bytes, s);
-  else if (path == 10) e = conv_wgrad_p2d(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!sw::raw(sw::FORCE_DIRECT) && mfma_wgrad_supported(d)) e = conv_wgrad_mfma(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!sw::raw(sw::FORCE_DIRECT) && wgrad_1x1_supported(d)) e = conv_wgrad_1x1(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!sw::raw(sw::FORCE_DIRECT) && c1_wgrad_supported(d)) e = conv_wgrad_c1(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!sw::raw(sw::FORCE_DIRECT) && k1_wgrad_supported(d)) e = conv_wgrad_k1(x, dy, dw, d, s);
-  else if (!sw::raw(sw::FORCE_DIRECT) && wgrad_path(d) == 8) {  // the bias gradient is a column of the same product
-    e = conv_wgrad_pg1(x, dy, nullptr, 1.f, dw, dbias, d, ws, ws_bytes, s);
-    dbias = nullptr;
-  }
-  else if (!sw::raw(sw::FORCE_DIRECT) && sconv_wgrad_on(d)) e = conv_wgrad_sconv(x, dy, dw, d, ws, ws_bytes, s);
-  else if (!sw::raw(sw::FORCE_DIRECT) && gemm_wgrad_supported(d)) e = conv_wgrad_gemm(x, dy, dw, d, ws, ws_bytes, s);
-  else e = conv_wgrad_direct(x, dy, dw, d, s);
+    const ConvRung rung = conv_route(2, d, ws, ws_bytes);
+    ProfScope ps(2, path_of(rung), d, 0, s);
+    switch (rung) {
+      case kRungS3: e = conv_wgrad_s3(x, nullptr, dy, nullptr, dw, d, ws, ws_bytes, s); break;
+      case kRungP2d: e = conv_wgrad_p2d(x, dy, dw, d, ws, ws_bytes, s); break;
+      case kRungBrick: e = conv_wgrad_mfma(x, dy, dw, d, ws, ws_bytes, s); break;
+      case kRungFlat: e = conv_wgrad_1x1(x, dy, dw, d, ws, ws_bytes, s); break;
+      case kRungTaps: e = conv_wgrad_c1(x, dy, dw, d, ws, ws_bytes, s); break;
+      case kRungK1: e = conv_wgrad_k1(x, dy, dw, d, s); break;
+      case kRungPg1: e = conv_wgrad_pg1(x, dy, nullptr, 1.f, dw, dbias, d, ws, ws_bytes, s); dbias = nullptr; break;  // (a column of the same product)
+      case kRungImgWgrad: e = conv_wgrad_sconv(x, dy, dw, d, ws, ws_bytes, s); break;
+      case kRungGemm: e = conv_wgrad_gemm(x, dy, dw, d, ws, ws_bytes, s); break;
+      default: e = conv_wgrad_direct(x, dy, dw, d, s);
+    }
   }
   if (e) return e;
-  if (dbias) return bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s);
-  return NC_OK;
+  return dbias ? bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s) : NC_OK;
 }
 
 // ---- ReflectionPad2d(1) + Conv2d(C, K, 3) of a ResnetBlock (reference models/networks.py:808-830) as one layer.  Workspace:
@@ -455,7 +432,7 @@ int nc_conv2d_k3_reflect_fwd(const float* x, const float* w, const float* bias, 
   hipStream_t s = (hipStream_t)stream;
   const size_t pb = k3r_pad_bytes(N, C, H, W);
   if (nc_conv2d_k3_reflect_active(0, N, C, H, W, K)) {
-    ProfScope ps(0, 12, d, 0, s);
+    ProfScope ps(0, kPathK3Img, d, 0, s);
     return conv_fwd_k3_reflect(x, w, bias, y, d, (char*)ws + pb, ws_bytes - pb, s);
   }
   if (int e = reflect_pad_fwd(x, (float*)ws, (long)N * C, H, W, 1, s)) return e;
@@ -470,7 +447,7 @@ int nc_conv2d_k3_reflect_dgrad(const float* dy, const float* w, float* dx, int N
   const size_t pb = k3r_pad_bytes(N, C, H, W);
   float* dxe = (float*)ws;  // the gradient at the padded input, [N][C][H + 2][W + 2]
   if (nc_conv2d_k3_reflect_active(1, N, C, H, W, K)) {
-    ProfScope ps(1, 12, d, 0, s);
+    ProfScope ps(1, kPathK3Img, d, 0, s);
     if (int e = conv_dgrad_k3_reflect_ext(dy, w, dxe, d, (char*)ws + pb, ws_bytes - pb, s)) return e;
   } else {
     if (int e = nc_conv_dgrad(dy, w, dxe, N, C, 1, H + 2, W + 2, K, 1, 3, 3, 1, 0, (char*)ws + pb, ws_bytes - pb, stream)) return e;
@@ -487,6 +464,19 @@ int nc_conv2d_k3_reflect_wgrad(const float* x, const float* dy, float* dw, float
   return nc_conv_wgrad((const float*)ws, dy, dw, dbias, N, C, 1, H + 2, W + 2, K, 1, 3, 3, 1, 0, (char*)ws + pb, ws_bytes - pb, stream);
 }
 
+// dY to S3 form once, then the data gradient (dx nullable) and the weight gradient (xs nullable: the input already in S3 form) from it
+static int bwd_s3_fused(const float* x, const void* xs, const float* dy, const float* w, float* dx, float* dw, const ConvDims& d, void* ws,
+                        size_t ws_bytes, hipStream_t s) {
+  {
+    ProfScope ps(1, kPathSplit, d, 0, s);
+    if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 0)) return e;
+    if (dx)
+      if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 1)) return e;
+  }
+  ProfScope ps(2, kPathSplit, d, 0, s);
+  return conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 2, xs);
+}
+
 // Backward of one convolution layer: dx (nullable) and dw (+ dbias) from x, dy, w.  The same results as nc_conv_dgrad followed
 // by nc_conv_wgrad; on the split-operand kernels dY is converted to its three-term form once for both.
 int nc_conv_bwd(const float* x, const float* dy, const float* w, float* dx, float* dw, float* dbias, int N, int C, int D, int H, int W,
@@ -496,18 +486,9 @@ int nc_conv_bwd(const float* x, const float* dy, const float* w, float* dx, floa
   if (!w) { set_error("conv_bwd: null pointer"); return NC_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
   SwitchScope switches_;  // the three phases below see ONE value of every arithmetic switch
-  if (dx && dgrad_path(d) == 9 && wgrad_path(d) == 9 && ws && s3_bwd_ws_bytes(d) && ws_bytes >= s3_bwd_ws_bytes(d)) {
-    {
-      ProfScope ps(1, 9, d, 0, s);
-      if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 0)) return e;
-      if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 1)) return e;
-    }
-    {
-      ProfScope ps(2, 9, d, 0, s);
-      if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 2)) return e;
-    }
-    if (dbias) return bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s);
-    return NC_OK;
+  if (dx && conv_route(1, d) == kRungS3 && conv_route(2, d) == kRungS3 && ws && s3_bwd_ws_bytes(d) && ws_bytes >= s3_bwd_ws_bytes(d)) {
+    if (int e = bwd_s3_fused(x, nullptr, dy, w, dx, dw, d, ws, ws_bytes, s)) return e;
+    return dbias ? bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s) : NC_OK;
   }
   if (dx)
     if (int e = nc_conv_dgrad(dy, w, dx, N, C, D, H, W, K, kd, kh, kw, stride, pad, ws, ws_bytes, stream)) return e;
@@ -521,9 +502,9 @@ int conv_fwd_keep(const float* x, const float* w, const float* bias, float* y, i
                   void* ws, size_t ws_bytes, void* stream, void* xs_keep, bool* kept, const S3xPrepared* prep) {
   ConvDims d;
   *kept = false;
-  if (xs_keep && make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && fwd_path(d) == 9 && wgrad_path(d) == 9) {
+  if (xs_keep && make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && conv_route(0, d) == kRungS3 && conv_route(2, d) == kRungS3) {
     if (!x || !w || !y) { set_error("conv_fwd: null pointer"); return NC_ERR_ARG; }
-    ProfScope ps(0, 9, d, 0, (hipStream_t)stream);
+    ProfScope ps(0, kPathSplit, d, 0, (hipStream_t)stream);
     *kept = true;
     return conv_fwd_s3(x, nullptr, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream, xs_keep, nullptr, prep);
   }
@@ -533,26 +514,26 @@ int conv_fwd_keep(const float* x, const float* w, const float* bias, float* y, i
 // Does the 3^3 / 5^3 layer run forward AND weight gradient on the split-operand kernels (then producers may hand it its input in S3 form)?
 bool conv_keep_supported(int N, int C, int D, int H, int W, int K, int ks) {
   ConvDims d;
-  return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && fwd_path(d) == 9 && wgrad_path(d) == 9;
+  return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && conv_route(0, d) == kRungS3 && conv_route(2, d) == kRungS3;
 }
 // ... the forward alone (the inference forward, unet_fwd.hip)?
 bool conv_fwd_on_split(int N, int C, int D, int H, int W, int K, int ks) {
   ConvDims d;
-  return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && fwd_path(d) == 9;
+  return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && conv_route(0, d) == kRungS3;
 }
 
 // The 1 x 1 layer behind an InstanceNorm + (Leaky)ReLU without the stored activation (conv_1x1.hip, the NORM forms): taken only where nc_conv_fwd
 // AND nc_conv_wgrad would put the layer on the two flat kernels now, whose products and order the forms keep.
 bool norm_1x1_taken(int N, int C, int D, int H, int W, int K) {
   ConvDims d;
-  return make_dims(d, N, C, D, H, W, K, 1, 1, 1, 1, 0) && fwd_path(d) == 3 && wgrad_path(d) == 3 && norm_1x1_supported(d);
+  return make_dims(d, N, C, D, H, W, K, 1, 1, 1, 1, 0) && conv_route(0, d) == kRungFlat && conv_route(2, d) == kRungFlat && norm_1x1_supported(d);
 }
 int conv_fwd_norm_1x1(const float* raw, const float* mean, const float* rstd, float slope, const float* w, const float* bias, float* y, int N, int C,
                       int D, int H, int W, int K, void* ws, size_t ws_bytes, void* stream) {
   ConvDims d;
   if (int e = conv_args("conv_fwd_norm_1x1", d, raw, w, y, N, C, D, H, W, K, 1, 1, 1, 1, 0)) return e;
   if (!mean || !rstd) { set_error("conv_fwd_norm_1x1: null pointer"); return NC_ERR_ARG; }
-  ProfScope ps(0, 3, d, 0, (hipStream_t)stream);
+  ProfScope ps(0, kPathFlat, d, 0, (hipStream_t)stream);
   return conv_fwd_1x1_norm(raw, mean, rstd, slope, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream);
 }
 int conv_wgrad_norm_1x1(const float* raw, const float* mean, const float* rstd, float slope, const float* dy, float* dw, float* dbias, int N, int C,
@@ -562,7 +543,7 @@ int conv_wgrad_norm_1x1(const float* raw, const float* mean, const float* rstd, 
   if (!mean || !rstd) { set_error("conv_wgrad_norm_1x1: null pointer"); return NC_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
   {
-    ProfScope ps(2, 3, d, 0, s);
+    ProfScope ps(2, kPathFlat, d, 0, s);
     if (int e = conv_wgrad_1x1_norm(raw, mean, rstd, slope, dy, dw, d, ws, ws_bytes, s)) return e;
   }
   if (dbias) return bias_grad(dy, dbias, d.N, d.K, (long)d.Do * d.Ho * d.Wo, ws, ws_bytes, s);  // (as nc_conv_wgrad)
@@ -574,8 +555,8 @@ int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, in
                  size_t ws_bytes, void* stream, float* stats_part, const S3xPrepared* prep) {
   ConvDims d;
   if (!xs || !w || !y) { set_error("conv_fwd_pre: null pointer"); return NC_ERR_ARG; }
-  if (!make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) || fwd_path(d) != 9) { set_error("conv_fwd_pre: layer not on the split-operand kernels"); return NC_ERR_SHAPE; }
-  ProfScope ps(0, 9, d, 0, (hipStream_t)stream);
+  if (!make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) || conv_route(0, d) != kRungS3) { set_error("conv_fwd_pre: layer not on the split-operand kernels"); return NC_ERR_SHAPE; }
+  ProfScope ps(0, kPathSplit, d, 0, (hipStream_t)stream);
   if (stats_part && !(conv_layer_h2(d) && ks == 3)) { set_error("conv_fwd_pre: epilogue statistics exist for the two-term 3^3 layers only"); return NC_ERR_ARG; }
   return conv_fwd_s3(nullptr, xs, w, bias, y, d, ws, ws_bytes, (hipStream_t)stream, nullptr, stats_part, prep);
 }
@@ -583,8 +564,8 @@ int conv_fwd_pre(const void* xs, const float* w, const float* bias, float* y, in
 // Can the backward of the layer take dY in S3 form at the head of its workspace (conv_bwd_pre)?  want_dx: the data gradient is needed too
 bool conv_bwd_pre_supported(int N, int C, int D, int H, int W, int K, int ks, bool want_dx, size_t ws_bytes) {
   ConvDims d;
-  return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && wgrad_path(d) == 9 && s3_bwd_ws_bytes(d) && ws_bytes >= s3_bwd_ws_bytes(d) &&
-         (!want_dx || dgrad_path(d) == 9);
+  return make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && conv_route(2, d) == kRungS3 && s3_bwd_ws_bytes(d) && ws_bytes >= s3_bwd_ws_bytes(d) &&
+         (!want_dx || conv_route(1, d) == kRungS3);
 }
 // data (dx nullable) + weight gradient with dY ALREADY in S3 form at the start of ws (where conv_bwd_s3's conversion phase puts it);
 // xs (nullable): the layer's input in S3 form, else it is converted from x
@@ -598,29 +579,19 @@ int conv_bwd_pre(const float* x, const void* xs, const float* w, float* dx, floa
   }
   if ((!x && !xs) || !w || !dw || !ws) { set_error("conv_bwd_pre: null pointer"); return NC_ERR_ARG; }
   if (dx) {
-    ProfScope ps(1, 9, d, 0, s);
+    ProfScope ps(1, kPathSplit, d, 0, s);
     if (int e = conv_bwd_s3(x, nullptr, w, dx, dw, d, ws, ws_bytes, s, 1, nullptr, dy_guarded, prep)) return e;
   }
-  ProfScope ps(2, 9, d, 0, s);
+  ProfScope ps(2, kPathSplit, d, 0, s);
   return conv_bwd_s3(x, nullptr, w, dx, dw, d, ws, ws_bytes, s, 2, xs, dy_guarded);
 }
 
 int conv_bwd_keep(const float* x, const void* xs, const float* dy, const float* w, float* dx, float* dw, int N, int C, int D, int H,
                   int W, int K, int ks, void* ws, size_t ws_bytes, void* stream) {
   ConvDims d;
-  hipStream_t s = (hipStream_t)stream;
-  if (xs && make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2) && wgrad_path(d) == 9 && ws && s3_bwd_ws_bytes(d) &&
-      ws_bytes >= s3_bwd_ws_bytes(d) &&
-      (!dx || dgrad_path(d) == 9)) {
+  if (xs && ws && conv_bwd_pre_supported(N, C, D, H, W, K, ks, dx != nullptr, ws_bytes) && make_dims(d, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2)) {
     if (!x || !dy || !w || !dw) { set_error("conv_bwd: null pointer"); return NC_ERR_ARG; }
-    {
-      ProfScope ps(1, 9, d, 0, s);
-      if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 0)) return e;
-      if (dx)
-        if (int e = conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 1)) return e;
-    }
-    ProfScope ps(2, 9, d, 0, s);
-    return conv_bwd_s3(x, dy, w, dx, dw, d, ws, ws_bytes, s, 2, xs);
+    return bwd_s3_fused(x, xs, dy, w, dx, dw, d, ws, ws_bytes, (hipStream_t)stream);
   }
   return nc_conv_bwd(x, dy, w, dx, dw, nullptr, N, C, D, H, W, K, ks, ks, ks, 1, ks / 2, ws, ws_bytes, stream);
 }

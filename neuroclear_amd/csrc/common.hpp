@@ -6,6 +6,7 @@
 #include <cstdio>
 
 #include "../../include/nc_hip.h"
+#include "conv_route.hpp"
 #include "switches.hpp"
 
 namespace nc {

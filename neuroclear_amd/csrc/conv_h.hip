@@ -1101,7 +1101,7 @@ int conv_fwd_h(const float* x, const void* xh, const float* w, const float* b, f
 int conv_fwd_h_c8(const void* xh, const float* w, const float* b, void* yh, int ctot, int c0, const ConvDims& d, int dt,
                   void* ws, size_t wsb, hipStream_t s) {
   const long T3 = (long)d.kd * d.kh * d.kw;
-  ProfScope ps(0, 1, d, 1, s);
+  ProfScope ps(0, kPathMfma, d, 1, s);
   if (dt == NC_DT_F16) return run_h<NC_DT_F16>(nullptr, xh, w, b, nullptr, d, d.C, d.K, d.C * T3, T3, 0, ws, wsb, s, yh, ctot, c0);
   return run_h<NC_DT_BF16>(nullptr, xh, w, b, nullptr, d, d.C, d.K, d.C * T3, T3, 0, ws, wsb, s, yh, ctot, c0);
 }
@@ -1112,14 +1112,14 @@ int conv_fwd_h_c8(const void* xh, const float* w, const float* b, void* yh, int 
 int conv_fwd_h_na1(const void* xh, const float* w, float* y, const ConvDims& d, int dt, void* ws, size_t wsb, hipStream_t s) {
   if (dt != NC_DT_BF16 || d.K != 64 || d.kd != 5 || !h_fwd_supported(d)) { set_error("conv_fwd_h_na1: shape not covered"); return NC_ERR_SHAPE; }
   ConvDims dh = d;
-  ProfScope ps(0, 1, dh, 1, s);
+  ProfScope ps(0, kPathMfma, dh, 1, s);
   return run_h<NC_DT_BF16>(nullptr, xh, w, nullptr, y, d, d.C, d.K, (long)d.C * 125, 125, 0, ws, wsb, s, nullptr, 0, 0, true);
 }
 
 int conv_dgrad_h_c8(const void* dyh, const float* w, void* dxh, int ctot, int c0, const ConvDims& d, int dt, void* ws,
                     size_t wsb, hipStream_t s) {
   const long T3 = (long)d.kd * d.kh * d.kw;
-  ProfScope ps(1, 1, d, 1, s);
+  ProfScope ps(1, kPathMfma, d, 1, s);
   if (dt == NC_DT_F16) return run_h<NC_DT_F16>(nullptr, dyh, w, nullptr, nullptr, d, d.K, d.C, T3, d.C * T3, 1, ws, wsb, s, dxh, ctot, c0);
   return run_h<NC_DT_BF16>(nullptr, dyh, w, nullptr, nullptr, d, d.K, d.C, T3, d.C * T3, 1, ws, wsb, s, dxh, ctot, c0);
 }
@@ -1136,7 +1136,7 @@ int conv_c1_fwd_h(const float* x, const float* w, const float* bias, void* yh, i
                   int dt, void* ws, size_t wsb, hipStream_t s) {
   ConvDims d;
   make_dims(d, N, 1, D, H, W, 64, KS, KS, KS, 1, KS / 2);
-  ProfScope ps(0, 1, d, 1, s);
+  ProfScope ps(0, kPathMfma, d, 1, s);
   if (dt == NC_DT_F16) return run_c1_fwd<NC_DT_F16>(x, w, bias, yh, ctot, c0, N, D, H, W, KS, ws, wsb, s);
   return run_c1_fwd<NC_DT_BF16>(x, w, bias, yh, ctot, c0, N, D, H, W, KS, ws, wsb, s);
 }
@@ -1144,7 +1144,7 @@ int conv_c1_dgrad_h(const void* dyh, const float* w, float* dx, int N, int D, in
                     hipStream_t s) {
   ConvDims d;
   make_dims(d, N, 1, D, H, W, 64, KS, KS, KS, 1, KS / 2);
-  ProfScope ps(1, 1, d, 1, s);
+  ProfScope ps(1, kPathMfma, d, 1, s);
   return run_c1_dgrad<NC_DT_BF16>(dyh, w, dx, N, D, H, W, KS, ws, wsb, s);
 }
 

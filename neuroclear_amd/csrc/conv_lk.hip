@@ -407,8 +407,6 @@ int lk_args(const char* what, ConvDims& d, const void* a, const void* b, const v
   return NC_OK;
 }
 
-constexpr int kLkPath = 12;  // profiler path code of these kernels
-
 }  // namespace
 }  // namespace nc
 
@@ -429,7 +427,7 @@ int nc_lk_fwd(const float* x, const float* w, float* y, int N, int D, int H, int
   ConvDims d;
   if (int e = lk_args("lk_fwd", d, x, w, y, N, D, H, W, k)) return e;
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(0, kLkPath, d, 0, s);
+  ProfScope ps(0, kPathLk, d, 0, s);
   return lk_fwd_any(x, w, y, N, D, H, W, k, 0, s);
 }
 
@@ -439,7 +437,7 @@ int nc_lk_dgrad(const float* dy, const float* w, float* dx, int N, int D, int H,
   ConvDims d;
   if (int e = lk_args("lk_dgrad", d, dy, w, dx, N, D, H, W, k)) return e;
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(1, kLkPath, d, 0, s);
+  ProfScope ps(1, kPathLk, d, 0, s);
   return lk_fwd_any(dy, w, dx, N, D, H, W, k, 1, s);
 }
 
@@ -450,7 +448,7 @@ int nc_lk_wgrad(const float* x, const float* dy, float* dw, int N, int D, int H,
   const size_t need = nc_lk_ws_bytes(N, D, H, W, k);
   if (!ws || ws_bytes < need) { set_error("lk_wgrad: workspace %zu < %zu bytes", ws_bytes, need); return NC_ERR_WS; }
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(2, kLkPath, d, 0, s);
+  ProfScope ps(2, kPathLk, d, 0, s);
   return lk_wgrad_any(x, dy, dw, N, D, H, W, k, ws, s);
 }
 

@@ -233,7 +233,7 @@ int nc_unet_deconv_lp_bwd(const float* params, const float* x, const float* y, c
     NC_TRY(c8_instnorm_bwd(g, gctot, gc0, V + p.raw[i], F(p.mean[i]), F(p.rstd[i]), 0.f, draw, DP + o.b[i], N, b.K, Sl, dt, u.c8ws,
                            p.c8_ws, hs));
     if (gin) NC_TRY(conv_dgrad_h_c8(draw, P + o.w[i], gin, b.C, 0, cd, NC_DT_BF16, u.cws, p.conv_ws, hs));
-    ProfScope ps(2, 1, cd, 1, hs);
+    ProfScope ps(2, kPathMfma, cd, 1, hs);
     return conv_wgrad_h(nullptr, in, nullptr, draw, DP + o.w[i], cd, NC_DT_BF16, u.cws, p.conv_ws, hs);
   };
   // head
@@ -525,7 +525,7 @@ int nc_deep_linear_lp_bwd(const float* params, const float* x, const void* saved
       hipLaunchKernelGGL(k_dl_shift27_c8, dim3(512, 4, (unsigned)N), dim3(256), 0, hs, dy, (uint4*)(G + p.B), S0, S1, S2);
       NC_TRY(check_launch("deep_linear_lp_bwd: shifted copies of dy"));
       {
-        ProfScope ps(2, 1, dsh, 1, hs);
+        ProfScope ps(2, kPathMfma, dsh, 1, hs);
         NC_TRY(conv_wgrad_c8x(G + p.B, V + p.f1h, dl_tail_P(tail), dsh, NC_DT_BF16, cws, p.conv_ws, hs));
       }
       NC_TRY(dl_q_from_p(tail, params + p.w[1], hs));
@@ -552,14 +552,14 @@ int nc_deep_linear_lp_bwd(const float* params, const float* x, const void* saved
   NC_TRY(check_launch("lin_tail_wgrad"));
   // 3^3 layer
   {
-    ProfScope ps(2, 1, c3, 1, hs);
+    ProfScope ps(2, kPathMfma, c3, 1, hs);
     NC_TRY(conv_wgrad_h(nullptr, V + p.f2h, nullptr, G + p.A, dparams + p.w[2], c3, NC_DT_BF16, cws, p.conv_ws, hs));
   }
   NC_TRY(conv_dgrad_h_c8(G + p.A, params + p.w[2], G + p.B, 64, 0, c3, NC_DT_BF16, cws, p.conv_ws, hs));
   }
   // 5^3 layer: its data gradient feeds the fp32 one-channel 7^3 kernels, so it leaves as fp32 NCDHW
   if (!rank_w1) {
-    ProfScope ps(2, 1, c5, 1, hs);
+    ProfScope ps(2, kPathMfma, c5, 1, hs);
     NC_TRY(conv_wgrad_h(nullptr, V + p.f1h, nullptr, G + p.B, dparams + p.w[1], c5, NC_DT_BF16, cws, p.conv_ws, hs));
   }
   float* Ff = (float*)(G + p.F);
@@ -577,7 +577,7 @@ int nc_deep_linear_lp_bwd(const float* params, const float* x, const void* saved
     return nc_conv_wgrad(x, Ff, dparams + p.w[0], nullptr, N, 1, S0, S1, S2, 64, 7, 7, 7, 1, 3, fws, p.f32conv_ws, stream);
   }
   {
-    ProfScope ps(1, 1, c5, 1, hs);
+    ProfScope ps(1, kPathMfma, c5, 1, hs);
     NC_TRY(conv_dgrad_h(nullptr, G + p.B, params + p.w[1], Ff, c5, NC_DT_BF16, cws, p.conv_ws, hs));
   }
   // 7^3 layer (fp32)

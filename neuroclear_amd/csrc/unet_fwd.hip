@@ -115,7 +115,7 @@ struct Fwd {
     ConvDims cd;
     make_dims(cd, bn, k.C, e[0], e[1], e[2], k.K, 3, 3, 3, 1, 1);
     {
-      ProfScope ps(0, 9, cd, 0, hs);
+      ProfScope ps(0, kPathSplit, cd, 0, hs);
       NC_TRY(conv_s3x_h2(in3, in_a, in_b, in_b ? split_c : k.C, w(i), b(i), raw(), bn, k.C, e[0], e[1], e[2], k.K, 3, (long)k.C * 27, 27, 0,
                          (unsigned*)cws(), (char*)cws() + 256, hs, nullptr, epi ? stats() : nullptr));
     }
@@ -133,7 +133,7 @@ struct Fwd {
     ConvDims cd;
     make_dims(cd, 1, k.C, e[0], e[1], e[2], k.K, 3, 3, 3, 1, 1);
     {
-      ProfScope ps(0, 9, cd, 0, hs);
+      ProfScope ps(0, kPathSplit, cd, 0, hs);
       NC_TRY(conv_fwd_s3(nullptr, in3, w(i), b(i), raw(), cd, cws(), u.conv_ws_bytes, hs));
     }
     return stats_sample(i, 0);

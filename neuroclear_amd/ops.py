@@ -26,15 +26,23 @@ def prof_start(min_flop=0.0):
     lib().nc_prof_begin(min_flop)
 
 
-_PATH = {0: 'direct', 1: 'mfma', 2: 'gemm', 3: 'flat', 4: 'taps', 5: 'k1', 6: 'to1', 7: 'img', 8: 'pg1', 9: 'split', 10: 'split2d', 11: 'split',
-         12: 'lk'}
+_PATH = {}   # path number -> tag, read from the library (nc_conv_path_name) the first time a profile is taken
+
+
+def _path_names():
+    if not _PATH:
+        buf = ctypes.create_string_buffer(32)
+        for path in range(16):
+            if lib().nc_conv_path_name(path, buf, len(buf)) > 0:
+                _PATH[path] = buf.value.decode()
+    return _PATH
 
 
 def prof_stop():
     """-> ({tag: [launches, ms, flop, algorithmic bytes]} of the convolution launches, [(tag, flop, ms)] of the whole-network calls).  The
     caller has synchronised the device."""
     global prof
-    L = lib()
+    L, names = lib(), _path_names()
     cap = 1 << 16
     cls, flop, ms, ab = (ctypes.c_int * cap)(), (ctypes.c_double * cap)(), (ctypes.c_float * cap)(), (ctypes.c_double * cap)()
     n = min(L.nc_prof_end2(cap, cls, flop, ms, ab), cap)
@@ -42,7 +50,7 @@ def prof_stop():
     for i in range(n):
         c = cls[i]
         op, path, k, lp = ('fwd', 'dgrad', 'wgrad')[c & 15], (c >> 4) & 15, (c >> 8) & 255, (c >> 16) & 1
-        tag = '%s_lp_k%d' % (op, k) if lp else '%s_%s_k%d' % (op, _PATH.get(path, '?'), k)
+        tag = '%s_lp_k%d' % (op, k) if lp else '%s_%s_k%d' % (op, names.get(path, '?'), k)
         s = stats.setdefault(tag, [0, 0.0, 0.0, 0.0])
         s[0] += 1
         s[1] += ms[i]

@@ -338,8 +338,8 @@ def direct_branch(op, d):
 
 
 def newer_family(op, d, mode):
-    """True where a kernel family that has its own op-level file may take the layer in front of the ladder below (api.hip fwd_path / dgrad_path /
-    wgrad_path, the rungs 9 .. 12, 8 and 7, and conv_c1k3.hip): stated as the NECESSARY conditions of those predicates, so that False is certain.
+    """True where a kernel family that has its own op-level file may take the layer in front of the ladder below (api.hip kRungs: the
+    paths 9 .. 11, 13, 8 and 7, and conv_c1k3.hip): stated as the NECESSARY conditions of those predicates, so that False is certain.
     The case lists stay out of them."""
     cubic_same = d.kd == d.kh == d.kw and d.sd == d.sh == d.sw == 1 and d.pd == d.ph == d.pw == d.kd // 2
     red, out = (d.C, d.K) if op != DGRAD else (d.K, d.C)
@@ -361,7 +361,7 @@ def newer_family(op, d, mode):
 
 
 def dispatch(op, d, mode):
-    """(path, branch): the rung of api.hip's fwd_path / dgrad_path / wgrad_path a layer reaches under a mode -- the number the profiler reports in
+    """(path, branch): the path of the rung of api.hip's kRungs (conv_route) a layer reaches under a mode -- the number the profiler reports in
     cls -- and the kernel behind it.  Brick variants are left to nc_conv_mfma_plan_debug ('brick'); NO_WS changes no path."""
     if mode == DIRECT:
         return 0, direct_branch(op, d)
@@ -527,7 +527,7 @@ DGRAD_CASES = [
     (1, 1, 64, (5, 6, 16), 7, 1, 3, NO_SPLIT, 'to1_mfma/1'),
     (1, 1, 64, (7, 8, 116), 7, 1, 3, NO_SPLIT, 'to1_mfma/2'),
     (2, 1, 64, (5, 30, 24), 7, 1, 3, NO_SPLIT, 'to1_mfma/1'),
-    # conv_c1.hip k_conv_to1<7> (dgrad_path reports it as rung 0)
+    # conv_c1.hip k_conv_to1<7> (reported as path 0, its own rung)
     (1, 1, 8, (5, 6, 18), 7, 1, 3, NO_SPLIT, 'to1_dgrad'),
     (1, 1, 64, (5, 6, 18), 7, 1, 3, NO_SPLIT, 'to1_dgrad'),
     # conv_mfma_fwd.hip as the data gradient (Cin = K, Cout = C)

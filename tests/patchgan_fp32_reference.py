@@ -265,7 +265,7 @@ def p2d_may_take(op, d):
 
 
 def dispatch(op, d):
-    """(rung, branch) of api.hip:88 fwd_path / :96 dgrad_path / :110 wgrad_path for a 2-D 4 x 4 padding-1 layer with rung 10 out of the way
+    """(path, branch) of the rung api.hip's kRungs (conv_route) gives a 2-D 4 x 4 padding-1 layer with rung 10 out of the way
     (no other rung in front of 8 takes a 4 x 4 layer with K > 1): pg1 (8), the image-staged kernels (7), else the gather GEMM (2)."""
     assert d.D == 1 and d.kd == 1 and d.kh == 4 and d.kw == 4 and d.ph == 1 and d.K > 1
     if pg1_supported(d):

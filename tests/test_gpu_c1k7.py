@@ -130,3 +130,30 @@ def test_layer_is_on_the_new_path_and_falls_back_when_told():
         assert _path(1, 64) == 1
     finally:
         ops.set_conv_split(True)
+
+
+@pytest.mark.parametrize('op,path_behind', [(0, 1), (1, 6)], ids=['fwd', 'dgrad'])
+def test_without_a_workspace_the_layer_is_routed_past_the_pseudo_channel_kernels(op, path_behind):
+    """Conv3d(1, 64, 7) at (5, 6, 16) with ws = NULL: the pseudo-channel form needs a workspace, so the call goes to the rung behind it -- the
+    fp32 brick kernel forward, to1_mfma for the data gradient -- and that rung refuses it with NC_ERR_WS before anything is launched.  The commit
+    before the dispatch became one table did exactly that (recorded from a build of it: NC_ERR_WS for both ops, output untouched) while its
+    profiler recorded path 11; cls now carries the rung that ran."""
+    import ctypes
+    N, D, H, W = 1, 5, 6, 16
+    g = torch.Generator(device=DEV).manual_seed(17)
+    a = torch.rand(N, 1 if op == 0 else 64, D, H, W, device=DEV, generator=g)
+    w = torch.randn(64, 1, 7, 7, 7, device=DEV, generator=g) * 0.05
+    out = torch.full((N, 64 if op == 0 else 1, D, H, W), float('nan'), device=DEV)
+    full = lib().nc_conv_ws_bytes(N, 1, D, H, W, 64, 7, 7, 7, 1, 3)
+    assert lib().nc_conv_route(op, N, 1, D, H, W, 64, 7, 7, 7, 1, 3, full) & 255 == 11
+    assert lib().nc_conv_route(op, N, 1, D, H, W, 64, 7, 7, 7, 1, 3, 0) & 255 == path_behind
+    cls, flop, ms = (ctypes.c_int * 4)(), (ctypes.c_double * 4)(), (ctypes.c_float * 4)()
+    st = ops._stream()
+    lib().nc_prof_begin(0.0)
+    if op == 0:
+        code = lib().nc_conv_fwd(ops._ptr(a), ops._ptr(w), None, ops._ptr(out), N, 1, D, H, W, 64, 7, 7, 7, 1, 3, None, 0, st)
+    else:
+        code = lib().nc_conv_dgrad(ops._ptr(a), ops._ptr(w), ops._ptr(out), N, 1, D, H, W, 64, 7, 7, 7, 1, 3, None, 0, st)
+    torch.cuda.synchronize()
+    assert lib().nc_prof_end(4, cls, flop, ms) == 1 and cls[0] == op | path_behind << 4 | 7 << 8
+    assert code == -2 and bool(torch.isnan(out).all())   # NC_ERR_WS, nothing written

@@ -176,3 +176,24 @@ def test_a_pinned_configuration_that_does_not_exist_is_the_launchers_choice():
         y = run(0, N, C, K, H, W)
     with k3(on=1, cfg=7):
         assert torch.equal(run(0, N, C, K, H, W), y)
+
+
+def test_the_profiler_reports_the_kernel_under_its_own_path():
+    """Path 13 / 'k3img' (12 is the learned-PSF kernels' number, 'lk'): cls of one forward and one data-gradient call at the smallest layer of
+    K3_CASES both cover, and the tag ops.prof_stop() makes of it."""
+    import ctypes
+    from neuroclear_amd import ops
+    N, C, K, H, W = min((c[:5] for c in R.K3_CASES if R.k3_covered(0, *c[:5]) and R.k3_covered(1, *c[:5])), key=lambda c: c[0] * c[1] * c[3] * c[4])
+    cls, flop, ms = (ctypes.c_int * 4)(), (ctypes.c_double * 4)(), (ctypes.c_float * 4)()
+    with k3(on=1):
+        L().nc_prof_begin(0.0)
+        run(0, N, C, K, H, W)
+        run(1, N, C, K, H, W)
+        assert L().nc_prof_end(4, cls, flop, ms) == 2
+        assert [cls[0], cls[1]] == [0 | 13 << 4 | 3 << 8, 1 | 13 << 4 | 3 << 8]
+        assert L().nc_conv_route(0, N, C, 1, H, W, K, 1, 3, 3, 1, 1, 0) & 255 == 13
+        ops.prof_start()
+        run(0, N, C, K, H, W)
+        run(1, N, C, K, H, W)
+        stats, _ = ops.prof_stop()
+    assert sorted(stats) == ['dgrad_k3img_k3', 'fwd_k3img_k3'] and all(v[0] == 1 for v in stats.values())

@@ -45,7 +45,7 @@ class _Recorder:
                 return self._npar[0]
             if ret is ctypes.c_size_t:
                 return 640
-            if name.endswith('_supported') or name.endswith('_active') or name in ('nc_conv_fwd_path', 'nc_conv_wgrad_path'):
+            if name.endswith('_supported') or name.endswith('_active') or name in ('nc_conv_fwd_path', 'nc_conv_wgrad_path', 'nc_conv_route', 'nc_conv_path_name'):
                 return 1
             return 0 if ret is ctypes.c_int else None
         fn.__name__ = name
